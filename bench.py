@@ -5,6 +5,15 @@
                                                             `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
                                                             --master-addr 127.0.0.1 ... bench.py <same flags>`; under a launcher
                                                             it reads RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*)
+    python bench.py ... --full                             also every side measurement below (sustained phase, PMC traffic,
+                                                            extra legs, cpu_baseline; with N > 1 the tensor-parallel leg)
+    python bench.py ... --dump-outputs DIR                 after the timed steps, rank 0 writes what its last step returned:
+                                                            DIR/decode_out.npy, float32 [1, 4096] (inputs are seeded: two builds
+                                                            run with the same flags can be compared output for output)
+
+A plain run (no --full) sets up, warms up, times exactly K steps (HIP events and a host clock around them, ending in a
+device synchronise), writes the outputs if asked, and prints the line: metric, value, unit, higher_is_better, dtype,
+ms_per_step (= wall time of the K steps / K), config and roofline (from the timed steps' events; traffic null).
 
 Workload (config.workload = "llama2-7b-awq-w4-g128-decode-b1"): BASELINE.json configs[1] -- the 32 x 7 quantized
 linears of Llama-2-7B in the AWQ "GEMM" pack mode, w4 g128 asymmetric zeros, batch 1.  ONE STEP = one decode token
@@ -21,14 +30,15 @@ value = decode tokens/s over all ranks (rank r runs an independent replica: batc
 no data-path collective -> "scaling": "weak").  `--tp N` instead runs the Llama-2-70B column/row-parallel layer stack
 (BASELINE configs[4]) with one RCCL all-reduce per Megatron pair; see tp_leg().
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (a plain run carries `roofline` alone, with `traffic` null; the rest needs --full):
   roofline     dominant kernel = the decode matvec (one kernel function serves every launch of the step).
                achieved = algorithmic bytes per launch (packed weights + scales + zeros + x + y,
                3,369,484,288 B per token / launches) / average launch duration, the latter measured here with HIP events
                on the launch stream over the K timed steps (= event time / launches: inter-kernel gaps included).
                traffic = HBM bytes per launch from two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE; separate passes,
                FETCH doubled per MI355X_MICROARCH.md) that THIS run spawns on itself (`--pmc-child`, 8 layers, the same
-               kernels); null if rocprofv3 is absent.
+               kernels); null if rocprofv3 is absent or without --full.
+  sustained    the same graph replayed on after the K steps until the GPU has been busy --min-timed-s in all.
   cpu_baseline the reference's CPU torch formulation (oracle/ref_torch.py: shift/mask dequant + fp16 torch.matmul,
                bit-identical to the oracle) timed on this host's cores over one decoder layer (3 warm + 5 timed calls per
                shape, thread count picked by a short sweep and stated), extrapolated x32.
@@ -420,7 +430,7 @@ def stub_main(args, world, rank):
               "data": "STUB (QLLM_BENCH_STUB=1: launch-path test on CPU, not a measurement)",
               "config": {"workload": "stub", "parallelism": f"replicas x{world}", "backend": "gloo" if world > 1 else None},
               "roofline": None, "cpu_baseline": None}
-    if world > 1:   # the same second leg as the real run: every rank enters it, rank 0 gets the record (watchdog included)
+    if world > 1 and args.full:   # the same second leg as the real run: every rank enters it, rank 0 gets the record (watchdog included)
         from tools import tp_bench
         tp_leg_guarded(result, rank, lambda: tp_bench.stub_measure(args, world, rank), args.tp_timeout_s)
     if rank == 0:
@@ -471,16 +481,25 @@ def main():
     ap.add_argument("--tp", type=int, default=0, help="Llama-2-70B tensor-parallel leg (BASELINE configs[4]); 1 = shard shapes on one GPU")
     ap.add_argument("--tp-layers", type=int, default=0, help="--tp: decoder layers of the stack (default: all 80)")
     ap.add_argument("--tp-timeout-s", type=float, default=420.0,
-                    help="--gpus N > 1: seconds the tensor-parallel leg behind extra.tp70b may take before the line is printed without it")
-    ap.add_argument("--no-tp-leg", action="store_true", help="--gpus N > 1: replicas only, no extra.tp70b")
-    ap.add_argument("--no-extra", action="store_true", help="skip the per-shape / prefill / CPU legs")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 PMC passes behind roofline.traffic")
+                    help="--full, --gpus N > 1: seconds the tensor-parallel leg behind extra.tp70b may take before the line is printed without it")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement run every side measurement too: the sustained phase, the PMC passes, the "
+                         "extra legs, cpu_baseline and (--gpus N > 1) the tensor-parallel leg; a plain run does none of them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output (rank 0) to DIR/decode_out.npy as float32")
+    ap.add_argument("--no-tp-leg", action="store_true", help="--full, --gpus N > 1: replicas only, no extra.tp70b")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the per-shape / prefill / CPU legs")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: skip the rocprofv3 PMC passes behind roofline.traffic")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--pmc-child-prefill", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--min-timed-s", type=float, default=8.0,
-                    help="after the K timed steps keep replaying until the GPU has been busy this long (reported as `sustained`; "
-                         "the headline numbers are those of exactly K steps)")
+                    help="--full: after the K timed steps keep replaying until the GPU has been busy this long (reported as "
+                         "`sustained`; the headline numbers are those of exactly K steps)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.tp:
+        ap.error("--dump-outputs writes the decode step of the headline run; --tp runs another workload")
     if args.pmc_child_prefill:
         return pmc_child_prefill()
 
@@ -520,7 +539,7 @@ def main():
     n_layers = 8 if args.pmc_child else LAYERS
     fused = bool(args.fused)
     stack = Stack(WQLinear_GEMM, n_layers, dev, seed=1234 + rank, fused=fused)
-    h0 = torch.randn(1, HIDDEN, device=dev, dtype=torch.float16)
+    h0 = torch.randn(1, HIDDEN, device=dev, dtype=torch.float16, generator=torch.Generator(device=dev).manual_seed(4321 + rank))
     graph, out = capture(decode_step_fn(stack, h0))
     torch.cuda.synchronize()
     assert torch.isfinite(out.float()).all(), "synthetic stack diverged"
@@ -552,11 +571,16 @@ def main():
         wall, ev_ms = float(t[0]), float(t[1])
     if args.pmc_child:
         return
+    if args.dump_outputs and rank == 0:
+        # `out` is the graph's output buffer: after the barrier it holds what the last timed replay computed
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "decode_out.npy"), out.float().cpu().numpy())
     # sustained phase: the K timed steps are tens of milliseconds; keep the same graph replaying until the GPU has been busy for
     # --min-timed-s in all, so that an outside observer (a utilisation sampler around this process) sees the work.  Reported
     # beside the headline numbers, which stay those of exactly K steps.
     sustained = None
-    if args.min_timed_s > 0:
+    if args.full and args.min_timed_s > 0:
         n_more = max(0, int((args.min_timed_s - wall) / max(wall / args.steps, 1e-6)))
         if n_more:
             t1 = time.perf_counter()
@@ -573,8 +597,8 @@ def main():
     avg_launch_us = ev_ms * 1e3 / (args.steps * launches)
     achieved = (bpt / launches) / (avg_launch_us * 1e-6) / 1e9
 
-    traffic, traffic_source = None, "skipped (--no-pmc / --no-extra / multi-GPU run: rank 0 of a 1-GPU run collects it)"
-    if rank == 0 and world == 1 and not args.no_pmc and not args.no_extra:
+    traffic, traffic_source = None, "skipped (no --full / --no-pmc / --no-extra / multi-GPU run: rank 0 of a 1-GPU --full run collects it)"
+    if args.full and rank == 0 and world == 1 and not args.no_pmc and not args.no_extra:
         del graph
         traffic, traffic_source = pmc_traffic(args)
 
@@ -597,7 +621,7 @@ def main():
                      "bytes_per_launch": bpt // launches, "avg_launch_us": round(avg_launch_us, 3)},
     }
 
-    if rank == 0 and world == 1 and not args.no_extra:
+    if args.full and rank == 0 and world == 1 and not args.no_extra:
         extra = {}
         # per-shape decode bandwidth (32 distinct weight sets per shape => HBM resident, not cache resident), ordinary launches
         stack.set_fused(False)
@@ -710,9 +734,9 @@ def main():
     elif rank == 0:
         result["cpu_baseline"] = None
 
-    if world > 1 and not args.no_tp_leg:
+    if world > 1 and args.full and not args.no_tp_leg:
         # BASELINE configs[4] on the ranks of THIS run: Llama-2-70B column / row-parallel over `world` GPUs, one all-reduce per
-        # Megatron pair (tools/tp_bench.measure) -- the driver's scaling run only ever passes --gpus N, so the leg rides on its line
+        # Megatron pair (tools/tp_bench.measure) -- with --full the leg rides on the `--gpus N` line
         from tools import tp_bench
         try:
             del graph

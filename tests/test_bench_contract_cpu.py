@@ -23,7 +23,7 @@ def test_algorithmic_bytes_and_flops():
 
 def test_command_line_contract():
     src = open(os.path.join(ROOT, "bench.py")).read()
-    for flag in ("--gpus", "--steps", "--warmup"):
+    for flag in ("--gpus", "--steps", "--warmup", "--full", "--dump-outputs"):
         assert f'"{flag}"' in src
     assert 'add_argument("--gpus", type=int, default=1)' in src
     for key in ('"metric"', '"value"', '"unit"', '"n_gpus"', '"ms_per_step"', '"higher_is_better"', '"scaling"', '"vs_baseline"', '"dtype"',
@@ -42,7 +42,7 @@ def test_gpus_n_starts_its_own_ranks():
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["QLLM_BENCH_STUB"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"],
                        env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -57,12 +57,21 @@ def test_gpus_n_starts_its_own_ranks():
         assert key in tp, key
     assert tp["ranks_seen"] == 2 and tp["backend"] == "gloo" and tp["tp_degree"] == 2 and "stub" in tp
     # a rank stuck in the leg's collectives must not cost the run its line: the watchdog prints the replica numbers with an error entry
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--tp-timeout-s", "4"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
+                        "--tp-timeout-s", "4"],
                        env=dict(env, QLLM_BENCH_STUB_HANG="1"), capture_output=True, text=True, timeout=240)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, (r.stdout, r.stderr[-2000:])
     rec = json.loads(lines[0])
     assert rec["n_gpus"] == 2 and "timeout" in rec["extra"]["tp70b"]["error"]
+    # without --full the line is the replica measurement alone
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"],
+                       env=env, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    rec = json.loads(lines[0])
+    assert rec["n_gpus"] == 2 and rec["steps"] == 3 and "extra" not in rec
     # under a launcher that set WORLD_SIZE the flag must agree with it
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], env=dict(env, WORLD_SIZE="3", RANK="0"),
                        capture_output=True, text=True, timeout=60)

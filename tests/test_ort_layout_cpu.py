@@ -61,7 +61,8 @@ def _layer_from_golden(g):
     layer.pack(lin, torch.from_numpy(g["scales"]).float().T.contiguous(), z_arg.T.contiguous(), torch.from_numpy(g["g_idx"]).clone())
     if g["bias"] is not None:
         layer.bias = torch.from_numpy(g["bias"]).clone()
-    return layer
+    # pack() runs on the GPU when one is visible and the ORT blobs stay where they were packed: bring them to the host
+    return layer.cpu()
 
 
 @pytest.mark.parametrize("name", ort_golden_names())

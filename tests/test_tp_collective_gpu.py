@@ -324,7 +324,7 @@ def test_bench_gpus_2_carries_the_tensor_parallel_leg():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["QLLM_BENCH_SHARE_GPU0"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--tp-layers", "4",
-                        "--min-timed-s", "0"], env=env, capture_output=True, text=True, timeout=900)
+                        "--min-timed-s", "0", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-3000:]

@@ -3,7 +3,7 @@ all-reduce per Megatron pair.  Used by bench.py:
 
     python -m torch.distributed.run --nproc-per-node 8 ... bench.py --gpus 8 --tp 8     the real thing (one rank per GPU)
     python bench.py --tp 1                                                            the per-rank shard shapes, no collective
-    bench.py (default run)                                                            extra.tp_shard_* via shard_shapes_leg()
+    bench.py --full                                                                   extra.tp_shard_* via shard_shapes_leg()
 
 Per rank and layer at TP = P (hidden 8192, 64 heads / 8 KV heads, intermediate 28672, 80 layers):
     q/k/v   column-parallel, 8192 -> (8192 + 2 x 1024) / P, one grouped launch (sibling group), output stays sharded
@@ -194,7 +194,7 @@ def measure(args, world, rank, dev, info):
     """The tensor-parallel leg on `world` ranks (or 1 rank running the TP=8 shard shapes without a collective): returns the record
     on rank 0, None on the others.  EVERY rank must call it (collectives inside).  `args.tp_layers` (default: all 80) shortens the
     stack for smoke runs (tests/test_tp_collective_gpu.py drives this function with two gloo ranks on one GPU, so that the first
-    8-GPU lease is not its first execution).  Callers: run() (`bench.py --tp N`) and bench.py's `--gpus N` run, which puts the
+    8-GPU lease is not its first execution).  Callers: run() (`bench.py --tp N`) and bench.py's `--gpus N --full` run, which puts the
     record on its JSON line as extra.tp70b (round-5 verdict: the driver only ever passes --gpus N)."""
     import torch.distributed as dist
     P = world if world > 1 else 8
