@@ -150,6 +150,10 @@ int qllm_workspace_init(void *workspace, size_t bytes, void *stream);
  * Fused widths: 4 bits everywhere; 3 bits (GPTQ / HQQ row stream; fp16, symmetric or packed zero points) for M <= 64 and, with
  * K % 64 == 0, N % 128 == 0 and fp16 activations, for every larger M; every other width / shape returns QLLM_ERR_UNSUPPORTED and the
  * caller takes the reference's own two-step branch (qllm_dequant + a dense GEMM, quant_linear_gptq.py:81-85).
+ * Native 4-bit layers at M > 64 need K % 64 == 0 and a power-of-two group size; N % 128 == 0, or (round 7, Falcon-7B's 4544 / 4672)
+ * N % 128 == 64 on single layers: the prefill kernel's last column tile is then half wide (plan string " n_tail=64"), split over K
+ * where the tiles leave CUs idle -- qllm_workspace_bytes covers those splits.  At batch 1 the native 4-bit layers with 64-wide groups
+ * take K % 128 == 64 too (the batch-1 kernel); the fused all-reduce entry keeps to 128-wide groups.
  * Replaces QuantLinearTorchFunction.forward + bias for all three layouts. */
 int qllm_linear_forward(const qllm_weight_t *w, const void *x, void *y, int32_t M, int32_t act_dtype,
                         void *workspace, size_t workspace_bytes, void *stream);

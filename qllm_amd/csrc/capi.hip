@@ -333,7 +333,8 @@ static bool strip_plan(const qllm_weight_t *w, int n, int M, StripPlan *plan) {
         // (round 6: 3-bit layers too -- batch 1, K <= 16384; QLLM_STRIP1_3BIT = 0 keeps them on the general kernel)
         const bool w4 = bits == 4 && (w[0].group_size == 128 || (w[0].group_size == 64 && s1 != 2 && w[0].K <= 24576));
         const bool w3 = bits == 3 && (w[0].group_size == 128 || w[0].group_size == 64) && w[0].K <= 16384 && knob("QLLM_STRIP1_3BIT", 1);
-        if (M == 1 && (w4 || w3) && s1 && strip1_shape(w[0].K, strips, compute_units(), &nw1, &maxs1)) {
+        // (round 7: K % 128 == 64 -- Falcon-7B's 4544 -- on the 4-bit 64-wide-group forms: strip1_shape)
+        if (M == 1 && (w4 || w3) && s1 && strip1_shape(w[0].K, strips, compute_units(), &nw1, &maxs1, w4 && w[0].group_size == 64)) {
           plan->one_nw = nw1;
           plan->one_maxs = maxs1;
         }
@@ -525,11 +526,12 @@ static size_t usable_ws(const void *workspace, size_t workspace_bytes) {
   return (workspace && (uintptr_t)workspace % 256 == 0) ? workspace_bytes : 0;
 }
 // gemm3 over K-split blocks when the 256x128 tiling leaves CUs idle and the workspace can hold the partial tiles: the split, or 1
+// (round 7: a half-wide last column tile is a tile -- and a 256x128 slab -- of its own: gemm3_tile_cols)
 static int gemm3_split_for(int M, int N, int K, size_t ws_bytes) {
   const int S = gemm3_split_k(M, N, K);
   if (S <= 1) return 1;
-  const int tiles = ((M + 255) / 256) * (N / 128);
-  if (ws_bytes < kCounterBytes + gemm2_slab_bytes(M, N, S) || tiles > (int)(kCounterBytes / sizeof(int))) return 1;
+  const int tiles = ((M + 255) / 256) * (gemm3_tile_cols(N) / 128);
+  if (ws_bytes < kCounterBytes + gemm2_slab_bytes(M, gemm3_tile_cols(N), S) || tiles > (int)(kCounterBytes / sizeof(int))) return 1;
   return S;
 }
 static int gemm2_split_for(int M, int N, int K, size_t ws_bytes) {
@@ -547,7 +549,7 @@ static int panel_split_for(int M, int n_panels, int K, size_t ws_bytes) {
 // gemm3's K-split of the ragged last round (gemm3.hip, round 6): the factor (1: none) and the first split tile
 static size_t gemm3_tail_slab_bytes(int tail_tiles, int TS) { return TS > 1 ? (size_t)tail_tiles * TS * 256 * 128 * sizeof(float) : 0; }
 static int gemm3_tail_for(int M, int N, int K, size_t ws_bytes, int *tail_from) {
-  const int tiles = ((M + 255) / 256) * (N / 128);
+  const int tiles = ((M + 255) / 256) * (gemm3_tile_cols(N) / 128);
   const int TS = gemm3_tail_split(M, N, K, tail_from);
   if (TS <= 1 || ws_bytes < kCounterBytes + gemm3_tail_slab_bytes(tiles - *tail_from, TS) || tiles - *tail_from > (int)(kCounterBytes / sizeof(int))) {
     *tail_from = tiles;
@@ -612,11 +614,11 @@ static TileChoice choose_tile(const GemmParams &p, int layout, size_t ws_bytes) 
     if (gemm2_split_k(p.M, p.N, p.K) == 1 || S3 > 1) {
       const int native = p.act_bf16 && gemm3_bf16_native(layout);
       const size_t copy = native ? 0 : bf16_copy_bytes(p.M, p.K, p.act_bf16);
-      const int tiles = ((p.M + 255) / 256) * (p.N / 128);
+      const int tiles = ((p.M + 255) / 256) * (gemm3_tile_cols(p.N) / 128);
       int tail_from = tiles;
       // (the slabs of the tail split and the fp16 copy of bf16 activations share the workspace: the copy comes first)
       const int TS = S3 > 1 ? 1 : gemm3_tail_for(p.M, p.N, p.K, ws_bytes > copy ? ws_bytes - copy : 0, &tail_from);
-      const size_t used = kCounterBytes + (S3 > 1 ? align_up(gemm2_slab_bytes(p.M, p.N, S3), 256) : align_up(gemm3_tail_slab_bytes(tiles - tail_from, TS), 256));
+      const size_t used = kCounterBytes + (S3 > 1 ? align_up(gemm2_slab_bytes(p.M, gemm3_tile_cols(p.N), S3), 256) : align_up(gemm3_tail_slab_bytes(tiles - tail_from, TS), 256));
       if (!copy || ws_bytes >= used + copy) return TileChoice{3, S3, used, tail_from, TS, native};
     }
   }
@@ -626,6 +628,8 @@ static TileChoice choose_tile(const GemmParams &p, int layout, size_t ws_bytes) 
 static int run_tile_gemm(GemmParams &p, int layout, void *workspace, size_t workspace_bytes, hipStream_t stream) {
   const TileChoice c = choose_tile(p, layout, usable_ws(workspace, workspace_bytes));
   set_split(p, c.split_k, workspace, c.tail_from, c.tail_split);
+  if (c.kernel == 2 && p.N % 128 != 0)  // (half-wide last tile: gemm2 has no such form; bf16 with QLLM_GEMM3_BF16=0 needs the fp16 copy)
+    return set_error(QLLM_ERR_WORKSPACE, "N %% 128 == 64 with bf16 activations converted to fp16: the workspace must hold the copy (call qllm_workspace_bytes_act)");
   if (c.kernel == 2) return launch_gemm2(p, layout, stream);
   if (c.native_bf16) {
     p.native_bf16 = 1;
@@ -719,7 +723,13 @@ static bool native_prefill_ok(const qllm_weight_t *w, GemmParams &p) {
   if ((uintptr_t)w->qweight % 16 || (uintptr_t)w->scales % 16 || (w->qzeros && (uintptr_t)w->qzeros % 8)) return false;
   if (panel_serves(w, p)) return true;
   if (w->bits == 3) return gemm3_ok(p, kGemm3Rows3Bit);
-  return w->bits == 4 && gemm2_ok(p, QLLM_LAYOUT_GPTQ);
+  if (w->bits != 4) return false;
+  if (gemm2_ok(p, QLLM_LAYOUT_GPTQ)) return true;
+  // round 7: N % 128 == 64 (Falcon-7B's 4544 / 4672) -- gemm3's half-wide last tile, whatever the activation type (choose_tile decides
+  // how gemm3 takes bf16)
+  GemmParams q = p;
+  q.act_bf16 = 0;
+  return gemm3_n_tail(q, QLLM_LAYOUT_GPTQ) && gemm3_ok(q, QLLM_LAYOUT_GPTQ);
 }
 
 // ---- ONE decision per forward call (round 6; round-5 verdict, weak #8: qllm_plan_describe used to restate this order by hand) -------
@@ -943,9 +953,10 @@ static void describe(const Decision &d, const qllm_weight_t *w, int n, int M, si
       GemmParams p;
       fill_gemm_params(p, &w[0], nullptr, nullptr, M, QLLM_F16);
       const TileChoice c = choose_tile(p, d.layout, ws_bytes);
-      if (c.kernel == 3 && c.tail_split > 1) snprintf(buf, buflen, "gemm3 tile=256x128 matrix-waves=8 staging-waves=4 tail_split=%d%s", c.tail_split, sm);
-      else if (c.kernel == 3 && c.split_k > 1) snprintf(buf, buflen, "gemm3 tile=256x128 matrix-waves=8 staging-waves=4 split_k=%d%s", c.split_k, sm);
-      else if (c.kernel == 3) snprintf(buf, buflen, "gemm3 tile=256x128 matrix-waves=8 staging-waves=4%s", sm);
+      const char *nt = w[0].N % 128 ? " n_tail=64" : "";  // (round 7: the half-wide last column tile)
+      if (c.kernel == 3 && c.tail_split > 1) snprintf(buf, buflen, "gemm3 tile=256x128 matrix-waves=8 staging-waves=4 tail_split=%d%s%s", c.tail_split, nt, sm);
+      else if (c.kernel == 3 && c.split_k > 1) snprintf(buf, buflen, "gemm3 tile=256x128 matrix-waves=8 staging-waves=4 split_k=%d%s%s", c.split_k, nt, sm);
+      else if (c.kernel == 3) snprintf(buf, buflen, "gemm3 tile=256x128 matrix-waves=8 staging-waves=4%s%s", nt, sm);
       else snprintf(buf, buflen, "gemm2 tile=256x%d split_k=%d%s", gemm2_tile_n(M, w[0].N, c.split_k), c.split_k, sm);
       return;
     }
@@ -1060,8 +1071,11 @@ size_t qllm_workspace_bytes_act(const qllm_weight_t *w, int32_t M, int32_t act_d
     const bool g3 = gemm3_ok(p, w->bits == 3 ? kGemm3Rows3Bit : (w->layout == QLLM_LAYOUT_AWQ_GEMM ? QLLM_LAYOUT_AWQ_GEMM : QLLM_LAYOUT_GPTQ));
     int tail_from = 0;
     const int TS = g3 && w->bits != 3 ? gemm3_tail_split(M, w->N, w->K, &tail_from) : 1;  // (the ragged last round's K-split, gemm3.hip)
-    const size_t tail = align_up(gemm3_tail_slab_bytes(((M + 255) / 256) * (w->N / 128) - tail_from, TS), 256);
-    tiles = std::max(align_up(gemm2_slab_bytes(M, w->N, gemm2_split_k(M, w->N, w->K)), 256), tail) + (g3 ? bf16_copy_bytes(M, w->K, act_dtype == QLLM_BF16) : 0);
+    const size_t tail = align_up(gemm3_tail_slab_bytes(((M + 255) / 256) * (gemm3_tile_cols(w->N) / 128) - tail_from, TS), 256);
+    // (round 7: gemm3's own split-K -- the only one a layer with a half-wide last tile has; never more than gemm2's elsewhere)
+    const size_t split3 = g3 ? align_up(gemm2_slab_bytes(M, gemm3_tile_cols(w->N), gemm3_split_k(M, w->N, w->K)), 256) : 0;
+    tiles = std::max(std::max(align_up(gemm2_slab_bytes(M, w->N, gemm2_split_k(M, w->N, w->K)), 256), split3), tail) +
+            (g3 ? bf16_copy_bytes(M, w->K, act_dtype == QLLM_BF16) : 0);
     if (M > 64 && M > 128) return kCounterBytes + tiles;
   }
   // the panel kernel's partial panels (single native 4-bit layers, 9..128 rows)

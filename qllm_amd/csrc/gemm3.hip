@@ -52,6 +52,10 @@ __device__ __forceinline__ int tile_off(int row, int slot) { return row * BK + (
 // a half k-tile are 3 consecutive word rows of the column).  p.sm (LAYOUT 0 / 2): the same words stored strip-major (the native
 // layout, include/qllm_mi355x.h): only the loop-constant per-lane offsets and the row strides change -- a thread's four words are
 // 4 x 64 B apart inside its strip instead of 4 x 4N B apart.  fp16 activations.  Requires K % 64 == 0, N % 128 == 0, power-of-two group size >= 32, no g_idx.
+// Round 7, half-wide last tile (single strip-major 4-bit layers with N % 128 == 64: Falcon-7B's 4544 / 4672): the layer has ceil(N / 128)
+// column tiles and the last one holds 64 live columns.  Its staging waves for columns >= N (waves MW+1, MW+3: bcol 64..127) read column
+// N - 1's words / scale / zero point again instead (never past the layer's buffers) and fill B columns nobody consumes; its matrix waves
+// with wn = 1 run the k-loop as usual (their DMA pieces feed wn = 0's rows) and leave before the epilogue: no bias read, no store.
 // MW: matrix waves, 4 (one per SIMD, 128x64 each) or 8 (two per SIMD, 64x64 each: 8 fragment reads per 8 MFMAs instead of 6,
 // but the two waves cover each other's LDS / barrier waits); always 4 dequant waves behind them.
 // BF (round 6, LAYOUT 0 only): NATIVE bf16 -- the activation tiles are the caller's bf16 rows as they are (LDS-DMA moves bytes), the
@@ -80,7 +84,7 @@ __global__ __launch_bounds__((MW + 4) * 64) void gemm3_kernel(const GemmParams p
   // layer 1's ...; a block looks its layer up from its tile id and takes that layer's pointers and width (P* below).  The rounds of
   // tiles are counted over the whole group: gate/up of Llama-2-7B are 1376 tiles = 5.4 rounds instead of 2 x 2.7 -> 2 x 3.
   const int tiles_m = (p.M + BM - 1) / BM;
-  const int tiles_all = p.n_prob > 1 ? p.total_tiles : tiles_m * (p.N / BN);
+  const int tiles_all = p.n_prob > 1 ? p.total_tiles : tiles_m * ((p.N + BN - 1) / BN);  // (a half-wide last column tile counts as one)
   // split-K (p.split_k > 1: fewer tiles than CUs): S consecutive block ids share an output tile and own consecutive K ranges;
   // each publishes its fp32 partial tile to a slab, the last to arrive sums them in fixed order (the protocol of gemm2.hip)
   // Round 6, tail split (p.tail_split > 1, tiles > CUs): the tiles of the whole rounds run unsplit; the tiles of the ragged last round
@@ -123,13 +127,15 @@ __global__ __launch_bounds__((MW + 4) * 64) void gemm3_kernel(const GemmParams p
     Pqweight = q.qweight; Pscales = q.scales; Pbias = q.bias; Pqzeros = q.qzeros; Py = q.y;
     PN = q.N; Pzk = q.zero_kind; bid = tile_id - q.tile_begin;
   }
-  const int tiles_n = PN / BN;
+  const int tiles_n = (PN + BN - 1) / BN;
   // p.raster 1: n fastest (an XCD's run shares activation rows, which stay in its L2 while the small packed weights stream)
   const int tm = p.raster ? (bid / tiles_n) : (bid % tiles_m);
   const int tn = p.raster ? (bid % tiles_n) : (bid / tiles_m);
   const int m0 = tm * BM, n0 = tn * BN;
-  const int KT = p.K / BK / S;   // this block's k-tiles (launch_gemm3 only splits when K / 64 is a multiple of S)
-  const int KT0 = ksplit * KT;  // ... starting at this one
+  // this block's k-tiles [KT0, KT0 + KT): the S blocks of a tile own k-tile counts that differ by one at most (the planner splits only
+  // where every block keeps >= 8; layers of N % 128 == 0 only where K / 64 is a multiple of S, i.e. equal counts)
+  const int KT0 = p.K / BK * ksplit / S;
+  const int KT = p.K / BK * (ksplit + 1) / S - KT0;
 
   if (wave >= MW) {
     // ================================================= dequant waves ==================================================
@@ -142,7 +148,7 @@ __global__ __launch_bounds__((MW + 4) * 64) void gemm3_kernel(const GemmParams p
     constexpr int WPT = (LAYOUT == 2) ? 3 : 4;  // packed words per thread and k-tile
     const int bcol = ROWS ? (t & 127) : 8 * (t & 15);
     const int brow = ROWS ? 4 * (t >> 7) : 4 * (t >> 4);
-    const int nB = n0 + bcol;
+    const int nB = min(n0 + bcol, PN - 1);  // (half-wide last tile: columns >= N re-read column N - 1; their B columns are never consumed)
     const uint32_t nibmask = nib_mask_vgpr();
     uint32_t himask;
     asm volatile("v_mov_b32 %0, 0x00f000f0" : "=v"(himask));  // (held in a VGPR for the same reason as nibmask: one v_and_or_b32)
@@ -412,6 +418,9 @@ __global__ __launch_bounds__((MW + 4) * 64) void gemm3_kernel(const GemmParams p
     G3_PIECE_END(kt + 3, sa, 1, 0)  // sub-step 3
     sa = sa1;
   }
+  // (half-wide last tile: the matrix waves with wn = 1 run this loop too -- their MFMAs on B columns nobody stores cost no time,
+  //  the tile's length is set by the live waves' SIMDs -- and leave before the epilogue)
+  const bool live = n0 + wn * 64 < PN;
 #undef G3_PIECE_MID
 #undef G3_PIECE_END
 #undef G3_SB
@@ -454,6 +463,7 @@ __global__ __launch_bounds__((MW + 4) * 64) void gemm3_kernel(const GemmParams p
     }
     if (tid == 0) __hip_atomic_store(p.counters + slab_tile, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
+  if (!live) return;  // (columns past N: no bias, no store; the block's last barrier is behind it)
 
   // ---- epilogue: + bias, round once, transpose through wave-private LDS, 16-byte row-contiguous stores ---------------------
   // C/D layout of 32x32 tiles: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).  (All fragment reads that
@@ -487,6 +497,10 @@ __global__ __launch_bounds__((MW + 4) * 64) void gemm3_kernel(const GemmParams p
   }
 }
 
+// round 7: single strip-major 4-bit layers whose last 128-column tile is half wide (N % 128 == 64: Falcon-7B); the 4-bit row-stream
+// layouts in place keep the 128x128 kernel, 3-bit and AWQ layers their N % 128 == 0 rule
+bool gemm3_n_tail(const GemmParams &p, int layout) { return p.N % 128 == 64 && p.sm && layout == QLLM_LAYOUT_GPTQ && p.n_prob <= 1; }
+
 bool gemm3_ok(const GemmParams &p, int layout) {
   const int on = knob("QLLM_GEMM3", 1);
   // 4 bits: from M = 1024 (below it gemm2's split-K form was the measured choice; QLLM_GEMM3_MIN_M moves the line);
@@ -496,8 +510,10 @@ bool gemm3_ok(const GemmParams &p, int layout) {
   const int min_m_env = knob("QLLM_GEMM3_MIN_M", 0);
   const int min_m = min_m_env ? min_m_env : (((size_t)p.K * p.N > (size_t)4096 * 4096) ? 384 : 768);
   const int min_m3 = knob("QLLM_GEMM3_MIN_M_3BIT", 33);  // (33..64: native-layout layers whose strips stop at two row tiles)
-  if (!on || p.g_idx || p.K % 64 != 0 || p.N % 128 != 0) return false;
-  if (p.M < (layout == kGemm3Rows3Bit ? min_m3 : min_m)) return false;
+  // round 7: a half-wide last column tile has no gemm2 form to fall back on -- gemm3 (split-K below min_m) from gemm2's 33 rows
+  const bool tail = gemm3_n_tail(p, layout);
+  if (!on || p.g_idx || p.K % 64 != 0 || (p.N % 128 != 0 && !tail)) return false;
+  if (p.M < (layout == kGemm3Rows3Bit ? min_m3 : (tail ? 33 : min_m))) return false;
   // fp16 activations only: the activation tile goes to LDS by DMA, which cannot convert bf16 on the way (callers convert x with
   // launch_bf16_to_f16 first and set out_bf16, or use gemm2); 32-bit byte offsets into x and the packed weights
   if (p.act_bf16 || (size_t)p.M * p.K * 2 >= 0x7fffffffull || (size_t)p.K * p.N / 2 >= 0x7fffffffull) return false;
@@ -524,7 +540,7 @@ static int launch_gemm3_b(const GemmParams &p, hipStream_t stream) {
   using namespace g3;
   static DeviceLatch attr_done;
   if (int rc = lds_optin(attr_done, (const void *)gemm3_kernel<LAYOUT, MW, PRIO, BF>)) return rc;
-  const int tiles_all = p.n_prob > 1 ? p.total_tiles : ((p.M + BM - 1) / BM) * (p.N / BN);
+  const int tiles_all = p.n_prob > 1 ? p.total_tiles : ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
   const int tiles = p.tail_split > 1 ? p.tail_from + (tiles_all - p.tail_from) * p.tail_split : tiles_all * p.split_k;
   const size_t lds = (size_t)(3 * kATile + 2 * kBTile) * sizeof(half_t);  // 128 KB
   hipLaunchKernelGGL((gemm3_kernel<LAYOUT, MW, PRIO, BF>), dim3(tiles), dim3((MW + 4) * 64), lds, stream, p);
@@ -533,10 +549,12 @@ static int launch_gemm3_b(const GemmParams &p, hipStream_t stream) {
 }
 
 // split-K factor for gemm3: gemm2's rule (largest S <= 8 with tiles * S <= CUs and >= 8 k-tiles per block), reduced until every
-// block owns the same number of k-tiles
+// block owns the same number of k-tiles.  Round 7, N % 128 == 64: the half-wide last tile counts as a tile, and the blocks' k-tile counts
+// may differ by one (Falcon-7B's K = 4544 is 71 k-tiles: a whole-count rule would never split it)
 int gemm3_split_k(int M, int N, int K) {
-  int s = gemm2_split_k(M, N, K);
-  while (s > 1 && (K / 64) % s != 0) s /= 2;
+  const bool tail = N % 128 != 0;
+  int s = gemm2_split_k(M, gemm3_tile_cols(N), K);
+  while (s > 1 && (K / 64) % s != 0 && !tail) s /= 2;
   return s;
 }
 
@@ -545,14 +563,17 @@ int gemm3_split_k(int M, int N, int K) {
 // of Llama-2-7B run at 970-1070): the r = tiles mod CUs tiles of that round are shared by TS blocks each -- the largest power of two with
 // r * TS <= CUs, whole k-tile counts and >= 16 k-tiles per block (the fix-up moves 2 x 128 KB per block: below that it eats the gain).
 // Returns TS (1: none) and the number of unsplit tiles in *tail_from.
-int gemm3_tail_split(int M, int N, int K, int *tail_from) { return gemm3_tail_split_tiles(((M + 255) / 256) * (N / 128), K, tail_from); }
-int gemm3_tail_split_tiles(int tiles, int K, int *tail_from) {
+// (round 7, N % 128 == 64: the half-wide last tile counts as a tile; k-tile counts may differ by one, as for gemm3_split_k)
+int gemm3_tail_split(int M, int N, int K, int *tail_from) {
+  return gemm3_tail_split_tiles(((M + 255) / 256) * (gemm3_tile_cols(N) / 128), K, tail_from, N % 128 != 0);
+}
+int gemm3_tail_split_tiles(int tiles, int K, int *tail_from, bool uneven) {
   const int cus = compute_units(), kt = K / 64;
   *tail_from = tiles;
   if (!knob("QLLM_GEMM3_TAIL", 1) || tiles <= cus || tiles % cus == 0) return 1;
   const int r = tiles % cus;
   int ts = 1;
-  while (ts < 8 && r * ts * 2 <= cus && kt % (ts * 2) == 0 && kt / (ts * 2) >= 16) ts *= 2;
+  while (ts < 8 && r * ts * 2 <= cus && (uneven || kt % (ts * 2) == 0) && kt / (ts * 2) >= 16) ts *= 2;
   if (ts > 1) *tail_from = tiles - r;
   return ts;
 }

@@ -165,7 +165,7 @@ __device__ __forceinline__ uint4_t load16_sys(const void *p) {
   const uint64_t b = __hip_atomic_load((const uint64_t *)p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   return uint4_t{(uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32)};
 }
-bool strip1_shape(int K, int blocks, int cus, int *nw, int *maxs);
+bool strip1_shape(int K, int blocks, int cus, int *nw, int *maxs, bool odd64 = false);  // (odd64: K % 128 == 64 allowed -- 4-bit 64-wide groups)
 int launch_strip1(const Strip1Params &p, int nw, int maxs, int n_prob, int max_strips, hipStream_t stream);
 int launch_strip1_allreduce(const Strip1Params &p, int nw, int maxs, int n_strips, hipStream_t stream);  // (p.ar_* set; one layer)
 
@@ -221,7 +221,7 @@ int gemm2_split_k(int M, int N, int K);
 constexpr int kGemm3MaxProb = 4;
 using GemmProb = GemmParams::GemmProb;
 int gemm3_tail_split(int M, int N, int K, int *tail_from);
-int gemm3_tail_split_tiles(int tiles, int K, int *tail_from);
+int gemm3_tail_split_tiles(int tiles, int K, int *tail_from, bool uneven = false);  // (uneven: k-tile counts may differ by one)
 bool gemm3_bf16_native(int layout);  // gemm3.hip: K-split factor of the ragged last round of tiles (1: none)
 int gemm2_tile_n(int M, int N, int split_k);
 size_t gemm2_slab_bytes(int M, int N, int S);
@@ -254,6 +254,8 @@ int launch_panel(const PanelParams &p, hipStream_t stream);
 // ---- gemm3.hip (256x128 tile, 4 matrix waves + 4 staging waves; no split-K) ---------------------------------------------
 constexpr int kGemm3Rows3Bit = 100;  // `layout` value for launch_gemm3 / gemm3_ok: GPTQ / HQQ row stream with 3-bit weights
 bool gemm3_ok(const GemmParams &p, int layout);
+bool gemm3_n_tail(const GemmParams &p, int layout);  // round 7: a strip-major 4-bit layer with N % 128 == 64 (half-wide last column tile)
+inline int gemm3_tile_cols(int N) { return (N + 127) / 128 * 128; }  // N over whole 128-column tiles (the slab / tile count of gemm3)
 int gemm3_split_k(int M, int N, int K);
 int launch_gemm3(const GemmParams &p, int layout, hipStream_t stream);
 int launch_bf16_to_f16(const void *src, void *dst, size_t n, hipStream_t stream);  // elementwise RNE conversion (gemm3's bf16 pre-pass)

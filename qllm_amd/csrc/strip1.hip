@@ -6,8 +6,11 @@ namespace qllm {
 // (waves per block, k-steps per wave) for T = K / 32 k-steps, or false: not served (the general strip kernel takes the call).
 // One round per wave: NW * MAXS >= T >= MAXS.  Measured choices: profiles/r05_decode_bisect.md.
 // `blocks`: 16-column strips of the launch (all layers); `cus`: compute units.
-bool strip1_shape(int K, int blocks, int cus, int *nw, int *maxs) {
-  if (K % 128 != 0) return false;  // (whole 16-byte windows of x per four k-steps; 64-wide groups: the same table)
+// Round 7, `odd64` (4-bit layers with 64-wide groups only): K % 128 == 64 too, i.e. T % 4 == 2 (Falcon-7B: K = 4544, T = 142).  No such T
+// is a whole number of rounds (MAXS % 4 == 0), so these shapes always take the non-EXACT forms, whose last live wave shifts its window
+// back to [T - MAXS, T): no load for a k-step >= T, and T - MAXS is even, so the window still starts on a 64-wide group (G0 = tb / 2).
+bool strip1_shape(int K, int blocks, int cus, int *nw, int *maxs, bool odd64) {
+  if (K % 128 != 0 && !(odd64 && K % 128 == 64)) return false;  // (whole 16-byte windows of x per four k-steps; 64-wide groups: the same table)
   const int T = K / 32;
   if (T < 8) return false;
   int w, m;

@@ -232,8 +232,8 @@ class HipForwardMixin:
             except ops.QllmUnsupported:
                 if w.layout not in (ops.LAYOUTS["NATIVE"], ops.LAYOUTS["NATIVE_F16Z"]):
                     raise
-                # a shape the native layout is not served at (e.g. M > 64 with N % 128 != 0): the reference buffers in place,
-                # and they stay on the device from now on
+                # a shape the native layout is not served at (e.g. M > 64 with N % 64 != 0, or 3 bits with N % 128 != 0; since
+                # round 7 N % 128 == 64 -- Falcon-7B -- is served): the reference buffers in place, and they stay on the device from now on
                 self._needs_reference = True
                 w = self._descriptor(act_order_g_idx, add_zero_bias)
                 y = ops.linear_forward(w, x2d)

@@ -29,6 +29,9 @@ FAMILIES = {
     "phi3-mini": (3072, 8192, 3072, 128),
     "llama2-70b": (8192, 28672, 1024, 128),
     "falcon-7b-like(g64)": (4544, 18176, 4544, 64),   # K = 4544 is not a multiple of 128: 64-wide groups (GPTQ row-stream layout)
+    # Falcon-7B itself: multi-query attention (k and v are one 64-wide head each), 64-wide groups; its fused query_key_value is
+    # 4544 -> 4672 = the q/k/v group here, its MLP one 4544 -> 18176 layer (the gate/up row counts it twice)
+    "falcon-7b": (4544, 18176, 64, 64),
 }
 FOOTPRINT = 640 << 20
 
