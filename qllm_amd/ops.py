@@ -212,6 +212,16 @@ def linear_forward_shared(w: QllmWeight, x2d: torch.Tensor, key: Optional[torch.
     return linear_forward(w, x2d)
 
 
+def grouped_workspace_bytes(ws_desc: Sequence[QllmWeight], m: int, act_dtype: int, device: torch.device) -> int:
+    """The grouped call's workspace rule (include/qllm_mi355x.h): the sum of the layers' qllm_workspace_bytes_act, and from 384 rows at
+    least 16 KB + 128 KB per CU -- a prefill group K-splits the ragged last round of ALL its layers' tiles, which no layer's size bounds."""
+    lib = _lib.load()
+    nbytes = sum(lib.qllm_workspace_bytes_act(C.byref(w), m, act_dtype) for w in ws_desc)
+    if m >= 384:
+        nbytes = max(nbytes, 16384 + torch.cuda.get_device_properties(device).multi_processor_count * 256 * 128 * 4)
+    return nbytes
+
+
 def linear_forward_grouped(ws_desc: Sequence[QllmWeight], x2d: torch.Tensor,
                            outs: Optional[Sequence[torch.Tensor]] = None):
     """Several layers sharing x (q/k/v, gate/up) in ONE launch (decode sizes only)."""
@@ -231,7 +241,7 @@ def linear_forward_grouped(ws_desc: Sequence[QllmWeight], x2d: torch.Tensor,
     arr = (QllmWeight * n)(*ws_desc)
     ys = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
     with torch.cuda.device(x2d.device):
-        nbytes = sum(lib.qllm_workspace_bytes_act(C.byref(w), m, _act_dtype(x2d)) for w in ws_desc)
+        nbytes = grouped_workspace_bytes(ws_desc, m, _act_dtype(x2d), x2d.device)
         wsp = workspace(x2d.device, nbytes)
         rc = lib.qllm_linear_forward_grouped(arr, ys, n, x2d.data_ptr(), m, _act_dtype(x2d), wsp.data_ptr(),
                                              wsp.numel(), _stream_ptr())

@@ -53,6 +53,19 @@ def oracle_y(d, x, w=None):
     return O.matmul_f16(x, w, d["bias"]).numpy()
 
 
+def guarded(t, pad_bytes=4096):
+    """A copy of the tensor `t` (fp16 / bf16) inside a larger buffer whose bytes before and after it are NaN of
+    t's dtype (fp16 0x7e00, bf16 0x7fc0).  Returns (buffer, view): the view has t's shape and starts `pad_bytes` into the buffer (torch's
+    allocations are 512-byte aligned, so it keeps that alignment for pad_bytes % 512 == 0).  A kernel that reads past either end of
+    the view reads NaN into its result.  (Integer tensors -- qweight, packed zero points, g_idx -- have no NaN pattern: not guarded.)"""
+    assert t.dtype in (torch.float16, torch.bfloat16) and pad_bytes % t.element_size() == 0
+    lead = pad_bytes // t.element_size()
+    buf = torch.full((lead + t.numel() + lead,), float("nan"), dtype=t.dtype, device=t.device)
+    view = buf[lead:lead + t.numel()].view(t.shape)
+    view.copy_(t)
+    return buf, view
+
+
 def randx(m, k, seed=1):
     return np.random.default_rng(seed).standard_normal((m, k)).astype(np.float16)
 

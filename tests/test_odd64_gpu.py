@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from oracle import ref_cpu as O
-from gpu_util import Ref, oracle_w, randx, synth, to_layer
+from gpu_util import Ref, guarded, oracle_w, randx, synth, to_layer
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -122,17 +122,9 @@ def test_splits_are_deterministic_and_match_the_unsplit_launch(K, M, split):
     assert O.rel_err(y2[torch.from_numpy(rows).to(DEV)].cpu().numpy(), ref.y16(x2[rows])) <= TOL
 
 
-def _guarded(t, pad_elems):
-    """a copy of `t` at the START of a larger buffer whose following bytes are fp16 NaN (0x7e00 in every half)"""
-    nbytes = t.numel() * t.element_size()
-    buf = torch.full((nbytes // 2 + pad_elems,), float("nan"), dtype=torch.float16, device=t.device)
-    buf.view(torch.uint8)[:nbytes].copy_(t.contiguous().view(torch.uint8).reshape(-1))
-    return buf
-
-
 @pytest.mark.parametrize("layout,zk,K,N", [("HQQ", "f16", 4544, 4544), ("GPTQ", "asym", 4544, 4672), ("HQQ", "f16", 1088, 320)])
 def test_no_read_past_the_native_tables(layout, zk, K, N):
-    """The native copy's scales / zero points / bias followed by NaN in memory: a read past column N (gemm3's dead half tile) or past
+    """The native copy's scales / zero points / bias between bands of NaN in memory: a read past column N (gemm3's dead half tile) or past
     k-step T (the batch-1 kernel's last window) would put a NaN into y."""
     from qllm_amd import ops
     d = synth(layout, 4, 64, K, N, zk, False, True, seed=3 * K + N)
@@ -141,8 +133,8 @@ def test_no_read_past_the_native_tables(layout, zk, K, N):
     assert w.layout in _layouts()
     native_keep = layer._native[1]                           # (qweight, scales, qzeros, None, bias) of the native copy
     nq, ns, nz, _, nb = native_keep
-    gs, gb = _guarded(ns, 4096), _guarded(nb, 4096)
-    gz = _guarded(nz, 4096) if nz is not None and nz.dtype == torch.float16 else nz
+    (_, gs), (_, gb) = guarded(ns, 8192), guarded(nb, 8192)
+    gz = guarded(nz, 8192)[1] if nz is not None and nz.dtype == torch.float16 else nz
     gw = ops.QllmWeight(nq.data_ptr(), gs.data_ptr(), gz.data_ptr() if gz is not None else None, None, gb.data_ptr(),
                         w.K, w.N, w.group_size, w.bits, w.layout, w.add_zero_bias)
     ref = Ref(d)
