@@ -52,7 +52,7 @@
 extern "C" {
 #endif
 
-#define QLLM_ABI_VERSION 6
+#define QLLM_ABI_VERSION 7
 
 typedef enum qllm_status {
   QLLM_OK = 0,
@@ -80,7 +80,8 @@ typedef enum qllm_dtype {
    * input -- and y is written as bf16(fp16(result)): the reference's own bf16 shim around its fp16 kernels
    * (quant_linear_awq.py:29-36, 144-146) with the conversion of x hoisted out of the call.  Served where the 256x128 prefill
    * kernel serves a bf16 call (the call that would otherwise convert x into the workspace); QLLM_ERR_UNSUPPORTED elsewhere. */
-  QLLM_F16_IN_BF16_OUT = 2
+  QLLM_F16_IN_BF16_OUT = 2,
+  QLLM_F32 = 3 /* qllm_hqq_quantize's w_dtype only (ABI 7) */
 } qllm_dtype_t;
 
 /* elementwise bf16 -> fp16 (round to nearest even), n a multiple of 8: the conversion the QLLM_F16_IN_BF16_OUT caller hoists (ABI 4) */
@@ -262,6 +263,27 @@ int qllm_pack_qweight(const int32_t *q_kn, int32_t layout, int32_t bits, int32_t
  * permutation applied to the columns of x at every forward.  perm: K int32 on the device, a permutation of 0..K-1 (entries are
  * not range-checked).  x, perm, out 16-byte aligned, out must not alias x; K % 8 == 0 and K <= 28672, else QLLM_ERR_UNSUPPORTED. */
 int qllm_gather_columns(const void *x, const int32_t *perm, void *out, int32_t M, int32_t K, int32_t act_dtype, void *stream);
+
+/* ---- HQQ quantizer (ABI 7) ---------------------------------------------------------------------------------------------------------- */
+/* W[N,K] (fp16 / bf16 / fp32 by w_dtype, row-major, 16-byte aligned) -> the HQQ layer buffers: qweight i32 [K*bits/32][N], scales f16
+ * [K/g][N] = fp16(1/s), zeros f16 [K/g][N] = fp16(z).  The algorithm is HQQQuant.do_quantize's (qllm/quantization/hqq/quant_hqq.py:34-36,
+ * _hqq_quantizer.py:29-121: axis=1, channel_wise, optimize, round_zero) in fp32, the dtype of the reference's CPU solver: per group of
+ * g consecutive k of one row, s = min(max_v * (1 / (max - min)), 2e4) (two roundings, as torch divides a scalar by a tensor), z = rint(-min s), then up to `iters` rounds of
+ *   Wq = clamp(rint(W s + z), 0, max_v);  x = W - (Wq - z) / s;  We = sign(x) max(|x| - |x|^(lp_norm-1) / beta, 0);
+ *   z = mean_group(Wq - (W - We) s);  beta *= kappa
+ * stopped, like the reference, after the first round whose TENSOR-wide mean |x| does not fall below the best so far (that round's z
+ * update is kept); codes = clamp(rint(W s + z), 0, max_v) with the final fp32 z.  The reference's defaults: iters 20, lp_norm 0.7,
+ * beta 10, kappa 1.01.  One fused kernel, run twice around a one-block reduction (csrc/hqq_quant.hip): no host synchronisation, no
+ * atomics, bit-reproducible, hipGraph-capturable.  rounds_run_dev (nullable, device int32): the number of rounds that were run.
+ * Serves bits 2 / 3 / 4 / 8, g % 32 == 0 with 32 <= g <= 1024, K % g == 0, N % 16 == 0, lp_norm < 1, iters <= 64 (beyond: QLLM_ERR_INVALID);
+ * other shapes and lp_norm >= 1: QLLM_ERR_UNSUPPORTED.  Workspace: qllm_hqq_quantize_workspace_bytes() (pure; 0 for shapes never served),
+ * 16-byte aligned, needs no initialisation; after the call its first int32 is rounds_run and the floats from byte 256 on are the per-round
+ * tensor-wide mean errors.  Debug output: a workspace with room for 2 x N x K/g further floats behind the required bytes (rounded up to
+ * 256) also receives the solver's fp32 s [K/g][N] and z [K/g][N] there. */
+size_t qllm_hqq_quantize_workspace_bytes(int32_t N, int32_t K, int32_t group_size, int32_t iters);
+int qllm_hqq_quantize(const void *w_nk, int32_t w_dtype, int32_t N, int32_t K, int32_t bits, int32_t group_size, int32_t iters,
+                      float lp_norm, float beta, float kappa, void *qweight, void *scales, void *zeros, int32_t *rounds_run_dev,
+                      void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- tensor-parallel decode: one-shot all-reduce over peer-mapped staging buffers (ABI 4; fused form ABI 5) -------------------------------------- */
 /* For decode-sized tensors ([1, 8192] fp16 = 16 KB per row-parallel layer) a ring / tree all-reduce is pure latency.  On the xGMI

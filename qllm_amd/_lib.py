@@ -15,8 +15,8 @@ LIB_PATH = os.environ.get("QLLM_MI355X_LIB") or os.path.join(_HERE, LIB_NAME)  #
 
 QLLM_OK, QLLM_ERR_INVALID, QLLM_ERR_UNSUPPORTED, QLLM_ERR_WORKSPACE, QLLM_ERR_LAUNCH, QLLM_ERR_DEVICE = range(6)
 LAYOUT_GPTQ, LAYOUT_AWQ_GEMM, LAYOUT_HQQ, LAYOUT_NATIVE, LAYOUT_NATIVE_F16Z = 0, 1, 2, 3, 4
-DT_F16, DT_BF16, DT_F16_IN_BF16_OUT = 0, 1, 2
-ABI_VERSION = 6
+DT_F16, DT_BF16, DT_F16_IN_BF16_OUT, DT_F32 = 0, 1, 2, 3
+ABI_VERSION = 7
 
 EXPORTS = (
     "qllm_abi_version", "qllm_is_lab_build", "qllm_last_error", "qllm_device_info", "qllm_workspace_bytes", "qllm_workspace_bytes_act", "qllm_workspace_init",
@@ -26,6 +26,7 @@ EXPORTS = (
     "qllm_comm_buffer_bytes", "qllm_comm_alloc", "qllm_comm_free", "qllm_comm_export", "qllm_comm_import", "qllm_comm_close",
     "qllm_allreduce_oneshot", "qllm_linear_forward_allreduce", "qllm_convert_bf16_to_f16",
     "qllm_set_knob", "qllm_get_knob", "qllm_reset_knobs",
+    "qllm_hqq_quantize_workspace_bytes", "qllm_hqq_quantize",
 )
 
 
@@ -129,6 +130,10 @@ def _declare(lib):
     lib.qllm_repack_native.argtypes = [wp, vp, vp, vp, vp]
     lib.qllm_unpack_native.restype = C.c_int
     lib.qllm_unpack_native.argtypes = [wp, i32, vp, vp, vp, vp]
+    lib.qllm_hqq_quantize_workspace_bytes.restype = sz
+    lib.qllm_hqq_quantize_workspace_bytes.argtypes = [i32, i32, i32, i32]
+    lib.qllm_hqq_quantize.restype = C.c_int
+    lib.qllm_hqq_quantize.argtypes = [vp, i32, i32, i32, i32, i32, i32, C.c_float, C.c_float, C.c_float, vp, vp, vp, vp, vp, sz, vp]
     lib.qllm_ort_dequantize4bits.restype = C.c_int
     lib.qllm_ort_dequantize4bits.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, vp, vp]
 

@@ -1127,6 +1127,33 @@ int qllm_convert_bf16_to_f16(const void *src, void *dst, size_t n, void *stream)
   return n ? launch_bf16_to_f16(src, dst, n, (hipStream_t)stream) : QLLM_OK;
 }
 
+size_t qllm_hqq_quantize_workspace_bytes(int32_t N, int32_t K, int32_t group_size, int32_t iters) {
+  return hqq_quant_workspace_bytes(N, K, group_size, iters);
+}
+
+int qllm_hqq_quantize(const void *w_nk, int32_t w_dtype, int32_t N, int32_t K, int32_t bits, int32_t group_size, int32_t iters, float lp_norm,
+                      float beta, float kappa, void *qweight, void *scales, void *zeros, int32_t *rounds_run_dev, void *workspace,
+                      size_t workspace_bytes, void *stream) {
+  clear_error();
+  if (!w_nk || !qweight || !scales || !zeros) return set_error(QLLM_ERR_INVALID, "w_nk / qweight / scales / zeros must not be NULL");
+  if (w_dtype != QLLM_F16 && w_dtype != QLLM_BF16 && w_dtype != QLLM_F32) return set_error(QLLM_ERR_INVALID, "w_dtype must be QLLM_F16, QLLM_BF16 or QLLM_F32");
+  if (N <= 0 || K <= 0 || group_size <= 0) return set_error(QLLM_ERR_INVALID, "bad N/K/group_size (%d/%d/%d)", N, K, group_size);
+  if (bits < 1 || bits > 8) return set_error(QLLM_ERR_INVALID, "bad bits (%d)", bits);
+  if (iters < 1 || iters > 64) return set_error(QLLM_ERR_INVALID, "iters must be 1..64 (got %d)", iters);
+  if (!(beta > 0.f) || !(kappa > 0.f) || !(lp_norm > 0.f)) return set_error(QLLM_ERR_INVALID, "lp_norm, beta and kappa must be positive");
+  if ((uintptr_t)w_nk % 16 || (uintptr_t)qweight % 4 || (uintptr_t)scales % 2 || (uintptr_t)zeros % 2 || (uintptr_t)rounds_run_dev % 4)
+    return set_error(QLLM_ERR_INVALID, "w_nk must be 16-byte aligned, the outputs aligned to their element size");
+  if (!hqq_quant_shape_ok(N, K, bits, group_size))
+    return set_error(QLLM_ERR_UNSUPPORTED, "the HQQ quantizer serves bits 2/3/4/8, group_size %% 32 == 0 in 32..1024, K %% group_size == 0, N %% 16 == 0 "
+                     "(got bits=%d group_size=%d K=%d N=%d)", bits, group_size, K, N);
+  if (!(lp_norm < 1.f)) return set_error(QLLM_ERR_UNSUPPORTED, "the HQQ quantizer serves lp_norm < 1 (got %g)", (double)lp_norm);
+  const size_t need = hqq_quant_workspace_bytes(N, K, group_size, iters);
+  if (!workspace || workspace_bytes < need || (uintptr_t)workspace % 16)
+    return set_error(QLLM_ERR_WORKSPACE, "qllm_hqq_quantize needs a 16-byte aligned workspace of %zu bytes (got %zu)", need, workspace ? workspace_bytes : (size_t)0);
+  return launch_hqq_quantize(w_nk, w_dtype, N, K, bits, group_size, iters, lp_norm, beta, kappa, qweight, scales, zeros, rounds_run_dev, workspace,
+                             workspace_bytes, (hipStream_t)stream);
+}
+
 int qllm_debug_timeline(void *buf, int32_t n_slots) {  // n_slots x 24 x u64
   clear_error();
   g_timeline = (uint64_t *)buf;

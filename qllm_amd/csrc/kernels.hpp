@@ -260,6 +260,12 @@ int gemm3_split_k(int M, int N, int K);
 int launch_gemm3(const GemmParams &p, int layout, hipStream_t stream);
 int launch_bf16_to_f16(const void *src, void *dst, size_t n, hipStream_t stream);  // elementwise RNE conversion (gemm3's bf16 pre-pass)
 
+// ---- hqq_quant.hip (ABI 7: the HQQ proximal solver + encoder, fp16 / bf16 / fp32 W[N,K] -> HQQ row stream) ---------------------------------
+bool hqq_quant_shape_ok(int N, int K, int bits, int group_size);
+size_t hqq_quant_workspace_bytes(int N, int K, int group_size, int iters);  // pure; 0 for shapes that are never served
+int launch_hqq_quantize(const void *w_nk, int w_dtype, int N, int K, int bits, int group_size, int iters, float lp_norm, float beta, float kappa,
+                        void *qweight, void *scales, void *zeros, int *rounds_run_dev, void *workspace, size_t workspace_bytes, hipStream_t stream);
+
 // ---- tools/lab/gemm5.hip (lab builds: 256x128 tile, every wave a matrix wave, B fragments dequantised in registers) ------------------
 bool gemm5_ok(const GemmParams &p, int layout);
 int launch_gemm5(const GemmParams &p, int wm, hipStream_t stream);

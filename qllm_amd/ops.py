@@ -353,6 +353,41 @@ def pack_qweight(q_kn: torch.Tensor, layout: str, bits: int) -> torch.Tensor:
     return out
 
 
+_W_DTYPES = {torch.float16: DT_F16, torch.bfloat16: DT_BF16, torch.float32: _lib.DT_F32}
+
+
+def hqq_quantize(weight: torch.Tensor, bits: int, group_size: int = 64, iters: int = 20, lp_norm: float = 0.7, beta: float = 10.0,
+                 kappa: float = 1.01, debug: bool = False):
+    """weight [N, K] (fp16 / bf16 / fp32, on the device) -> the HQQ layer buffers, by the library's fused proximal solver
+    (qllm_hqq_quantize, include/qllm_mi355x.h): (qweight i32 [K*bits/32, N], scales f16 [K/g, N], zeros f16 [K/g, N], rounds_run i32 [1]
+    on the device).  `debug` appends the solver's own fp32 (s [K/g, N], z [K/g, N], per-round tensor-wide mean errors [iters])."""
+    _check_input(weight, "weight")
+    if weight.dim() != 2 or weight.dtype not in _W_DTYPES:
+        raise RuntimeError(f"weight must be a 2-D float16 / bfloat16 / float32 tensor, got {tuple(weight.shape)} {weight.dtype}")
+    lib = _lib.load()
+    n, k = weight.shape
+    g = k if group_size == -1 else int(group_size)
+    dev = weight.device
+    need = lib.qllm_hqq_quantize_workspace_bytes(n, k, g, int(iters))
+    groups = n * (k // g) if g > 0 and k % g == 0 else 0
+    dbg_at = (need + 255) // 256 * 256
+    ws = torch.empty(max(dbg_at + (8 * groups if debug else 0), 16), dtype=torch.uint8, device=dev)
+    qweight = torch.empty((max(k * bits // 32, 0), n), dtype=torch.int32, device=dev)
+    scales = torch.empty((max(k // max(g, 1), 1), n), dtype=torch.float16, device=dev)
+    zeros = torch.empty_like(scales)
+    rounds = torch.empty(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.qllm_hqq_quantize(weight.data_ptr(), _W_DTYPES[weight.dtype], n, k, int(bits), g, int(iters), float(lp_norm), float(beta),
+                                   float(kappa), qweight.data_ptr(), scales.data_ptr(), zeros.data_ptr(), rounds.data_ptr(), ws.data_ptr(),
+                                   ws.numel() if debug else need, _stream_ptr())
+    _lib.check(rc)
+    if not debug:
+        return qweight, scales, zeros, rounds
+    f = ws[dbg_at:dbg_at + 8 * groups].view(torch.float32)
+    return (qweight, scales, zeros, rounds, f[:groups].view(k // g, n).clone(), f[groups:].view(k // g, n).clone(),
+            ws[256:256 + 4 * int(iters)].view(torch.float32).clone())
+
+
 def repack_native(w: QllmWeight, keep):
     """The layer behind descriptor `w` (GPTQ / AWQ GEMM / HQQ buffers, no g_idx) re-laid-out into the library's strip-major native
     layout (include/qllm_mi355x.h, "native layout") on its device: returns (QllmWeight, keepalive) like make_weight.  A pure integer
@@ -399,4 +434,4 @@ def unpack_native(w: QllmWeight, keep, layout: str):
 
 
 __all__ = ["make_weight", "linear_forward", "linear_forward_grouped", "dequant", "gather_columns", "unpack_qweight", "pack_qweight",
-           "workspace", "QllmUnsupported", "LAYOUTS", "plan_describe", "repack_native", "unpack_native"]
+           "workspace", "QllmUnsupported", "LAYOUTS", "plan_describe", "repack_native", "unpack_native", "hqq_quantize"]
