@@ -12,7 +12,7 @@
 
 namespace qllm {
 
-// waves per block of the lds-slab form, or 0: use the register-A form (host planner, capi.hip)
+// waves per block of the lds-slab form, or 0: use the register-A form (host planner, planner.hip)
 int strip_sm_nw(int K, int M, int group_size, int bits) {
   const int nw4 = knob("QLLM_SM_NW4", 0);
   const int T = K / 32;

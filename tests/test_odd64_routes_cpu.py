@@ -10,7 +10,7 @@ from qllm_amd import _lib
 GPTQ, NATIVE, NATIVE_F16Z = _lib.LAYOUT_GPTQ, _lib.LAYOUT_NATIVE, _lib.LAYOUT_NATIVE_F16Z
 G3 = "gemm3 tile=256x128 matrix-waves=8 staging-waves=4"
 SM = " layout=strip-major"
-COUNTERS = 16384                 # the workspace's arrival counters (capi.hip, kCounterBytes)
+COUNTERS = 16384                 # the workspace's arrival counters (planner.hpp, kCounterBytes)
 TILE_SLAB = 256 * 128 * 4        # one fp32 partial 256x128 tile
 
 
@@ -110,3 +110,15 @@ def test_fused_allreduce_refuses_64_wide_groups_at_k_4544(lib):
         rc = lib.qllm_linear_forward_allreduce(C.byref(w), 4096, 8192, 1, _lib.DT_F16, 12288, 0, 1, 1 << 20, None, None)
         assert rc == _lib.QLLM_ERR_UNSUPPORTED, (w.K, rc, _lib.last_error())
         assert "128-wide groups" in _lib.last_error()
+
+
+@pytest.mark.parametrize("layout", [NATIVE, NATIVE_F16Z])
+@pytest.mark.parametrize("K", [4096, 3584, 16384])
+def test_fused_allreduce_refuses_3bit_layers(lib, layout, K):
+    """The batch-1 kernel plans 3-bit native layers with 128-wide groups too, but its all-reduce instantiations are 4-bit only: the fused
+    form refuses them (UNSUPPORTED, as parallel.py expects) before anything touches a device -- fake, aligned pointers suffice."""
+    w = W(K, 4096, g=128, bits=3, layout=layout)
+    assert plan(lib, [w], 1).startswith("strip1 ")   # (the plan the refusal must not follow)
+    rc = lib.qllm_linear_forward_allreduce(C.byref(w), 4096, 8192, 1, _lib.DT_F16, 12288, 0, 1, 1 << 20, None, None)
+    assert rc == _lib.QLLM_ERR_UNSUPPORTED, (K, rc, _lib.last_error())
+    assert "4-bit" in _lib.last_error()
