@@ -285,6 +285,36 @@ int qllm_hqq_quantize(const void *w_nk, int32_t w_dtype, int32_t N, int32_t K, i
                       float lp_norm, float beta, float kappa, void *qweight, void *scales, void *zeros, int32_t *rounds_run_dev,
                       void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- GPTQ quantizer (additive to ABI 7) ---------------------------------------------------------------------------------------------- */
+/* The column solver of GPTQ.fasterquant (qllm/quantization/gptq/gptq.py:129-258) with blocksize = 128, static_groups = False, mse = False,
+ * perchannel = True, in fp32, for all K columns of a layer in one kernel (csrc/gptq_quant.hip).  The caller prepares what is plumbing:
+ * w_nk [N,K] (fp16 / bf16 / fp32 by w_dtype, row-major) with its columns already in processing order (act-order: permuted; dead columns
+ * zeroed) and u_kk [K,K] fp32 row-major, the UPPER Cholesky factor of the inverse of the damped (and equally permuted) Hessian; only
+ * its upper triangle is used (the 128 x 128 tiles on the diagonal are loaded whole, so what lies below it must be readable, and no
+ * value there reaches a result); u_kk is 16-byte aligned and K a multiple of 4 (QLLM_ERR_INVALID otherwise).
+ * Columns are walked left to right in blocks of 128 (the last one may be narrower):
+ *   per column i:  q = scale * (clamp(rint(w / scale) + zero, 0, maxq) - zero);  err = (w - q) / U[i,i];
+ *                  every later column j of the same block: w[j] -= err * U[i,j]   (a product, then a difference: two roundings)
+ *   per block:     the columns behind the block receive Err(N x 128) . U[block, j] -- in the order of the blocks -- before they are used.
+ * Group parameters are found when column c with c % group_size == 0 is reached, from columns c .. c+group_size-1 in their state at the
+ * last BLOCK boundary (all earlier blocks' updates, none of the current block's): with group_size 32 / 64 this differs from the
+ * column-by-column state, which makes the 128-column block part of the semantics.  group_size == K (the reference's -1): one set per
+ * row from w_nk as given.  find_params (per row of the group): xmin = min(min, 0), xmax = max(max, 0); sym: xmax = max(|xmin|, xmax) and
+ * xmin = -xmax where xmin < 0; xmin == xmax == 0 -> (-1, +1); scale = (xmax - xmin) / maxq; zero = (maxq + 1) / 2 (sym) or
+ * rint(-xmin / scale), maxq = 2^bits - 1.
+ * Outputs: codes_kn i32 [K,N] (column order of w_nk); scales_ng / zeros_ng f32 [N, K/group_size] (zero is integer-valued); wq_nk
+ * (nullable) [N,K] = scale * (code - zero) rounded to w's dtype; loss_n (nullable) f32 [N] = sum over the row of (w - q)^2 / U[i,i]^2 / 2.
+ * u_kk == NULL stands for the identity: plain round-to-nearest on the same grid (no update; parameters from w_nk itself).
+ * Serves bits 2..8 and group_size 32 / 64 / 128 / K (others: QLLM_ERR_UNSUPPORTED); K % group_size != 0, NULL or misaligned buffers:
+ * QLLM_ERR_INVALID; all of it before any device work.  Every buffer aligned to its element size.  Workspace:
+ * qllm_gptq_quantize_workspace_bytes() (pure: N x K floats, the error history each row tile keeps for its own rows), 16-byte aligned,
+ * needs no initialisation.  No host synchronisation, no atomics, bit-reproducible, hipGraph-capturable.
+ * Not served (the reference's other switches): static_groups, mse, trits, Conv layers. */
+size_t qllm_gptq_quantize_workspace_bytes(int32_t N, int32_t K);
+int qllm_gptq_quantize(const void *w_nk, int32_t w_dtype, const float *u_kk, int32_t N, int32_t K, int32_t bits, int32_t group_size,
+                       int32_t sym, int32_t *codes_kn, float *scales_ng, float *zeros_ng, void *wq_nk, float *loss_n, void *workspace,
+                       size_t workspace_bytes, void *stream);
+
 /* ---- tensor-parallel decode: one-shot all-reduce over peer-mapped staging buffers (ABI 4; fused form ABI 5) -------------------------------------- */
 /* For decode-sized tensors ([1, 8192] fp16 = 16 KB per row-parallel layer) a ring / tree all-reduce is pure latency.  On the xGMI
  * full mesh every rank instead writes its vector into every peer's staging buffer (one hop), waits for the world's flags and sums

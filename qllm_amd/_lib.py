@@ -26,7 +26,7 @@ EXPORTS = (
     "qllm_comm_buffer_bytes", "qllm_comm_alloc", "qllm_comm_free", "qllm_comm_export", "qllm_comm_import", "qllm_comm_close",
     "qllm_allreduce_oneshot", "qllm_linear_forward_allreduce", "qllm_convert_bf16_to_f16",
     "qllm_set_knob", "qllm_get_knob", "qllm_reset_knobs",
-    "qllm_hqq_quantize_workspace_bytes", "qllm_hqq_quantize",
+    "qllm_hqq_quantize_workspace_bytes", "qllm_hqq_quantize", "qllm_gptq_quantize_workspace_bytes", "qllm_gptq_quantize",
 )
 
 
@@ -134,6 +134,10 @@ def _declare(lib):
     lib.qllm_hqq_quantize_workspace_bytes.argtypes = [i32, i32, i32, i32]
     lib.qllm_hqq_quantize.restype = C.c_int
     lib.qllm_hqq_quantize.argtypes = [vp, i32, i32, i32, i32, i32, i32, C.c_float, C.c_float, C.c_float, vp, vp, vp, vp, vp, sz, vp]
+    lib.qllm_gptq_quantize_workspace_bytes.restype = sz
+    lib.qllm_gptq_quantize_workspace_bytes.argtypes = [i32, i32]
+    lib.qllm_gptq_quantize.restype = C.c_int
+    lib.qllm_gptq_quantize.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.qllm_ort_dequantize4bits.restype = C.c_int
     lib.qllm_ort_dequantize4bits.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, vp, vp]
 

@@ -437,6 +437,33 @@ int qllm_hqq_quantize(const void *w_nk, int32_t w_dtype, int32_t N, int32_t K, i
                              workspace_bytes, (hipStream_t)stream);
 }
 
+size_t qllm_gptq_quantize_workspace_bytes(int32_t N, int32_t K) { return gptq_quant_workspace_bytes(N, K); }
+
+int qllm_gptq_quantize(const void *w_nk, int32_t w_dtype, const float *u_kk, int32_t N, int32_t K, int32_t bits, int32_t group_size, int32_t sym,
+                       int32_t *codes_kn, float *scales_ng, float *zeros_ng, void *wq_nk, float *loss_n, void *workspace, size_t workspace_bytes,
+                       void *stream) {
+  clear_error();
+  if (!w_nk || !codes_kn || !scales_ng || !zeros_ng) return set_error(QLLM_ERR_INVALID, "w_nk / codes_kn / scales_ng / zeros_ng must not be NULL");
+  if (w_dtype != QLLM_F16 && w_dtype != QLLM_BF16 && w_dtype != QLLM_F32) return set_error(QLLM_ERR_INVALID, "w_dtype must be QLLM_F16, QLLM_BF16 or QLLM_F32");
+  if (N <= 0 || K <= 0 || group_size <= 0) return set_error(QLLM_ERR_INVALID, "bad N/K/group_size (%d/%d/%d)", N, K, group_size);
+  if (sym < 0 || sym > 1) return set_error(QLLM_ERR_INVALID, "sym must be 0 or 1 (got %d)", sym);
+  if (!gptq_quant_shape_ok(K, bits, group_size))
+    return set_error(QLLM_ERR_UNSUPPORTED, "the GPTQ quantizer serves bits 2..8 and group_size 32 / 64 / 128 / K (got bits=%d group_size=%d K=%d)",
+                     bits, group_size, K);
+  if (K % group_size != 0) return set_error(QLLM_ERR_INVALID, "K must be a multiple of group_size (K=%d group_size=%d)", K, group_size);
+  if (K % 4 != 0) return set_error(QLLM_ERR_INVALID, "K must be a multiple of 4 (K=%d)", K);
+  if ((uintptr_t)u_kk % 16) return set_error(QLLM_ERR_INVALID, "u_kk must be 16-byte aligned: its tiles are read four floats at a time");
+  const int esz = w_dtype == QLLM_F32 ? 4 : 2;
+  if ((uintptr_t)w_nk % esz || (uintptr_t)wq_nk % esz || (uintptr_t)codes_kn % 4 || (uintptr_t)scales_ng % 4 ||
+      (uintptr_t)zeros_ng % 4 || (uintptr_t)loss_n % 4)
+    return set_error(QLLM_ERR_INVALID, "every buffer must be aligned to its element size");
+  const size_t need = gptq_quant_workspace_bytes(N, K);
+  if (!workspace || workspace_bytes < need || (uintptr_t)workspace % 16)
+    return set_error(QLLM_ERR_WORKSPACE, "qllm_gptq_quantize needs a 16-byte aligned workspace of %zu bytes (got %zu)", need, workspace ? workspace_bytes : (size_t)0);
+  return launch_gptq_quantize(w_nk, w_dtype, u_kk, N, K, bits, group_size, sym, codes_kn, scales_ng, zeros_ng, wq_nk, loss_n, workspace,
+                              (hipStream_t)stream);
+}
+
 int qllm_debug_timeline(void *buf, int32_t n_slots) {  // n_slots x 24 x u64
   clear_error();
   g_timeline = (uint64_t *)buf;

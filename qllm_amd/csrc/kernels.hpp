@@ -266,6 +266,12 @@ size_t hqq_quant_workspace_bytes(int N, int K, int group_size, int iters);  // p
 int launch_hqq_quantize(const void *w_nk, int w_dtype, int N, int K, int bits, int group_size, int iters, float lp_norm, float beta, float kappa,
                         void *qweight, void *scales, void *zeros, int *rounds_run_dev, void *workspace, size_t workspace_bytes, hipStream_t stream);
 
+// ---- gptq_quant.hip (the GPTQ column solver: fp16 / bf16 / fp32 W[N,K] + U[K,K] -> codes, scale / zero, dequantized W, per-row loss) -------
+bool gptq_quant_shape_ok(int K, int bits, int group_size);        // bits 2..8, group_size 32 / 64 / 128 / K
+size_t gptq_quant_workspace_bytes(int N, int K);                  // pure: the fp32 error history Err[N][K], rounded up to 256 bytes
+int launch_gptq_quantize(const void *w_nk, int w_dtype, const float *u_kk, int N, int K, int bits, int group_size, int sym, int32_t *codes_kn,
+                         float *scales_ng, float *zeros_ng, void *wq_nk, float *loss_n, void *workspace, hipStream_t stream);
+
 // ---- tools/lab/gemm5.hip (lab builds: 256x128 tile, every wave a matrix wave, B fragments dequantised in registers) ------------------
 bool gemm5_ok(const GemmParams &p, int layout);
 int launch_gemm5(const GemmParams &p, int wm, hipStream_t stream);

@@ -28,6 +28,8 @@ class QuantConfig:
     quant_method: str = "gptq"
     compatible_with_autogptq: bool = False
     by_layer: Dict[str, dict] = field(default_factory=dict)  # quant_config_by_layer.json (mixed precision)
+    desc_act: bool = False           # GPTQ act-order / symmetric grid: recorded by quantization/gptq.py; the layers
+    sym: bool = False                # themselves carry g_idx and their zero points, so loading needs neither
 
     @classmethod
     def from_dir(cls, path: str) -> "QuantConfig":
@@ -51,6 +53,7 @@ class QuantConfig:
             raise ValueError("quantisation config needs bits/w_bit and group_size/q_group_size")
         cfg = cls(bits=int(bits), group_size=int(group))
         cfg.compatible_with_autogptq = bool(raw.get("COMPATIBLE_WITH_AUTOGPTQ", False))
+        cfg.desc_act, cfg.sym = bool(raw.get("desc_act", False)), bool(raw.get("sym", False))
         if "version" not in raw:  # GPTQ-for-LLaMa / AutoGPTQ checkpoints: GPTQ layout, zeros stored minus one
             cfg.version, cfg.quant_method, cfg.compatible_with_autogptq = "GPTQ", "gptq", True
         else:
@@ -65,6 +68,10 @@ class QuantConfig:
         d = dict(bits=self.bits, group_size=self.group_size, version=self.version, quant_method=self.quant_method)
         if self.compatible_with_autogptq:
             d["COMPATIBLE_WITH_AUTOGPTQ"] = 1
+        if self.desc_act:
+            d["desc_act"] = True
+        if self.sym:
+            d["sym"] = True
         return d
 
 

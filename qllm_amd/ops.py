@@ -388,6 +388,49 @@ def hqq_quantize(weight: torch.Tensor, bits: int, group_size: int = 64, iters: i
             ws[256:256 + 4 * int(iters)].view(torch.float32).clone())
 
 
+def gptq_quantize(weight: torch.Tensor, u: Optional[torch.Tensor], bits: int, group_size: int = 128, sym: bool = False,
+                  want_wq: bool = True, out=None, workspace: Optional[torch.Tensor] = None):
+    """weight [N, K] (fp16 / bf16 / fp32 on the device, columns in processing order) and u [K, K] fp32, the upper Cholesky factor of
+    the inverse Hessian (None: identity = round-to-nearest), through the library's fused GPTQ column solver (qllm_gptq_quantize,
+    include/qllm_mi355x.h): (codes i32 [K, N], scales f32 [N, K/g], zeros f32 [N, K/g], wq [N, K] in weight's dtype or None,
+    loss f32 [N]).  `out`: that tuple preallocated (wq may be None); `workspace`: a uint8 tensor of at least
+    qllm_gptq_quantize_workspace_bytes -- both for callers that capture the call in a graph or own the memory."""
+    _check_input(weight, "weight")
+    if weight.dim() != 2 or weight.dtype not in _W_DTYPES:
+        raise RuntimeError(f"weight must be a 2-D float16 / bfloat16 / float32 tensor, got {tuple(weight.shape)} {weight.dtype}")
+    lib = _lib.load()
+    n, k = weight.shape
+    g = k if group_size == -1 else int(group_size)
+    dev = weight.device
+    if u is not None:
+        _check_input(u, "u")
+        if u.dtype != torch.float32 or tuple(u.shape) != (k, k) or u.device != dev:
+            raise RuntimeError(f"u must be a float32 [{k}, {k}] tensor on {dev}, got {tuple(u.shape)} {u.dtype} on {u.device}")
+    groups = max(k // max(g, 1), 1)
+    if out is None:
+        out = (torch.empty((k, n), dtype=torch.int32, device=dev), torch.empty((n, groups), dtype=torch.float32, device=dev),
+               torch.empty((n, groups), dtype=torch.float32, device=dev), torch.empty_like(weight) if want_wq else None,
+               torch.empty(n, dtype=torch.float32, device=dev))
+    codes, scales, zeros, wq, loss = out
+    for name, t, shape, dtype in (("codes", codes, (k, n), torch.int32), ("scales", scales, (n, groups), torch.float32),
+                                  ("zeros", zeros, (n, groups), torch.float32), ("wq", wq, (n, k), weight.dtype),
+                                  ("loss", loss, (n,), torch.float32)):
+        if t is None and name in ("wq", "loss"):
+            continue
+        _check_input(t, name)
+        if tuple(t.shape) != shape or t.dtype != dtype or t.device != dev:
+            raise RuntimeError(f"{name} must be a contiguous {dtype} {shape} tensor on {dev}")
+    need = lib.qllm_gptq_quantize_workspace_bytes(n, k)
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev) if workspace is None else workspace
+    with torch.cuda.device(dev):
+        rc = lib.qllm_gptq_quantize(weight.data_ptr(), _W_DTYPES[weight.dtype], u.data_ptr() if u is not None else None, n, k, int(bits), g,
+                                    1 if sym else 0, codes.data_ptr(), scales.data_ptr(), zeros.data_ptr(),
+                                    wq.data_ptr() if wq is not None else None, loss.data_ptr() if loss is not None else None,
+                                    ws.data_ptr(), ws.numel(), _stream_ptr())
+    _lib.check(rc)
+    return codes, scales, zeros, wq, loss
+
+
 def repack_native(w: QllmWeight, keep):
     """The layer behind descriptor `w` (GPTQ / AWQ GEMM / HQQ buffers, no g_idx) re-laid-out into the library's strip-major native
     layout (include/qllm_mi355x.h, "native layout") on its device: returns (QllmWeight, keepalive) like make_weight.  A pure integer
