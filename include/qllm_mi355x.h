@@ -81,7 +81,7 @@ typedef enum qllm_dtype {
    * (quant_linear_awq.py:29-36, 144-146) with the conversion of x hoisted out of the call.  Served where the 256x128 prefill
    * kernel serves a bf16 call (the call that would otherwise convert x into the workspace); QLLM_ERR_UNSUPPORTED elsewhere. */
   QLLM_F16_IN_BF16_OUT = 2,
-  QLLM_F32 = 3 /* qllm_hqq_quantize's w_dtype only (ABI 7) */
+  QLLM_F32 = 3 /* the quantizers' w_dtype only (ABI 7) */
 } qllm_dtype_t;
 
 /* elementwise bf16 -> fp16 (round to nearest even), n a multiple of 8: the conversion the QLLM_F16_IN_BF16_OUT caller hoists (ABI 4) */
@@ -314,6 +314,33 @@ size_t qllm_gptq_quantize_workspace_bytes(int32_t N, int32_t K);
 int qllm_gptq_quantize(const void *w_nk, int32_t w_dtype, const float *u_kk, int32_t N, int32_t K, int32_t bits, int32_t group_size,
                        int32_t sym, int32_t *codes_kn, float *scales_ng, float *zeros_ng, void *wq_nk, float *loss_n, void *workspace,
                        size_t workspace_bytes, void *stream);
+
+/* ---- AWQ quantizer (additive to ABI 7) ----------------------------------------------------------------------------------------------- */
+/* The two device steps of the AWQ search (qllm/quantization/awq/_awq_quantizer.py) with zero_point = True, in fp32 (csrc/awq_quant.hip).
+ * pseudo_quantize of a group of group_size values v with minimum vmin and maximum vmax, maxq = 2^bits - 1, true divisions, no contraction:
+ *   sc = max(vmax - vmin, 1e-5) / maxq;  z = clamp(-rint(vmin / sc), 0, maxq);  code = clamp(rint(v / sc) + z, 0, maxq);  q = (code - z) * sc
+ *
+ * qllm_awq_quantize: w_nk [N,K] (fp16 / bf16 / fp32 by w_dtype, row-major), col_scale_k (nullable: 1) f32 [K], clip_ng (nullable: none)
+ * f32 [N, K/group_size]:  v = w * col_scale, rounded to w's type when that is a 16-bit one (what an in-place product leaves);
+ * v = clamp(v, -clip, clip); the grid above per (row, group).  Outputs, each nullable (not all of them): codes_kn i32 [K,N];
+ * scales_ng / zeros_ng f32 [N, K/group_size] (zero is integer-valued); wq_nk [N,K] = (code - z) * sc / col_scale rounded to w's type.
+ *
+ * qllm_awq_clip_search: auto_clip_layer as a quadratic form.  gram f32 [K/group_size][group_size][group_size], 16-byte aligned: per group
+ * the Gram matrix X^T X / tokens of the group's input channels.  Per (row, group) with org = max |w|, for i = 0 .. int(max_shrink *
+ * n_grid) - 1 (1..10 candidates):  m = org * float32(1 - i / n_grid);  d = pseudo_quantize(clamp(w, -m, m)) - w;  e_i = d^T gram_j d
+ * (fp32 FMAs) = the reference's ((x.q) - (x.w))^2 averaged over the tokens.  The first strict minimum below 1e9 wins (none: i = 0).
+ * Outputs: best_max_ng f32 = org * float32(1 - i / n_grid) of the winner, best_idx_ng i32 = i, err_ng2 f32 [N, K/group_size, 2] = (e_0, the
+ * winner's e).  Workspace: qllm_awq_clip_search_workspace_bytes() (pure; currently 0: workspace may then be NULL), 16-byte aligned.
+ *
+ * Both serve bits 2..8 and group_size 32 / 64 / 128 (others: QLLM_ERR_UNSUPPORTED); K % group_size != 0, NULL or misaligned buffers:
+ * QLLM_ERR_INVALID; a short or misaligned workspace: QLLM_ERR_WORKSPACE; all of it before any device work.  One launch each, no host
+ * synchronisation, no atomics, bit-reproducible, hipGraph-capturable.  Not served: symmetric grids, group_size = -1. */
+size_t qllm_awq_clip_search_workspace_bytes(int32_t N, int32_t K, int32_t group_size);
+int qllm_awq_clip_search(const void *w_nk, int32_t w_dtype, const float *gram, int32_t N, int32_t K, int32_t bits, int32_t group_size, int32_t n_grid,
+                         float max_shrink, float *best_max_ng, int32_t *best_idx_ng, float *err_ng2, void *workspace, size_t workspace_bytes,
+                         void *stream);
+int qllm_awq_quantize(const void *w_nk, int32_t w_dtype, const float *col_scale_k, const float *clip_ng, int32_t N, int32_t K, int32_t bits,
+                      int32_t group_size, int32_t *codes_kn, float *scales_ng, float *zeros_ng, void *wq_nk, void *stream);
 
 /* ---- tensor-parallel decode: one-shot all-reduce over peer-mapped staging buffers (ABI 4; fused form ABI 5) -------------------------------------- */
 /* For decode-sized tensors ([1, 8192] fp16 = 16 KB per row-parallel layer) a ring / tree all-reduce is pure latency.  On the xGMI

@@ -464,6 +464,49 @@ int qllm_gptq_quantize(const void *w_nk, int32_t w_dtype, const float *u_kk, int
                               (hipStream_t)stream);
 }
 
+size_t qllm_awq_clip_search_workspace_bytes(int32_t N, int32_t K, int32_t group_size) { return awq_clip_search_workspace_bytes(N, K, group_size); }
+
+// what the two AWQ entry points check alike: the weight, its type, the shape and the grid
+static int awq_check_layer(const void *w_nk, int32_t w_dtype, int32_t N, int32_t K, int32_t bits, int32_t group_size) {
+  if (!w_nk) return set_error(QLLM_ERR_INVALID, "w_nk must not be NULL");
+  if (w_dtype != QLLM_F16 && w_dtype != QLLM_BF16 && w_dtype != QLLM_F32) return set_error(QLLM_ERR_INVALID, "w_dtype must be QLLM_F16, QLLM_BF16 or QLLM_F32");
+  if (N <= 0 || K <= 0 || group_size <= 0) return set_error(QLLM_ERR_INVALID, "bad N/K/group_size (%d/%d/%d)", N, K, group_size);
+  if (!awq_quant_shape_ok(bits, group_size))
+    return set_error(QLLM_ERR_UNSUPPORTED, "the AWQ quantizer serves bits 2..8 and group_size 32 / 64 / 128 (got bits=%d group_size=%d)", bits, group_size);
+  if (K % group_size != 0) return set_error(QLLM_ERR_INVALID, "K must be a multiple of group_size (K=%d group_size=%d)", K, group_size);
+  if ((uintptr_t)w_nk % (w_dtype == QLLM_F32 ? 4 : 2)) return set_error(QLLM_ERR_INVALID, "every buffer must be aligned to its element size");
+  return QLLM_OK;
+}
+
+int qllm_awq_clip_search(const void *w_nk, int32_t w_dtype, const float *gram, int32_t N, int32_t K, int32_t bits, int32_t group_size, int32_t n_grid,
+                         float max_shrink, float *best_max_ng, int32_t *best_idx_ng, float *err_ng2, void *workspace, size_t workspace_bytes,
+                         void *stream) {
+  clear_error();
+  if (!gram || !best_max_ng || !best_idx_ng || !err_ng2) return set_error(QLLM_ERR_INVALID, "gram / best_max_ng / best_idx_ng / err_ng2 must not be NULL");
+  if (int rc = awq_check_layer(w_nk, w_dtype, N, K, bits, group_size)) return rc;
+  if (!awq_clip_candidates(n_grid, max_shrink))
+    return set_error(QLLM_ERR_UNSUPPORTED, "the clip search evaluates int(max_shrink * n_grid) = 1..10 candidates, 0 < max_shrink <= 1 (got n_grid=%d max_shrink=%g)",
+                     n_grid, (double)max_shrink);
+  if ((uintptr_t)gram % kAwqGramAlign) return set_error(QLLM_ERR_INVALID, "gram must be 16-byte aligned: its tiles are read four floats at a time");
+  if ((uintptr_t)best_max_ng % 4 || (uintptr_t)best_idx_ng % 4 || (uintptr_t)err_ng2 % 4)
+    return set_error(QLLM_ERR_INVALID, "every buffer must be aligned to its element size");
+  const size_t need = awq_clip_search_workspace_bytes(N, K, group_size);
+  if ((need && !workspace) || workspace_bytes < need || (uintptr_t)workspace % 16)
+    return set_error(QLLM_ERR_WORKSPACE, "qllm_awq_clip_search needs a 16-byte aligned workspace of %zu bytes (got %zu)", need, workspace ? workspace_bytes : (size_t)0);
+  return launch_awq_clip_search(w_nk, w_dtype, gram, N, K, bits, group_size, n_grid, max_shrink, best_max_ng, best_idx_ng, err_ng2, (hipStream_t)stream);
+}
+
+int qllm_awq_quantize(const void *w_nk, int32_t w_dtype, const float *col_scale_k, const float *clip_ng, int32_t N, int32_t K, int32_t bits,
+                      int32_t group_size, int32_t *codes_kn, float *scales_ng, float *zeros_ng, void *wq_nk, void *stream) {
+  clear_error();
+  if (int rc = awq_check_layer(w_nk, w_dtype, N, K, bits, group_size)) return rc;
+  if ((uintptr_t)col_scale_k % 4 || (uintptr_t)clip_ng % 4 || (uintptr_t)codes_kn % 4 || (uintptr_t)scales_ng % 4 || (uintptr_t)zeros_ng % 4 ||
+      (uintptr_t)wq_nk % (w_dtype == QLLM_F32 ? 4 : 2))
+    return set_error(QLLM_ERR_INVALID, "every buffer must be aligned to its element size");
+  if (!codes_kn && !scales_ng && !zeros_ng && !wq_nk) return set_error(QLLM_ERR_INVALID, "every output is NULL: nothing to write");
+  return launch_awq_quantize(w_nk, w_dtype, col_scale_k, clip_ng, N, K, bits, group_size, codes_kn, scales_ng, zeros_ng, wq_nk, (hipStream_t)stream);
+}
+
 int qllm_debug_timeline(void *buf, int32_t n_slots) {  // n_slots x 24 x u64
   clear_error();
   g_timeline = (uint64_t *)buf;

@@ -272,6 +272,16 @@ size_t gptq_quant_workspace_bytes(int N, int K);                  // pure: the f
 int launch_gptq_quantize(const void *w_nk, int w_dtype, const float *u_kk, int N, int K, int bits, int group_size, int sym, int32_t *codes_kn,
                          float *scales_ng, float *zeros_ng, void *wq_nk, float *loss_n, void *workspace, hipStream_t stream);
 
+// ---- awq_quant.hip (the AWQ quantizer: the clip search as a quadratic form over per-group Gram matrices, and the pseudo-quantizer) ---------
+constexpr int kAwqGramAlign = 16;                                 // the Gram tiles are staged four floats at a time
+bool awq_quant_shape_ok(int bits, int group_size);                // bits 2..8, group_size 32 / 64 / 128
+int awq_clip_candidates(int n_grid, float max_shrink);            // int(max_shrink * n_grid) where the search serves it (1..10), else 0
+size_t awq_clip_search_workspace_bytes(int N, int K, int group_size);   // pure: 0, the search lives in registers and LDS
+int launch_awq_clip_search(const void *w_nk, int w_dtype, const float *gram, int N, int K, int bits, int group_size, int n_grid, float max_shrink,
+                           float *best_max, int32_t *best_idx, float *err, hipStream_t stream);
+int launch_awq_quantize(const void *w_nk, int w_dtype, const float *col_scale, const float *clip_ng, int N, int K, int bits, int group_size,
+                        int32_t *codes_kn, float *scales_ng, float *zeros_ng, void *wq_nk, hipStream_t stream);
+
 // ---- tools/lab/gemm5.hip (lab builds: 256x128 tile, every wave a matrix wave, B fragments dequantised in registers) ------------------
 bool gemm5_ok(const GemmParams &p, int layout);
 int launch_gemm5(const GemmParams &p, int wm, hipStream_t stream);

@@ -431,6 +431,85 @@ def gptq_quantize(weight: torch.Tensor, u: Optional[torch.Tensor], bits: int, gr
     return codes, scales, zeros, wq, loss
 
 
+def _awq_layer(weight: torch.Tensor, group_size: int):
+    _check_input(weight, "weight")
+    if weight.dim() != 2 or weight.dtype not in _W_DTYPES:
+        raise RuntimeError(f"weight must be a 2-D float16 / bfloat16 / float32 tensor, got {tuple(weight.shape)} {weight.dtype}")
+    n, k = weight.shape
+    g = int(group_size)
+    return n, k, g, max(k // max(g, 1), 1)
+
+
+def _awq_f32(t: Optional[torch.Tensor], name: str, shape, dev):
+    if t is None:
+        return None
+    _check_input(t, name)
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or t.device != dev:
+        raise RuntimeError(f"{name} must be a contiguous float32 {tuple(shape)} tensor on {dev}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+    return t.data_ptr()
+
+
+def awq_quantize(weight: torch.Tensor, bits: int, group_size: int = 128, col_scale: Optional[torch.Tensor] = None,
+                 clip: Optional[torch.Tensor] = None, want=("codes", "scales", "zeros", "wq"), out=None):
+    """weight [N, K] (fp16 / bf16 / fp32 on the device) through the library's AWQ pseudo-quantizer (qllm_awq_quantize,
+    include/qllm_mi355x.h): v = weight * col_scale [K] (None: 1), clamped to +-clip [N, K/g] (None: not), on the asymmetric min/max grid
+    of every (row, group) -> (codes i32 [K, N], scales f32 [N, K/g], zeros f32 [N, K/g], wq [N, K] = dequantized / col_scale in
+    weight's dtype).  `want` names the outputs to produce, the others come back None (the scale search wants wq alone); `out`: that
+    tuple preallocated, None where an output is not wanted."""
+    n, k, g, groups = _awq_layer(weight, group_size)
+    lib = _lib.load()
+    dev = weight.device
+    shapes = (("codes", (k, n), torch.int32), ("scales", (n, groups), torch.float32), ("zeros", (n, groups), torch.float32),
+              ("wq", (n, k), weight.dtype))
+    if out is None:
+        unknown = set(want) - {name for name, _, _ in shapes}
+        if unknown:
+            raise TypeError(f"unknown outputs {sorted(unknown)}")
+        out = tuple(torch.empty(shape, dtype=dtype, device=dev) if name in want else None for name, shape, dtype in shapes)
+    for (name, shape, dtype), t in zip(shapes, out):
+        if t is None:
+            continue
+        _check_input(t, name)
+        if tuple(t.shape) != shape or t.dtype != dtype or t.device != dev:
+            raise RuntimeError(f"{name} must be a contiguous {dtype} {shape} tensor on {dev}")
+    s_ptr, c_ptr = _awq_f32(col_scale, "col_scale", (k,), dev), _awq_f32(clip, "clip", (n, groups), dev)
+    with torch.cuda.device(dev):
+        rc = lib.qllm_awq_quantize(weight.data_ptr(), _W_DTYPES[weight.dtype], s_ptr, c_ptr, n, k, int(bits), g,
+                                   *(t.data_ptr() if t is not None else None for t in out), _stream_ptr())
+    _lib.check(rc)
+    return tuple(out)
+
+
+def awq_clip_search(weight: torch.Tensor, gram: torch.Tensor, bits: int, group_size: int = 128, n_grid: int = 20, max_shrink: float = 0.5,
+                    out=None, workspace: Optional[torch.Tensor] = None):
+    """weight [N, K] (fp16 / bf16 / fp32 on the device) and gram f32 [K/g, g, g], the per-group Gram matrices X^T X / tokens of the
+    layer's input, through the library's clip search (qllm_awq_clip_search, include/qllm_mi355x.h): per (row, group) the clip
+    org * (1 - i / n_grid), i < int(max_shrink * n_grid), whose pseudo-quantized weights change the group's output least ->
+    (best_max f32 [N, K/g], best_idx i32 [N, K/g], err f32 [N, K/g, 2]: unclipped and chosen).  `out`: that tuple preallocated;
+    `workspace`: a uint8 tensor of at least qllm_awq_clip_search_workspace_bytes."""
+    n, k, g, groups = _awq_layer(weight, group_size)
+    lib = _lib.load()
+    dev = weight.device
+    g_ptr = _awq_f32(gram, "gram", (groups, g, g), dev)
+    if g_ptr is None:
+        raise RuntimeError("gram must not be None")
+    shapes = (("best_max", (n, groups), torch.float32), ("best_idx", (n, groups), torch.int32), ("err", (n, groups, 2), torch.float32))
+    if out is None:
+        out = tuple(torch.empty(shape, dtype=dtype, device=dev) for _, shape, dtype in shapes)
+    for (name, shape, dtype), t in zip(shapes, out):
+        _check_input(t, name)
+        if tuple(t.shape) != shape or t.dtype != dtype or t.device != dev:
+            raise RuntimeError(f"{name} must be a contiguous {dtype} {shape} tensor on {dev}")
+    need = lib.qllm_awq_clip_search_workspace_bytes(n, k, g)
+    ws = workspace if workspace is not None else (torch.empty(need, dtype=torch.uint8, device=dev) if need else None)
+    with torch.cuda.device(dev):
+        rc = lib.qllm_awq_clip_search(weight.data_ptr(), _W_DTYPES[weight.dtype], g_ptr, n, k, int(bits), g, int(n_grid), float(max_shrink),
+                                      out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), ws.data_ptr() if ws is not None else None,
+                                      ws.numel() if ws is not None else 0, _stream_ptr())
+    _lib.check(rc)
+    return tuple(out)
+
+
 def repack_native(w: QllmWeight, keep):
     """The layer behind descriptor `w` (GPTQ / AWQ GEMM / HQQ buffers, no g_idx) re-laid-out into the library's strip-major native
     layout (include/qllm_mi355x.h, "native layout") on its device: returns (QllmWeight, keepalive) like make_weight.  A pure integer

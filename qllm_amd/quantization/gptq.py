@@ -5,8 +5,8 @@ GPTQ.add_batch / GPTQ.fasterquant (gptq.py:75-102, 129-258) followed by QuantLin
 packing are torch / library plumbing, and the column walk -- the reference's six tiny launches per column -- is ONE library call per layer
 (qllm_gptq_quantize, csrc/gptq_quant.hip).  There is no CPU quantizer.
 
-Out of scope (the reference's other switches): static_groups, mse, the allow_mix_bits search, true_sequential, Conv layers; there is no
-AWQ quantizer either."""
+Out of scope (the reference's other switches): static_groups, mse, the allow_mix_bits search, true_sequential, Conv layers.  The AWQ
+quantizer is awq.py."""
 from __future__ import annotations
 
 import math
