@@ -15,7 +15,7 @@
 // Gm[a][own columns] with 16-byte LDS loads (8-byte at g = 32).  Lanes of one row read different rows of the tile at different bank
 // offsets (4l, resp. 2l + 32k, dwords): conflict-free; the four rows of a wave read the same addresses: a broadcast.  The products are
 // explicit FMAs (this file is compiled with -ffp-contract=off: the quantization arithmetic must round where the reference rounds).
-#include "kernels.hpp"
+#include "quant_common.hpp"
 
 namespace qllm {
 
@@ -23,19 +23,6 @@ namespace {
 
 constexpr int kRows = 16;    // rows per thread block
 constexpr int kCand = 10;    // the most clip candidates one search evaluates: int(max_shrink * n_grid) of the reference's defaults
-
-struct bf16_t { uint16_t bits; };
-__device__ __forceinline__ float to_f32(half_t v) { return (float)v; }
-__device__ __forceinline__ float to_f32(bf16_t v) { return __builtin_bit_cast(float, (uint32_t)v.bits << 16); }
-__device__ __forceinline__ float to_f32(float v) { return v; }
-__device__ __forceinline__ void from_f32(half_t *d, float v) { *d = (half_t)v; }
-__device__ __forceinline__ void from_f32(float *d, float v) { *d = v; }
-__device__ __forceinline__ void from_f32(bf16_t *d, float v) {  // round to nearest even (v is finite)
-  const uint32_t u = __builtin_bit_cast(uint32_t, v);
-  d->bits = (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
-// v rounded to the storage type T and back: what an in-place product leaves in a 16-bit tensor
-template <typename T> __device__ __forceinline__ float round_to(float v) { T t; from_f32(&t, v); return to_f32(t); }
 
 // the c-th column (of the group) that lane l of a row holds, CPL = g / 16 columns per lane
 template <int CPL> __device__ __forceinline__ int col_of(int l, int c) {
@@ -96,7 +83,7 @@ __global__ __launch_bounds__(256, 2) void awq_clip_kernel(AwqClipParams p) {
       mx = c ? fmaxf(mx, w[c]) : w[c];
     }
 #pragma unroll
-    for (int m = 1; m < 16; m <<= 1) { mn = fminf(mn, __shfl_xor(mn, m, 16)); mx = fmaxf(mx, __shfl_xor(mx, m, 16)); }
+    for (int m = 1; m < 16; m <<= 1) { const MinMax r = minmax_xor({mn, mx}, m); mn = r.mn; mx = r.mx; }
     const float org = fmaxf(fabsf(mn), fabsf(mx));
 
     // d = q - w of the candidates, kBatch at a time: at g = 128 ten of them with their travelling copy would not leave two blocks per CU
@@ -214,7 +201,7 @@ __global__ __launch_bounds__(256) void awq_quant_kernel(AwqQuantParams p) {
       mx = c ? fmaxf(mx, v[c]) : v[c];
     }
 #pragma unroll
-    for (int k = 1; k < 16; k <<= 1) { mn = fminf(mn, __shfl_xor(mn, k, 16)); mx = fmaxf(mx, __shfl_xor(mx, k, 16)); }
+    for (int k = 1; k < 16; k <<= 1) { const MinMax r = minmax_xor({mn, mx}, k); mn = r.mn; mx = r.mx; }
     float sc, z;
     grid_of(mn, mx, maxq, sc, z);
     if (live && l == 0) {
@@ -230,10 +217,7 @@ __global__ __launch_bounds__(256) void awq_quant_kernel(AwqQuantParams p) {
     }
     if (p.codes) {
       __syncthreads();
-      for (int idx = tid; idx < g * kRows; idx += 256) {
-        const int c = idx >> 4, nn = blockIdx.x * kRows + (idx & 15);
-        if (nn < N) p.codes[(size_t)(j * g + c) * N + nn] = s_q[idx];
-      }
+      for (int idx = tid; idx < g * kRows; idx += 256) store_code(p.codes, s_q, idx, j * g, blockIdx.x * kRows, N);
     }
   }
 }
@@ -282,12 +266,10 @@ int launch_awq_clip_search(const void *w_nk, int w_dtype, const float *gram, int
   p.err = err;
   p.N = N; p.K = K; p.g = g;
   p.nc = awq_clip_candidates(n_grid, max_shrink);
-  p.maxq = (float)((1 << bits) - 1);
+  p.maxq = maxq_of(bits);
   for (int i = 0; i < kCand; ++i) p.shrink[i] = (float)(1.0 - (double)i / (double)n_grid);
   const dim3 grid = grid_of_layer(N, K / g);
-  if (w_dtype == QLLM_F16) launch_clip<half_t>(p, grid, stream);
-  else if (w_dtype == QLLM_BF16) launch_clip<bf16_t>(p, grid, stream);
-  else launch_clip<float>(p, grid, stream);
+  with_w_type(w_dtype, [&](auto tag) { launch_clip<decltype(tag)>(p, grid, stream); });
   QLLM_HIP_CHECK(hipGetLastError());
   return QLLM_OK;
 }
@@ -303,11 +285,9 @@ int launch_awq_quantize(const void *w_nk, int w_dtype, const float *col_scale, c
   p.zeros = zeros_ng;
   p.wq = wq_nk;
   p.N = N; p.K = K; p.g = g;
-  p.maxq = (float)((1 << bits) - 1);
+  p.maxq = maxq_of(bits);
   const dim3 grid = grid_of_layer(N, K / g);
-  if (w_dtype == QLLM_F16) launch_quant<half_t>(p, grid, stream);
-  else if (w_dtype == QLLM_BF16) launch_quant<bf16_t>(p, grid, stream);
-  else launch_quant<float>(p, grid, stream);
+  with_w_type(w_dtype, [&](auto tag) { launch_quant<decltype(tag)>(p, grid, stream); });
   QLLM_HIP_CHECK(hipGetLastError());
   return QLLM_OK;
 }

@@ -72,6 +72,27 @@ static int check_io(const void *x, const void *y, int M, int act_dtype) {
   return QLLM_OK;
 }
 
+// What the four quantizer entry points check first, alike: the pointers they require (`required` names them, w_nk among them), the
+// weight's type and N / K / group_size.  Each entry's own checks follow in the order they have always fired.
+static int check_quant_layer(const char *required, bool missing, int32_t w_dtype, int32_t N, int32_t K, int32_t group_size) {
+  if (missing) return set_error(QLLM_ERR_INVALID, "%s must not be NULL", required);
+  if (w_dtype != QLLM_F16 && w_dtype != QLLM_BF16 && w_dtype != QLLM_F32) return set_error(QLLM_ERR_INVALID, "w_dtype must be QLLM_F16, QLLM_BF16 or QLLM_F32");
+  if (N <= 0 || K <= 0 || group_size <= 0) return set_error(QLLM_ERR_INVALID, "bad N/K/group_size (%d/%d/%d)", N, K, group_size);
+  return QLLM_OK;
+}
+static int check_whole_groups(int32_t K, int32_t group_size) {
+  if (K % group_size != 0) return set_error(QLLM_ERR_INVALID, "K must be a multiple of group_size (K=%d group_size=%d)", K, group_size);
+  return QLLM_OK;
+}
+static int elem_size(int32_t w_dtype) { return w_dtype == QLLM_F32 ? 4 : 2; }
+static const char *const kElemAligned = "every buffer must be aligned to its element size";
+
+static int check_workspace(const char *entry, const void *workspace, size_t workspace_bytes, size_t need) {
+  if ((need && !workspace) || workspace_bytes < need || (uintptr_t)workspace % 16)
+    return set_error(QLLM_ERR_WORKSPACE, "%s needs a 16-byte aligned workspace of %zu bytes (got %zu)", entry, need, workspace ? workspace_bytes : (size_t)0);
+  return QLLM_OK;
+}
+
 // ---- parameter-block fills shared by the run_* functions ------------------------------------------------------------------------------
 // diagnostics: timeline buffer handed to the native-layout decode launches (24 x u64 per launch), see qllm_debug_timeline()
 static uint64_t *g_timeline = nullptr;
@@ -418,9 +439,7 @@ int qllm_hqq_quantize(const void *w_nk, int32_t w_dtype, int32_t N, int32_t K, i
                       float beta, float kappa, void *qweight, void *scales, void *zeros, int32_t *rounds_run_dev, void *workspace,
                       size_t workspace_bytes, void *stream) {
   clear_error();
-  if (!w_nk || !qweight || !scales || !zeros) return set_error(QLLM_ERR_INVALID, "w_nk / qweight / scales / zeros must not be NULL");
-  if (w_dtype != QLLM_F16 && w_dtype != QLLM_BF16 && w_dtype != QLLM_F32) return set_error(QLLM_ERR_INVALID, "w_dtype must be QLLM_F16, QLLM_BF16 or QLLM_F32");
-  if (N <= 0 || K <= 0 || group_size <= 0) return set_error(QLLM_ERR_INVALID, "bad N/K/group_size (%d/%d/%d)", N, K, group_size);
+  if (int rc = check_quant_layer("w_nk / qweight / scales / zeros", !w_nk || !qweight || !scales || !zeros, w_dtype, N, K, group_size)) return rc;
   if (bits < 1 || bits > 8) return set_error(QLLM_ERR_INVALID, "bad bits (%d)", bits);
   if (iters < 1 || iters > 64) return set_error(QLLM_ERR_INVALID, "iters must be 1..64 (got %d)", iters);
   if (!(beta > 0.f) || !(kappa > 0.f) || !(lp_norm > 0.f)) return set_error(QLLM_ERR_INVALID, "lp_norm, beta and kappa must be positive");
@@ -430,9 +449,7 @@ int qllm_hqq_quantize(const void *w_nk, int32_t w_dtype, int32_t N, int32_t K, i
     return set_error(QLLM_ERR_UNSUPPORTED, "the HQQ quantizer serves bits 2/3/4/8, group_size %% 32 == 0 in 32..1024, K %% group_size == 0, N %% 16 == 0 "
                      "(got bits=%d group_size=%d K=%d N=%d)", bits, group_size, K, N);
   if (!(lp_norm < 1.f)) return set_error(QLLM_ERR_UNSUPPORTED, "the HQQ quantizer serves lp_norm < 1 (got %g)", (double)lp_norm);
-  const size_t need = hqq_quant_workspace_bytes(N, K, group_size, iters);
-  if (!workspace || workspace_bytes < need || (uintptr_t)workspace % 16)
-    return set_error(QLLM_ERR_WORKSPACE, "qllm_hqq_quantize needs a 16-byte aligned workspace of %zu bytes (got %zu)", need, workspace ? workspace_bytes : (size_t)0);
+  if (int rc = check_workspace("qllm_hqq_quantize", workspace, workspace_bytes, hqq_quant_workspace_bytes(N, K, group_size, iters))) return rc;
   return launch_hqq_quantize(w_nk, w_dtype, N, K, bits, group_size, iters, lp_norm, beta, kappa, qweight, scales, zeros, rounds_run_dev, workspace,
                              workspace_bytes, (hipStream_t)stream);
 }
@@ -443,23 +460,20 @@ int qllm_gptq_quantize(const void *w_nk, int32_t w_dtype, const float *u_kk, int
                        int32_t *codes_kn, float *scales_ng, float *zeros_ng, void *wq_nk, float *loss_n, void *workspace, size_t workspace_bytes,
                        void *stream) {
   clear_error();
-  if (!w_nk || !codes_kn || !scales_ng || !zeros_ng) return set_error(QLLM_ERR_INVALID, "w_nk / codes_kn / scales_ng / zeros_ng must not be NULL");
-  if (w_dtype != QLLM_F16 && w_dtype != QLLM_BF16 && w_dtype != QLLM_F32) return set_error(QLLM_ERR_INVALID, "w_dtype must be QLLM_F16, QLLM_BF16 or QLLM_F32");
-  if (N <= 0 || K <= 0 || group_size <= 0) return set_error(QLLM_ERR_INVALID, "bad N/K/group_size (%d/%d/%d)", N, K, group_size);
+  if (int rc = check_quant_layer("w_nk / codes_kn / scales_ng / zeros_ng", !w_nk || !codes_kn || !scales_ng || !zeros_ng, w_dtype, N, K, group_size))
+    return rc;
   if (sym < 0 || sym > 1) return set_error(QLLM_ERR_INVALID, "sym must be 0 or 1 (got %d)", sym);
   if (!gptq_quant_shape_ok(K, bits, group_size))
     return set_error(QLLM_ERR_UNSUPPORTED, "the GPTQ quantizer serves bits 2..8 and group_size 32 / 64 / 128 / K (got bits=%d group_size=%d K=%d)",
                      bits, group_size, K);
-  if (K % group_size != 0) return set_error(QLLM_ERR_INVALID, "K must be a multiple of group_size (K=%d group_size=%d)", K, group_size);
+  if (int rc = check_whole_groups(K, group_size)) return rc;
   if (K % 4 != 0) return set_error(QLLM_ERR_INVALID, "K must be a multiple of 4 (K=%d)", K);
   if ((uintptr_t)u_kk % 16) return set_error(QLLM_ERR_INVALID, "u_kk must be 16-byte aligned: its tiles are read four floats at a time");
-  const int esz = w_dtype == QLLM_F32 ? 4 : 2;
+  const int esz = elem_size(w_dtype);
   if ((uintptr_t)w_nk % esz || (uintptr_t)wq_nk % esz || (uintptr_t)codes_kn % 4 || (uintptr_t)scales_ng % 4 ||
       (uintptr_t)zeros_ng % 4 || (uintptr_t)loss_n % 4)
-    return set_error(QLLM_ERR_INVALID, "every buffer must be aligned to its element size");
-  const size_t need = gptq_quant_workspace_bytes(N, K);
-  if (!workspace || workspace_bytes < need || (uintptr_t)workspace % 16)
-    return set_error(QLLM_ERR_WORKSPACE, "qllm_gptq_quantize needs a 16-byte aligned workspace of %zu bytes (got %zu)", need, workspace ? workspace_bytes : (size_t)0);
+    return set_error(QLLM_ERR_INVALID, "%s", kElemAligned);
+  if (int rc = check_workspace("qllm_gptq_quantize", workspace, workspace_bytes, gptq_quant_workspace_bytes(N, K))) return rc;
   return launch_gptq_quantize(w_nk, w_dtype, u_kk, N, K, bits, group_size, sym, codes_kn, scales_ng, zeros_ng, wq_nk, loss_n, workspace,
                               (hipStream_t)stream);
 }
@@ -468,13 +482,11 @@ size_t qllm_awq_clip_search_workspace_bytes(int32_t N, int32_t K, int32_t group_
 
 // what the two AWQ entry points check alike: the weight, its type, the shape and the grid
 static int awq_check_layer(const void *w_nk, int32_t w_dtype, int32_t N, int32_t K, int32_t bits, int32_t group_size) {
-  if (!w_nk) return set_error(QLLM_ERR_INVALID, "w_nk must not be NULL");
-  if (w_dtype != QLLM_F16 && w_dtype != QLLM_BF16 && w_dtype != QLLM_F32) return set_error(QLLM_ERR_INVALID, "w_dtype must be QLLM_F16, QLLM_BF16 or QLLM_F32");
-  if (N <= 0 || K <= 0 || group_size <= 0) return set_error(QLLM_ERR_INVALID, "bad N/K/group_size (%d/%d/%d)", N, K, group_size);
+  if (int rc = check_quant_layer("w_nk", !w_nk, w_dtype, N, K, group_size)) return rc;
   if (!awq_quant_shape_ok(bits, group_size))
     return set_error(QLLM_ERR_UNSUPPORTED, "the AWQ quantizer serves bits 2..8 and group_size 32 / 64 / 128 (got bits=%d group_size=%d)", bits, group_size);
-  if (K % group_size != 0) return set_error(QLLM_ERR_INVALID, "K must be a multiple of group_size (K=%d group_size=%d)", K, group_size);
-  if ((uintptr_t)w_nk % (w_dtype == QLLM_F32 ? 4 : 2)) return set_error(QLLM_ERR_INVALID, "every buffer must be aligned to its element size");
+  if (int rc = check_whole_groups(K, group_size)) return rc;
+  if ((uintptr_t)w_nk % elem_size(w_dtype)) return set_error(QLLM_ERR_INVALID, "%s", kElemAligned);
   return QLLM_OK;
 }
 
@@ -488,11 +500,8 @@ int qllm_awq_clip_search(const void *w_nk, int32_t w_dtype, const float *gram, i
     return set_error(QLLM_ERR_UNSUPPORTED, "the clip search evaluates int(max_shrink * n_grid) = 1..10 candidates, 0 < max_shrink <= 1 (got n_grid=%d max_shrink=%g)",
                      n_grid, (double)max_shrink);
   if ((uintptr_t)gram % kAwqGramAlign) return set_error(QLLM_ERR_INVALID, "gram must be 16-byte aligned: its tiles are read four floats at a time");
-  if ((uintptr_t)best_max_ng % 4 || (uintptr_t)best_idx_ng % 4 || (uintptr_t)err_ng2 % 4)
-    return set_error(QLLM_ERR_INVALID, "every buffer must be aligned to its element size");
-  const size_t need = awq_clip_search_workspace_bytes(N, K, group_size);
-  if ((need && !workspace) || workspace_bytes < need || (uintptr_t)workspace % 16)
-    return set_error(QLLM_ERR_WORKSPACE, "qllm_awq_clip_search needs a 16-byte aligned workspace of %zu bytes (got %zu)", need, workspace ? workspace_bytes : (size_t)0);
+  if ((uintptr_t)best_max_ng % 4 || (uintptr_t)best_idx_ng % 4 || (uintptr_t)err_ng2 % 4) return set_error(QLLM_ERR_INVALID, "%s", kElemAligned);
+  if (int rc = check_workspace("qllm_awq_clip_search", workspace, workspace_bytes, awq_clip_search_workspace_bytes(N, K, group_size))) return rc;
   return launch_awq_clip_search(w_nk, w_dtype, gram, N, K, bits, group_size, n_grid, max_shrink, best_max_ng, best_idx_ng, err_ng2, (hipStream_t)stream);
 }
 
@@ -501,8 +510,8 @@ int qllm_awq_quantize(const void *w_nk, int32_t w_dtype, const float *col_scale_
   clear_error();
   if (int rc = awq_check_layer(w_nk, w_dtype, N, K, bits, group_size)) return rc;
   if ((uintptr_t)col_scale_k % 4 || (uintptr_t)clip_ng % 4 || (uintptr_t)codes_kn % 4 || (uintptr_t)scales_ng % 4 || (uintptr_t)zeros_ng % 4 ||
-      (uintptr_t)wq_nk % (w_dtype == QLLM_F32 ? 4 : 2))
-    return set_error(QLLM_ERR_INVALID, "every buffer must be aligned to its element size");
+      (uintptr_t)wq_nk % elem_size(w_dtype))
+    return set_error(QLLM_ERR_INVALID, "%s", kElemAligned);
   if (!codes_kn && !scales_ng && !zeros_ng && !wq_nk) return set_error(QLLM_ERR_INVALID, "every output is NULL: nothing to write");
   return launch_awq_quantize(w_nk, w_dtype, col_scale_k, clip_ng, N, K, bits, group_size, codes_kn, scales_ng, zeros_ng, wq_nk, (hipStream_t)stream);
 }

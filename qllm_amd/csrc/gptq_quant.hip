@@ -17,7 +17,7 @@
 //   4. codes leave through an LDS transpose ([column][16 rows]) so that 16 consecutive int32 along N are stored together.
 // No block waits for another one: no grid-wide synchronisation, no atomics, bit-reproducible.  u == NULL skips 1 and 3: round-to-nearest
 // on the same grid.
-#include "kernels.hpp"
+#include "quant_common.hpp"
 
 namespace qllm {
 
@@ -25,17 +25,6 @@ namespace {
 
 constexpr int kBlk = 128;    // the reference's blocksize: when group parameters are found depends on it, so it is semantics
 constexpr int kRows = 16;    // rows per thread block
-
-struct bf16_t { uint16_t bits; };
-__device__ __forceinline__ float to_f32(half_t v) { return (float)v; }
-__device__ __forceinline__ float to_f32(bf16_t v) { return __builtin_bit_cast(float, (uint32_t)v.bits << 16); }
-__device__ __forceinline__ float to_f32(float v) { return v; }
-__device__ __forceinline__ void from_f32(half_t *d, float v) { *d = (half_t)v; }
-__device__ __forceinline__ void from_f32(float *d, float v) { *d = v; }
-__device__ __forceinline__ void from_f32(bf16_t *d, float v) {  // round to nearest even (v is finite)
-  const uint32_t u = __builtin_bit_cast(uint32_t, v);
-  d->bits = (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
 
 // InternalGPTQQuantizer.find_params on the minimum / maximum of one row's group (both already taken against 0)
 __device__ __forceinline__ void find_params(float xmin, float xmax, float maxq, bool sym, float &scale, float &zero) {
@@ -92,7 +81,7 @@ __global__ __launch_bounds__(256) void gptq_quant_kernel(GptqQuantParams p) {
     if (live)
       for (int j = l; j < K; j += 16) { const float v = to_f32(wrow[j]); mn = fminf(mn, v); mx = fmaxf(mx, v); }
 #pragma unroll
-    for (int m = 1; m < 16; m <<= 1) { mn = fminf(mn, __shfl_xor(mn, m, 16)); mx = fmaxf(mx, __shfl_xor(mx, m, 16)); }
+    for (int m = 1; m < 16; m <<= 1) { const MinMax r = minmax_xor({mn, mx}, m); mn = r.mn; mx = r.mx; }
     find_params(mn, mx, maxq, sym, rs, rz);
     if (live && l == 0) { p.scales[n] = rs; p.zeros[n] = rz; }
   }
@@ -145,8 +134,8 @@ __global__ __launch_bounds__(256) void gptq_quant_kernel(GptqQuantParams p) {
         mn[h] = fminf(fminf(fminf(w[4 * h], w[4 * h + 1]), fminf(w[4 * h + 2], w[4 * h + 3])), 0.f);
         mx[h] = fmaxf(fmaxf(fmaxf(w[4 * h], w[4 * h + 1]), fmaxf(w[4 * h + 2], w[4 * h + 3])), 0.f);
 #pragma unroll
-        for (int m = 1; m < 8; m <<= 1) { mn[h] = fminf(mn[h], __shfl_xor(mn[h], m, 16)); mx[h] = fmaxf(mx[h], __shfl_xor(mx[h], m, 16)); }
-        if (g >= 64) { mn[h] = fminf(mn[h], __shfl_xor(mn[h], 8, 16)); mx[h] = fmaxf(mx[h], __shfl_xor(mx[h], 8, 16)); }
+        for (int m = 1; m < 8; m <<= 1) { const MinMax r = minmax_xor({mn[h], mx[h]}, m); mn[h] = r.mn; mx[h] = r.mx; }
+        if (g >= 64) { const MinMax r = minmax_xor({mn[h], mx[h]}, 8); mn[h] = r.mn; mx[h] = r.mx; }
       }
       if (g == 128) { mn[0] = mn[1] = fminf(mn[0], mn[1]); mx[0] = mx[1] = fmaxf(mx[0], mx[1]); }
 #pragma unroll
@@ -227,10 +216,7 @@ __global__ __launch_bounds__(256) void gptq_quant_kernel(GptqQuantParams p) {
       }
     }
     __syncthreads();
-    for (int idx = tid; idx < count * kRows; idx += 256) {
-      const int c = idx >> 4, nn = blockIdx.x * kRows + (idx & 15);
-      if (nn < N) p.codes[(size_t)(i1 + c) * N + nn] = s_q[idx];
-    }
+    for (int idx = tid; idx < count * kRows; idx += 256) store_code(p.codes, s_q, idx, i1, blockIdx.x * kRows, N);
   }
   if (p.loss) {
 #pragma unroll
@@ -260,11 +246,9 @@ int launch_gptq_quantize(const void *w_nk, int w_dtype, const float *u_kk, int N
   p.loss = loss_n;
   p.err = (float *)workspace;
   p.N = N; p.K = K; p.g = g; p.sym = sym;
-  p.maxq = (float)((1 << bits) - 1);
+  p.maxq = maxq_of(bits);
   const dim3 grid((N + kRows - 1) / kRows), block(256);
-  if (w_dtype == QLLM_F16) hipLaunchKernelGGL((gptq_quant_kernel<half_t>), grid, block, 0, stream, p);
-  else if (w_dtype == QLLM_BF16) hipLaunchKernelGGL((gptq_quant_kernel<bf16_t>), grid, block, 0, stream, p);
-  else hipLaunchKernelGGL((gptq_quant_kernel<float>), grid, block, 0, stream, p);
+  with_w_type(w_dtype, [&](auto tag) { hipLaunchKernelGGL((gptq_quant_kernel<decltype(tag)>), grid, block, 0, stream, p); });
   QLLM_HIP_CHECK(hipGetLastError());
   return QLLM_OK;
 }

@@ -13,7 +13,7 @@
 //           rounds the reference would have run to the workspace (and to rounds_run_dev);
 //   pass 2  reads that number, re-runs that many rounds (the same instructions on the same data: the same bits) and encodes.
 // Codes go through an LDS transpose ([k][16 rows] bytes) so that each packed word row is stored as 16 consecutive int32 along N.
-#include "kernels.hpp"
+#include "quant_common.hpp"
 
 namespace qllm {
 
@@ -45,11 +45,6 @@ __device__ __forceinline__ float row_max(float v) {
   v = fmaxf(v, dpp_peer<0x141>(v));
   return fmaxf(v, dpp_peer<0x140>(v));
 }
-
-struct bf16_t { uint16_t bits; };
-__device__ __forceinline__ float to_f32(half_t v) { return (float)v; }
-__device__ __forceinline__ float to_f32(bf16_t v) { return __builtin_bit_cast(float, (uint32_t)v.bits << 16); }
-__device__ __forceinline__ float to_f32(float v) { return v; }
 
 // E elements of T at `src`: one aligned vector read when the lane owns exactly E (e == E: src is then E * sizeof(T) aligned),
 // element reads under `j < e` for group sizes between two instantiations
@@ -221,9 +216,7 @@ static void hqq_launch_e(const HqqQuantParams &p, int blocks, hipStream_t stream
 }
 
 static void hqq_launch(const HqqQuantParams &p, int w_dtype, int blocks, hipStream_t stream) {
-  if (w_dtype == QLLM_F16) hqq_launch_e<half_t>(p, blocks, stream);
-  else if (w_dtype == QLLM_BF16) hqq_launch_e<bf16_t>(p, blocks, stream);
-  else hqq_launch_e<float>(p, blocks, stream);
+  with_w_type(w_dtype, [&](auto tag) { hqq_launch_e<decltype(tag)>(p, blocks, stream); });
 }
 
 int launch_hqq_quantize(const void *w_nk, int w_dtype, int N, int K, int bits, int g, int iters, float lp_norm, float beta, float kappa,
@@ -236,7 +229,7 @@ int launch_hqq_quantize(const void *w_nk, int w_dtype, int N, int K, int bits, i
   p.zeros = (half_t *)zeros;
   p.N = N; p.K = K; p.g = g; p.bits = bits; p.iters = iters; p.e = g / 16;
   p.tiles = (N / 16) * (K / g);
-  p.max_v = (float)((1 << bits) - 1);
+  p.max_v = maxq_of(bits);
   p.pm1 = (float)((double)lp_norm - 1.0);
   double b = (double)beta;
   for (int r = 0; r < 64; ++r) {

@@ -260,6 +260,7 @@ int gemm3_split_k(int M, int N, int K);
 int launch_gemm3(const GemmParams &p, int layout, hipStream_t stream);
 int launch_bf16_to_f16(const void *src, void *dst, size_t n, hipStream_t stream);  // elementwise RNE conversion (gemm3's bf16 pre-pass)
 
+// (the three quantizers share quant_common.hpp: storage types and conversions, dtype dispatch, the min / max butterfly step, the codes store)
 // ---- hqq_quant.hip (ABI 7: the HQQ proximal solver + encoder, fp16 / bf16 / fp32 W[N,K] -> HQQ row stream) ---------------------------------
 bool hqq_quant_shape_ok(int N, int K, int bits, int group_size);
 size_t hqq_quant_workspace_bytes(int N, int K, int group_size, int iters);  // pure; 0 for shapes that are never served

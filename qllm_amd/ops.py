@@ -356,36 +356,59 @@ def pack_qweight(q_kn: torch.Tensor, layout: str, bits: int) -> torch.Tensor:
 _W_DTYPES = {torch.float16: DT_F16, torch.bfloat16: DT_BF16, torch.float32: _lib.DT_F32}
 
 
+def _check_weight(weight: torch.Tensor):
+    """The quantizers' input: a contiguous 2-D fp16 / bf16 / fp32 device tensor -> (N, K, the library's code of its dtype)."""
+    _check_input(weight, "weight")
+    if weight.dim() != 2 or weight.dtype not in _W_DTYPES:
+        raise RuntimeError(f"weight must be a 2-D float16 / bfloat16 / float32 tensor, got {tuple(weight.shape)} {weight.dtype}")
+    return weight.shape[0], weight.shape[1], _W_DTYPES[weight.dtype]
+
+
+def _outputs(spec, out, want, dev, optional=()):
+    """A quantizer's output tuple.  spec: ((name, shape, dtype), ..).  out None: the outputs named in `want` are allocated on dev, the
+    others are None; else `out` is the caller's tuple, where only the names in `optional` may be None.  Every tensor is checked."""
+    if out is None:
+        unknown = set(want) - {name for name, _, _ in spec}
+        if unknown:
+            raise TypeError(f"unknown outputs {sorted(unknown)}")
+        out = tuple(torch.empty(shape, dtype=dtype, device=dev) if name in want else None for name, shape, dtype in spec)
+    for (name, shape, dtype), t in zip(spec, out):
+        if t is None and name in optional:
+            continue
+        _check_input(t, name)
+        if tuple(t.shape) != shape or t.dtype != dtype or t.device != dev:
+            raise RuntimeError(f"{name} must be a contiguous {dtype} {shape} tensor on {dev}")
+    return tuple(out)
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return t.data_ptr() if t is not None else None
+
+
 def hqq_quantize(weight: torch.Tensor, bits: int, group_size: int = 64, iters: int = 20, lp_norm: float = 0.7, beta: float = 10.0,
                  kappa: float = 1.01, debug: bool = False):
     """weight [N, K] (fp16 / bf16 / fp32, on the device) -> the HQQ layer buffers, by the library's fused proximal solver
     (qllm_hqq_quantize, include/qllm_mi355x.h): (qweight i32 [K*bits/32, N], scales f16 [K/g, N], zeros f16 [K/g, N], rounds_run i32 [1]
     on the device).  `debug` appends the solver's own fp32 (s [K/g, N], z [K/g, N], per-round tensor-wide mean errors [iters])."""
-    _check_input(weight, "weight")
-    if weight.dim() != 2 or weight.dtype not in _W_DTYPES:
-        raise RuntimeError(f"weight must be a 2-D float16 / bfloat16 / float32 tensor, got {tuple(weight.shape)} {weight.dtype}")
+    n, k, code = _check_weight(weight)
     lib = _lib.load()
-    n, k = weight.shape
     g = k if group_size == -1 else int(group_size)
     dev = weight.device
     need = lib.qllm_hqq_quantize_workspace_bytes(n, k, g, int(iters))
     groups = n * (k // g) if g > 0 and k % g == 0 else 0
     dbg_at = (need + 255) // 256 * 256
     ws = torch.empty(max(dbg_at + (8 * groups if debug else 0), 16), dtype=torch.uint8, device=dev)
-    qweight = torch.empty((max(k * bits // 32, 0), n), dtype=torch.int32, device=dev)
-    scales = torch.empty((max(k // max(g, 1), 1), n), dtype=torch.float16, device=dev)
-    zeros = torch.empty_like(scales)
-    rounds = torch.empty(1, dtype=torch.int32, device=dev)
+    rows = max(k // max(g, 1), 1)
+    spec = (((max(k * bits // 32, 0), n), torch.int32), ((rows, n), torch.float16), ((rows, n), torch.float16), ((1,), torch.int32))
+    out = tuple(torch.empty(shape, dtype=dtype, device=dev) for shape, dtype in spec)   # qweight, scales, zeros, rounds
     with torch.cuda.device(dev):
-        rc = lib.qllm_hqq_quantize(weight.data_ptr(), _W_DTYPES[weight.dtype], n, k, int(bits), g, int(iters), float(lp_norm), float(beta),
-                                   float(kappa), qweight.data_ptr(), scales.data_ptr(), zeros.data_ptr(), rounds.data_ptr(), ws.data_ptr(),
-                                   ws.numel() if debug else need, _stream_ptr())
+        rc = lib.qllm_hqq_quantize(weight.data_ptr(), code, n, k, int(bits), g, int(iters), float(lp_norm), float(beta), float(kappa),
+                                   *(t.data_ptr() for t in out), ws.data_ptr(), ws.numel() if debug else need, _stream_ptr())
     _lib.check(rc)
     if not debug:
-        return qweight, scales, zeros, rounds
+        return out
     f = ws[dbg_at:dbg_at + 8 * groups].view(torch.float32)
-    return (qweight, scales, zeros, rounds, f[:groups].view(k // g, n).clone(), f[groups:].view(k // g, n).clone(),
-            ws[256:256 + 4 * int(iters)].view(torch.float32).clone())
+    return out + (f[:groups].view(k // g, n).clone(), f[groups:].view(k // g, n).clone(), ws[256:256 + 4 * int(iters)].view(torch.float32).clone())
 
 
 def gptq_quantize(weight: torch.Tensor, u: Optional[torch.Tensor], bits: int, group_size: int = 128, sym: bool = False,
@@ -395,11 +418,8 @@ def gptq_quantize(weight: torch.Tensor, u: Optional[torch.Tensor], bits: int, gr
     include/qllm_mi355x.h): (codes i32 [K, N], scales f32 [N, K/g], zeros f32 [N, K/g], wq [N, K] in weight's dtype or None,
     loss f32 [N]).  `out`: that tuple preallocated (wq may be None); `workspace`: a uint8 tensor of at least
     qllm_gptq_quantize_workspace_bytes -- both for callers that capture the call in a graph or own the memory."""
-    _check_input(weight, "weight")
-    if weight.dim() != 2 or weight.dtype not in _W_DTYPES:
-        raise RuntimeError(f"weight must be a 2-D float16 / bfloat16 / float32 tensor, got {tuple(weight.shape)} {weight.dtype}")
+    n, k, code = _check_weight(weight)
     lib = _lib.load()
-    n, k = weight.shape
     g = k if group_size == -1 else int(group_size)
     dev = weight.device
     if u is not None:
@@ -407,37 +427,16 @@ def gptq_quantize(weight: torch.Tensor, u: Optional[torch.Tensor], bits: int, gr
         if u.dtype != torch.float32 or tuple(u.shape) != (k, k) or u.device != dev:
             raise RuntimeError(f"u must be a float32 [{k}, {k}] tensor on {dev}, got {tuple(u.shape)} {u.dtype} on {u.device}")
     groups = max(k // max(g, 1), 1)
-    if out is None:
-        out = (torch.empty((k, n), dtype=torch.int32, device=dev), torch.empty((n, groups), dtype=torch.float32, device=dev),
-               torch.empty((n, groups), dtype=torch.float32, device=dev), torch.empty_like(weight) if want_wq else None,
-               torch.empty(n, dtype=torch.float32, device=dev))
-    codes, scales, zeros, wq, loss = out
-    for name, t, shape, dtype in (("codes", codes, (k, n), torch.int32), ("scales", scales, (n, groups), torch.float32),
-                                  ("zeros", zeros, (n, groups), torch.float32), ("wq", wq, (n, k), weight.dtype),
-                                  ("loss", loss, (n,), torch.float32)):
-        if t is None and name in ("wq", "loss"):
-            continue
-        _check_input(t, name)
-        if tuple(t.shape) != shape or t.dtype != dtype or t.device != dev:
-            raise RuntimeError(f"{name} must be a contiguous {dtype} {shape} tensor on {dev}")
+    spec = (("codes", (k, n), torch.int32), ("scales", (n, groups), torch.float32), ("zeros", (n, groups), torch.float32),
+            ("wq", (n, k), weight.dtype), ("loss", (n,), torch.float32))
+    out = _outputs(spec, out, [name for name, _, _ in spec if want_wq or name != "wq"], dev, optional=("wq", "loss"))
     need = lib.qllm_gptq_quantize_workspace_bytes(n, k)
     ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev) if workspace is None else workspace
     with torch.cuda.device(dev):
-        rc = lib.qllm_gptq_quantize(weight.data_ptr(), _W_DTYPES[weight.dtype], u.data_ptr() if u is not None else None, n, k, int(bits), g,
-                                    1 if sym else 0, codes.data_ptr(), scales.data_ptr(), zeros.data_ptr(),
-                                    wq.data_ptr() if wq is not None else None, loss.data_ptr() if loss is not None else None,
+        rc = lib.qllm_gptq_quantize(weight.data_ptr(), code, _ptr(u), n, k, int(bits), g, 1 if sym else 0, *(_ptr(t) for t in out),
                                     ws.data_ptr(), ws.numel(), _stream_ptr())
     _lib.check(rc)
-    return codes, scales, zeros, wq, loss
-
-
-def _awq_layer(weight: torch.Tensor, group_size: int):
-    _check_input(weight, "weight")
-    if weight.dim() != 2 or weight.dtype not in _W_DTYPES:
-        raise RuntimeError(f"weight must be a 2-D float16 / bfloat16 / float32 tensor, got {tuple(weight.shape)} {weight.dtype}")
-    n, k = weight.shape
-    g = int(group_size)
-    return n, k, g, max(k // max(g, 1), 1)
+    return out
 
 
 def _awq_f32(t: Optional[torch.Tensor], name: str, shape, dev):
@@ -456,28 +455,19 @@ def awq_quantize(weight: torch.Tensor, bits: int, group_size: int = 128, col_sca
     of every (row, group) -> (codes i32 [K, N], scales f32 [N, K/g], zeros f32 [N, K/g], wq [N, K] = dequantized / col_scale in
     weight's dtype).  `want` names the outputs to produce, the others come back None (the scale search wants wq alone); `out`: that
     tuple preallocated, None where an output is not wanted."""
-    n, k, g, groups = _awq_layer(weight, group_size)
+    n, k, code = _check_weight(weight)
+    g = int(group_size)
+    groups = max(k // max(g, 1), 1)
     lib = _lib.load()
     dev = weight.device
-    shapes = (("codes", (k, n), torch.int32), ("scales", (n, groups), torch.float32), ("zeros", (n, groups), torch.float32),
-              ("wq", (n, k), weight.dtype))
-    if out is None:
-        unknown = set(want) - {name for name, _, _ in shapes}
-        if unknown:
-            raise TypeError(f"unknown outputs {sorted(unknown)}")
-        out = tuple(torch.empty(shape, dtype=dtype, device=dev) if name in want else None for name, shape, dtype in shapes)
-    for (name, shape, dtype), t in zip(shapes, out):
-        if t is None:
-            continue
-        _check_input(t, name)
-        if tuple(t.shape) != shape or t.dtype != dtype or t.device != dev:
-            raise RuntimeError(f"{name} must be a contiguous {dtype} {shape} tensor on {dev}")
+    spec = (("codes", (k, n), torch.int32), ("scales", (n, groups), torch.float32), ("zeros", (n, groups), torch.float32),
+            ("wq", (n, k), weight.dtype))
+    out = _outputs(spec, out, want, dev, optional=[name for name, _, _ in spec])
     s_ptr, c_ptr = _awq_f32(col_scale, "col_scale", (k,), dev), _awq_f32(clip, "clip", (n, groups), dev)
     with torch.cuda.device(dev):
-        rc = lib.qllm_awq_quantize(weight.data_ptr(), _W_DTYPES[weight.dtype], s_ptr, c_ptr, n, k, int(bits), g,
-                                   *(t.data_ptr() if t is not None else None for t in out), _stream_ptr())
+        rc = lib.qllm_awq_quantize(weight.data_ptr(), code, s_ptr, c_ptr, n, k, int(bits), g, *(_ptr(t) for t in out), _stream_ptr())
     _lib.check(rc)
-    return tuple(out)
+    return out
 
 
 def awq_clip_search(weight: torch.Tensor, gram: torch.Tensor, bits: int, group_size: int = 128, n_grid: int = 20, max_shrink: float = 0.5,
@@ -487,27 +477,23 @@ def awq_clip_search(weight: torch.Tensor, gram: torch.Tensor, bits: int, group_s
     org * (1 - i / n_grid), i < int(max_shrink * n_grid), whose pseudo-quantized weights change the group's output least ->
     (best_max f32 [N, K/g], best_idx i32 [N, K/g], err f32 [N, K/g, 2]: unclipped and chosen).  `out`: that tuple preallocated;
     `workspace`: a uint8 tensor of at least qllm_awq_clip_search_workspace_bytes."""
-    n, k, g, groups = _awq_layer(weight, group_size)
+    n, k, code = _check_weight(weight)
+    g = int(group_size)
+    groups = max(k // max(g, 1), 1)
     lib = _lib.load()
     dev = weight.device
     g_ptr = _awq_f32(gram, "gram", (groups, g, g), dev)
     if g_ptr is None:
         raise RuntimeError("gram must not be None")
-    shapes = (("best_max", (n, groups), torch.float32), ("best_idx", (n, groups), torch.int32), ("err", (n, groups, 2), torch.float32))
-    if out is None:
-        out = tuple(torch.empty(shape, dtype=dtype, device=dev) for _, shape, dtype in shapes)
-    for (name, shape, dtype), t in zip(shapes, out):
-        _check_input(t, name)
-        if tuple(t.shape) != shape or t.dtype != dtype or t.device != dev:
-            raise RuntimeError(f"{name} must be a contiguous {dtype} {shape} tensor on {dev}")
+    spec = (("best_max", (n, groups), torch.float32), ("best_idx", (n, groups), torch.int32), ("err", (n, groups, 2), torch.float32))
+    out = _outputs(spec, out, [name for name, _, _ in spec], dev)
     need = lib.qllm_awq_clip_search_workspace_bytes(n, k, g)
     ws = workspace if workspace is not None else (torch.empty(need, dtype=torch.uint8, device=dev) if need else None)
     with torch.cuda.device(dev):
-        rc = lib.qllm_awq_clip_search(weight.data_ptr(), _W_DTYPES[weight.dtype], g_ptr, n, k, int(bits), g, int(n_grid), float(max_shrink),
-                                      out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), ws.data_ptr() if ws is not None else None,
-                                      ws.numel() if ws is not None else 0, _stream_ptr())
+        rc = lib.qllm_awq_clip_search(weight.data_ptr(), code, g_ptr, n, k, int(bits), g, int(n_grid), float(max_shrink),
+                                      *(t.data_ptr() for t in out), _ptr(ws), ws.numel() if ws is not None else 0, _stream_ptr())
     _lib.check(rc)
-    return tuple(out)
+    return out
 
 
 def repack_native(w: QllmWeight, keep):
@@ -556,4 +542,5 @@ def unpack_native(w: QllmWeight, keep, layout: str):
 
 
 __all__ = ["make_weight", "linear_forward", "linear_forward_grouped", "dequant", "gather_columns", "unpack_qweight", "pack_qweight",
-           "workspace", "QllmUnsupported", "LAYOUTS", "plan_describe", "repack_native", "unpack_native", "hqq_quantize"]
+           "workspace", "QllmUnsupported", "LAYOUTS", "plan_describe", "repack_native", "unpack_native", "hqq_quantize", "gptq_quantize",
+           "awq_quantize", "awq_clip_search"]

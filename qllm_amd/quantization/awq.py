@@ -19,8 +19,7 @@ from typing import Dict, List, Optional
 import torch
 
 from .. import ops
-from .gptq import _Catcher, _Stop, _first
-from .hqq import _decoder_blocks
+from ._common import capture_first_block_inputs, decoder_blocks, first, layer_dtype, need_device
 
 N_GRID = 20               # ratios of the scale search and the grid of the clip search (_awq_quantizer.py:320, :184)
 MAX_SHRINK = 0.5
@@ -42,16 +41,11 @@ def gram_matrices(x: torch.Tensor, g: int, n_sample_token: int = N_SAMPLE_TOKEN)
     return (torch.einsum("tjg,tjh->jgh", xs, xs) / xs.shape[0]).contiguous()
 
 
-def _need_device(t: torch.Tensor, what: str):
-    if not t.is_cuda:
-        raise RuntimeError(f"{what} needs the weight on an MI355X: qllm_amd ships no CPU quantizer")
-
-
 def clip_linear(linear: torch.nn.Linear, x: torch.Tensor, bits: int, g: int, n_sample_token: int = N_SAMPLE_TOKEN):
     """auto_clip_layer for one linear and its input x [.., K]: (best_max f32 [N, K/g], best_idx i32 [N, K/g], err f32 [N, K/g, 2]:
     the unclipped and the chosen output error of every (row, group)).  The weight is left as it is."""
     w = linear.weight.data
-    _need_device(w, "clip_linear")
+    need_device(w, "clip_linear")
     return ops.awq_clip_search(w.contiguous(), gram_matrices(x.to(w.device), g, n_sample_token), bits, g, N_GRID, MAX_SHRINK)
 
 
@@ -86,8 +80,8 @@ def fold_scales(block, prev_op, layers, s: torch.Tensor):
 def _run(module, x: torch.Tensor, kwargs):
     """module over x [batch, tokens, K] one calibration row at a time (the captured keyword arguments are those of one row)."""
     if x.dim() < 3:
-        return _first(module(x, **kwargs))
-    return torch.cat([_first(module(x[b:b + 1], **kwargs)) for b in range(x.shape[0])], dim=0)
+        return first(module(x, **kwargs))
+    return torch.cat([first(module(x[b:b + 1], **kwargs)) for b in range(x.shape[0])], dim=0)
 
 
 def search_scales(module2inspect, linears, x: torch.Tensor, kwargs: Optional[dict], bits: int, g: int):
@@ -101,7 +95,7 @@ def search_scales(module2inspect, linears, x: torch.Tensor, kwargs: Optional[dic
     kwargs = dict(kwargs or {})
     kwargs.pop("use_cache", None)
     orig = [fc.weight.data for fc in linears]
-    _need_device(orig[0], "search_scales")
+    need_device(orig[0], "search_scales")
     dev = orig[0].device
     x = x.to(dev)
     weight = torch.cat([w.float() for w in orig], dim=0)
@@ -169,7 +163,7 @@ def quantize_block(block, inps: List[torch.Tensor], args, kwargs, bits: int = 4,
         raise NotImplementedError(f"group_size must be 32, 64 or 128 (got {group_size}); -1 is not built")
     linears = modelutils.find_layers(block, [torch.nn.Linear])
     for lin in linears.values():
-        _need_device(lin.weight.data, "quantize_block")
+        need_device(lin.weight.data, "quantize_block")
     report = {f"{prefix}{name}": {"ratio": None, "history": None, "clip_err": None} for name in linears}
     kwargs = {k: v for k, v in kwargs.items() if k != "use_cache"}
     with torch.no_grad():
@@ -202,7 +196,7 @@ def quantize_block(block, inps: List[torch.Tensor], args, kwargs, bits: int = 4,
                 report[f"{prefix}{name}"]["clip_err"] = err.sum(dim=(0, 1))
             codes, scales, zeros, _ = ops.awq_quantize(w, bits, group_size, clip=clip, want=("codes", "scales", "zeros"))
             n, k = w.shape
-            dtype = w.dtype if w.dtype in (torch.float16, torch.bfloat16) else torch.float16
+            dtype = layer_dtype(w)
             layer = WQLinear_GEMM(bits, group_size, k, n, lin.bias is not None, dtype=dtype)
             layer.pack_on_device(codes, zeros.t().contiguous().to(torch.int32))
             layer.scales = scales.t().contiguous().to(dtype)
@@ -214,7 +208,7 @@ def quantize_block(block, inps: List[torch.Tensor], args, kwargs, bits: int = 4,
         for r in report.values():
             if r["clip_err"] is not None:
                 r["clip_err"] = [float(v) for v in r["clip_err"].cpu()]
-        outs = [_first(block(x, *args, **kwargs)) for x in inps]
+        outs = [first(block(x, *args, **kwargs)) for x in inps]
     return outs, report
 
 
@@ -229,10 +223,9 @@ def quantize_model(model, calibration_input_ids, bits: int = 4, group_size: int 
     from ..modeling import base
     from ..modeling.q_layers import WQLinear_GEMM, install_sibling_groups
     dev = torch.device(device)
-    prefix, blocks = _decoder_blocks(model)
+    prefix, blocks = decoder_blocks(model)
     for p in model.parameters():
-        if not p.is_cuda:
-            raise RuntimeError("quantize_model needs the weight on an MI355X: qllm_amd ships no CPU quantizer")
+        need_device(p, "quantize_model")
     if bits != 4:
         raise NotImplementedError("WQLinear_GEMM packs 4-bit layers only")
     cfg = base.QuantConfig(bits=bits, group_size=group_size, version="GEMM", quant_method="awq")
@@ -241,23 +234,7 @@ def quantize_model(model, calibration_input_ids, bits: int = 4, group_size: int 
         ids = ids.unsqueeze(0)
     report = {}
     with torch.no_grad():
-        saved = [blocks[i] for i in range(len(blocks))]
-        catcher = _Catcher()
-        del blocks[:]
-        blocks.append(catcher)
-        try:
-            model.to(dev)
-            for j in range(ids.shape[0]):
-                try:
-                    model(ids[j:j + 1].to(dev), use_cache=False)
-                except _Stop:
-                    pass
-        finally:
-            del blocks[:]
-            blocks.extend(saved)
-        inps, args, kwargs = catcher.inputs, catcher.args, catcher.kwargs
-        if len(inps) != ids.shape[0]:
-            raise RuntimeError("the decoder blocks were not reached by the model's forward")
+        inps, args, kwargs = capture_first_block_inputs(model, blocks, ids, dev)
         for i in range(len(blocks)):
             block = blocks[i].to(dev)
             inps, rep = quantize_block(block, inps, args, kwargs, bits, group_size, auto_scale, auto_clip, prefix=f"{prefix}.{i}.")

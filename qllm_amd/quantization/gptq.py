@@ -16,7 +16,8 @@ from typing import Dict, Optional
 import torch
 
 from .. import ops
-from .hqq import _decoder_blocks
+from ._common import bits_for, capture_first_block_inputs, decoder_blocks, first, layer_dtype, need_device
+
 
 def accumulate_hessian(H: Optional[torch.Tensor], nsamples: int, x: torch.Tensor):
     """GPTQ.add_batch (gptq.py:75-102): the running mean H = 2/n sum X^T X over calibration batches, in H's dtype (fp32 when H is None).
@@ -68,8 +69,7 @@ def _pack(codes_kn: torch.Tensor, zeros_gn: torch.Tensor, bits: int, group_size:
 def _solve(weight, H, bits, g, act_order, sym, damp_percent, debug):
     """gptq_quantize_weight before packing: (codes i32 [K, N], scale / zero f32 [N, K/g], wq [N, K], all in the original column order,
     g_idx i32 [K], the summed loss, the debug extras or None)."""
-    if not weight.is_cuda:
-        raise RuntimeError("gptq_quantize_weight needs the weight on an MI355X: qllm_amd ships no CPU quantizer")
+    need_device(weight, "gptq_quantize_weight")
     if weight.dim() != 2:
         raise RuntimeError(f"weight must be [out_features, in_features], got {tuple(weight.shape)}")
     n, k = weight.shape
@@ -126,7 +126,7 @@ def gptq_quantize_weight(weight: torch.Tensor, H: Optional[torch.Tensor], bits: 
     only with debug).  pack=False leaves qweight / qzeros None (layers QuantLinearGPTQ cannot hold)."""
     g = weight.shape[-1] if group_size == -1 else int(group_size)
     codes, scale, zero, _, g_idx, loss, extras = _solve(weight, H, bits, g, act_order, sym, damp_percent, debug)
-    sdtype = weight.dtype if weight.dtype in (torch.float16, torch.bfloat16) else torch.float16
+    sdtype = layer_dtype(weight)
     qweight, qzeros = _pack(codes, zero.t().contiguous(), bits, g) if pack else (None, None)
     ret = (qweight, qzeros, scale.t().contiguous().to(sdtype), g_idx, loss)
     return ret + (extras,) if debug else ret
@@ -143,7 +143,7 @@ def quantize_linear(linear: torch.nn.Linear, H: Optional[torch.Tensor], bits: in
     n, k = w.shape
     g = k if group_size == -1 else int(group_size)
     codes, scale, zero, wq, g_idx, loss, extras = _solve(w.to(dev), H, bits, g, act_order, sym, damp_percent, debug)
-    dtype = w.dtype if w.dtype in (torch.float16, torch.bfloat16) else torch.float16
+    dtype = layer_dtype(w)
     layer = QuantLinearGPTQ(bits, g, k, n, linear.bias is not None, dtype=dtype)
     layer.qweight, layer.qzeros = _pack(codes, zero.t().contiguous(), bits, g, layer)
     layer.scales, layer.g_idx = scale.t().contiguous().to(dtype), g_idx
@@ -155,27 +155,6 @@ def quantize_linear(linear: torch.nn.Linear, H: Optional[torch.Tensor], bits: in
         layer.gptq_rtn_loss, layer.gptq_loss_hd = float(extras["rtn_loss"]), float(extras["loss_hd"])
     linear.weight.data = wq.to(device=w.device, dtype=w.dtype)
     return layer
-
-
-class _Stop(Exception):
-    pass
-
-
-class _Catcher(torch.nn.Module):
-    """Stands in for the first decoder block: records what the model hands it, then ends the forward."""
-
-    def __init__(self):
-        super().__init__()
-        self.inputs, self.args, self.kwargs = [], (), {}
-
-    def forward(self, hidden, *args, **kwargs):
-        self.inputs.append(hidden)
-        self.args, self.kwargs = args, kwargs
-        raise _Stop()
-
-
-def _first(out):
-    return out[0] if isinstance(out, (tuple, list)) else out
 
 
 def quantize_model(model, calibration_input_ids, bits: int, group_size: int = 128, act_order: bool = False, sym: bool = False,
@@ -193,31 +172,14 @@ def quantize_model(model, calibration_input_ids, bits: int, group_size: int = 12
     from ..utils import modelutils
     dev = torch.device(device)
     bits_by_layer = dict(bits_by_layer or {})
-    prefix, blocks = _decoder_blocks(model)
+    prefix, blocks = decoder_blocks(model)
     cfg = base.QuantConfig(bits=bits, group_size=group_size, version="GPTQ", quant_method="gptq", desc_act=bool(act_order), sym=bool(sym))
     ids = torch.as_tensor(calibration_input_ids)
     if ids.dim() == 1:
         ids = ids.unsqueeze(0)
     losses, rtn_losses, losses_hd = {}, {}, {}
     with torch.no_grad():
-        # the first block's inputs: everything but the blocks goes to the device, a catcher stands where block 0 was
-        saved = [blocks[i] for i in range(len(blocks))]
-        catcher = _Catcher()
-        del blocks[:]
-        blocks.append(catcher)
-        try:
-            model.to(dev)
-            for j in range(ids.shape[0]):
-                try:
-                    model(ids[j:j + 1].to(dev), use_cache=False)
-                except _Stop:
-                    pass
-        finally:
-            del blocks[:]
-            blocks.extend(saved)
-        inps, args, kwargs = catcher.inputs, catcher.args, catcher.kwargs
-        if len(inps) != ids.shape[0]:
-            raise RuntimeError("the decoder blocks were not reached by the model's forward")
+        inps, args, kwargs = capture_first_block_inputs(model, blocks, ids, dev)
         for i in range(len(blocks)):
             block = blocks[i].to(dev)
             linears = modelutils.find_layers(block, [torch.nn.Linear])
@@ -236,7 +198,7 @@ def quantize_model(model, calibration_input_ids, bits: int, group_size: int = 12
                     h.remove()
             for name, lin in linears.items():
                 full = f"{prefix}.{i}.{name}"
-                b = bits_by_layer.get(full, bits_by_layer.get(name.rsplit(".", 1)[-1], bits))
+                b = bits_for(bits_by_layer, full, name, bits)
                 layer = quantize_linear(lin, stats[name][0], b, group_size, act_order, sym, damp_percent, device=dev, debug=debug)
                 lin.weight.data = torch.empty(0, dtype=lin.weight.dtype, device=lin.weight.device)   # the block runs on the q_layer
                 modelutils.set_op_by_name(block, name, layer)
@@ -245,7 +207,7 @@ def quantize_model(model, calibration_input_ids, bits: int, group_size: int = 12
                 if debug:
                     rtn_losses[full], losses_hd[full] = layer.gptq_rtn_loss, layer.gptq_loss_hd
                 stats[name][0] = None
-            inps = [_first(block(x, *args, **kwargs)) for x in inps]
+            inps = [first(block(x, *args, **kwargs)) for x in inps]
     model.to(dev)
     model.sibling_groups = install_sibling_groups(model, [QuantLinearGPTQ])
     model.quant_config = cfg

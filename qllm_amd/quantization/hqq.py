@@ -11,6 +11,7 @@ from typing import Dict, Optional
 import torch
 
 from .. import ops
+from ._common import bits_for, decoder_blocks, layer_dtype, need_device
 
 HQQ_DEFAULTS = dict(iters=20, lp_norm=0.7, beta=10.0, kappa=1.01)   # _hqq_quantizer.py:30
 
@@ -21,8 +22,7 @@ def hqq_quantize_weight(weight: torch.Tensor, bits: int, group_size: int = 64, *
     unknown = set(opt) - set(HQQ_DEFAULTS)
     if unknown:
         raise TypeError(f"unknown solver options {sorted(unknown)}; known: {sorted(HQQ_DEFAULTS)}")
-    if not weight.is_cuda:
-        raise RuntimeError("hqq_quantize_weight needs the weight on an MI355X: qllm_amd ships no CPU quantizer")
+    need_device(weight, "hqq_quantize_weight")
     return ops.hqq_quantize(weight.contiguous(), bits, group_size, **{**HQQ_DEFAULTS, **opt})[:3]
 
 
@@ -35,7 +35,7 @@ def quantize_linear(linear: torch.nn.Linear, bits: int, group_size: int = 64, de
     n, k = w.shape
     g = k if group_size == -1 else group_size
     qweight, scales, zeros = hqq_quantize_weight(w.to(dev), bits, g, **opt)
-    dtype = w.dtype if w.dtype in (torch.float16, torch.bfloat16) else torch.float16
+    dtype = layer_dtype(w)
     layer = QuantLinearHQQ(bits, g, k, n, linear.bias is not None, dtype=dtype)
     layer.qweight, layer.scales, layer.qzeros = qweight, scales.to(dtype), zeros.to(dtype)
     if linear.bias is not None:
@@ -43,17 +43,6 @@ def quantize_linear(linear: torch.nn.Linear, bits: int, group_size: int = 64, de
     linear.weight.data = torch.empty(0, dtype=w.dtype, device=w.device)
     del w
     return layer
-
-
-def _decoder_blocks(model):
-    """(prefix, ModuleList) of the decoder blocks: the longest nn.ModuleList of the model (model.layers, transformer.h, ...)."""
-    best = None
-    for name, m in model.named_modules():
-        if isinstance(m, torch.nn.ModuleList) and (best is None or len(m) > len(best[1])):
-            best = (name, m)
-    if best is None:
-        raise ValueError("no nn.ModuleList of decoder blocks found in the model")
-    return best
 
 
 def quantize_model(model, bits: int, group_size: int = 64, bits_by_layer: Optional[Dict[str, int]] = None, device="cuda:0", **opt):
@@ -67,14 +56,14 @@ def quantize_model(model, bits: int, group_size: int = 64, bits_by_layer: Option
     from ..utils import modelutils
     dev = torch.device(device)
     bits_by_layer = dict(bits_by_layer or {})
-    prefix, blocks = _decoder_blocks(model)
+    prefix, blocks = decoder_blocks(model)
     cfg = base.QuantConfig(bits=bits, group_size=group_size, version="HQQ", quant_method="hqq")
     with torch.no_grad():
         for i in range(len(blocks)):
             block = blocks[i].to(dev)
             for name in list(modelutils.find_layers(block, [torch.nn.Linear])):
                 full = f"{prefix}.{i}.{name}"
-                b = bits_by_layer.get(full, bits_by_layer.get(name.rsplit(".", 1)[-1], bits))
+                b = bits_for(bits_by_layer, full, name, bits)
                 layer = quantize_linear(modelutils.get_op_by_name(block, name), b, group_size, device=dev, **opt)
                 modelutils.set_op_by_name(block, name, layer)
                 cfg.by_layer[full] = {"wbits": b, "groupsize": layer.groupsize}

@@ -2,33 +2,16 @@
 the code-object metadata only).  The design: 16 lanes own a row and hold g/16 columns of the current group; the clip search keeps the
 candidates' quantization errors and their travelling copy in registers (nothing in private memory) and shares exactly one g x g fp32
 Gram tile per block -- 64 KB at g = 128, two thread blocks per CU within the 160 KB of LDS and, at two waves per SIMD, 256 registers."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "qllm_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from kernel_resources import resources
 
 
 @pytest.fixture(scope="module")
-def kernels(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    out = str(tmp_path_factory.mktemp("awq_res") / "awq_quant.s")
-    subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-S", "--cuda-device-only",
-                    os.path.join(CSRC, "awq_quant.hip"), "-o", out], check=True, capture_output=True)
-    meta = open(out).read().split("amdhsa.kernels:")[1]
-    res = {}
-    for block in meta.split("\n  - ")[1:]:
-        f = {k: re.search(r"\.%s:\s+(\S+)" % k, block) for k in
-             ("name", "vgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size", "group_segment_fixed_size")}
-        if all(f.values()):
-            res[f["name"].group(1)] = {k: int(m.group(1)) for k, m in f.items() if k != "name"}
-    return res
+def kernels():
+    return resources("awq_quant.hip")
 
 
 def _by_group(kernels, which):

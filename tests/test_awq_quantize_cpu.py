@@ -80,16 +80,16 @@ def _block_and_input():
     """Block 0 of a small fp32 Llama with what the model hands it."""
     import torch
     import transformers
-    from qllm_amd.quantization.gptq import _Catcher, _Stop
+    from qllm_amd.quantization._common import Catcher, Stop
     cfg = transformers.LlamaConfig(hidden_size=64, intermediate_size=128, num_hidden_layers=1, num_attention_heads=4, num_key_value_heads=4,
                                    vocab_size=64, max_position_embeddings=32, tie_word_embeddings=False)
     torch.manual_seed(0)
     model = transformers.LlamaForCausalLM(cfg).float().eval()
-    block, catcher = model.model.layers[0], _Catcher()
+    block, catcher = model.model.layers[0], Catcher()
     model.model.layers[0] = catcher
     try:
         model(torch.randint(0, 64, (2, 12), generator=torch.Generator().manual_seed(1)), use_cache=False)
-    except _Stop:
+    except Stop:
         pass
     return block, catcher.inputs[0], catcher.args, catcher.kwargs
 

@@ -3,33 +3,14 @@ the code-object metadata only).  The kernel's design: a row tile's 8 columns per
 in registers through the walk of a 128-column block (nothing in private memory), and the block shares exactly one 128 x 128 fp32 tile of
 U (64 KB) plus one 16 x (128 + 4) fp32 tile (8.25 KB: the error history of an earlier block, rows padded against bank conflicts, then
 the codes on their way out) -- two thread blocks per CU within the 160 KB of LDS."""
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "qllm_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from kernel_resources import resources
 
 
 @pytest.fixture(scope="module")
-def kernels(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    out = str(tmp_path_factory.mktemp("gptq_res") / "gptq_quant.s")
-    subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-S", "--cuda-device-only",
-                    os.path.join(CSRC, "gptq_quant.hip"), "-o", out], check=True, capture_output=True)
-    meta = open(out).read().split("amdhsa.kernels:")[1]
-    res = {}
-    for block in meta.split("\n  - ")[1:]:
-        f = {k: re.search(r"\.%s:\s+(\S+)" % k, block) for k in
-             ("name", "vgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size", "group_segment_fixed_size")}
-        if all(f.values()):
-            res[f["name"].group(1)] = {k: int(m.group(1)) for k, m in f.items() if k != "name"}
-    return res
+def kernels():
+    return resources("gptq_quant.hip")
 
 
 def test_one_kernel_per_weight_dtype_without_scratch(kernels):

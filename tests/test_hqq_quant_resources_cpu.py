@@ -2,39 +2,21 @@
 the code-object metadata).  A group lives in registers through every solver round: the per-lane element array must never end up in
 private (scratch) memory -- a dynamically indexed register array, or a `break` inside an unrolled loop, would put it there -- and a
 256-thread block must stay within the register file."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "qllm_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from kernel_resources import asm_text, parse
 
 
 @pytest.fixture(scope="module")
-def asm(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    out = str(tmp_path_factory.mktemp("hqq_res") / "hqq_quant.s")
-    subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-S", "--cuda-device-only",
-                    os.path.join(CSRC, "hqq_quant.hip"), "-o", out], check=True, capture_output=True)
-    return open(out).read()
+def asm():
+    return asm_text("hqq_quant.hip")
 
 
 def _kernels(text):
-    res = {}
-    for block in text.split("\n  - ")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", block)
-        vg = re.search(r"\.vgpr_count:\s+(\d+)", block)
-        sp = re.search(r"\.vgpr_spill_count:\s+(\d+)", block)
-        pr = re.search(r"\.private_segment_fixed_size:\s+(\d+)", block)
-        lds = re.search(r"\.group_segment_fixed_size:\s+(\d+)", block)
-        if name and vg and sp and pr and lds:
-            res[name.group(1)] = tuple(int(m.group(1)) for m in (vg, sp, pr, lds))
-    return res
+    return {n: (r["vgpr_count"], r["vgpr_spill_count"], r["private_segment_fixed_size"], r["group_segment_fixed_size"])
+            for n, r in parse(text).items()}
 
 
 def test_every_instantiation_is_built_and_uses_no_scratch(asm):

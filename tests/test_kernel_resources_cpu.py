@@ -4,46 +4,13 @@ cross-compiles gfx950 to assembly and the resource usage is read from the code-o
 Why: the decode kernels sit next to occupancy cliffs -- the 8-wave 64-column strip variant shares a CU between two
 blocks only up to 128 VGPRs (130 cost 8 % on gate/up this round), 16-wave blocks cannot exceed 128 at all (anything more
 spills), and a spilled register inside the prefill k-loop is a scratch load that also counts against vmcnt."""
-import atexit
-import os
 import re
-import shutil
-import subprocess
-import tempfile
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "qllm_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-
-
-_ASM = {}   # source file -> its gfx950 assembly, compiled once per session into a private directory removed at exit
-
-
-def _asm(src):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    if src not in _ASM:
-        if "dir" not in _ASM:
-            _ASM["dir"] = tempfile.mkdtemp(prefix="qllm_res_")
-            atexit.register(shutil.rmtree, _ASM["dir"], True)
-        out = os.path.join(_ASM["dir"], src + ".s")
-        subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-S",
-                        "--cuda-device-only", os.path.join(CSRC, src), "-o", out], check=True, capture_output=True)
-        _ASM[src] = out
-    return _ASM[src]
+from kernel_resources import asm_text, resources
 
 
 def _resources(src):
-    res = {}
-    for block in open(_asm(src)).read().split("\n  - ")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", block)
-        vg = re.search(r"\.vgpr_count:\s+(\d+)", block)
-        sp = re.search(r"\.vgpr_spill_count:\s+(\d+)", block)
-        if name and vg and sp:
-            res[name.group(1)] = (int(vg.group(1)), int(sp.group(1)))
-    return res
+    return {n: (r["vgpr_count"], r["vgpr_spill_count"]) for n, r in resources(src).items()}
 
 
 def _strip(nw, cpl, maxs, spg, xl, bits=4, ra=False, bf=False, mt=1, sm=False, dbg=False, oner=False):
@@ -156,6 +123,6 @@ def test_bit_stream_matvec_never_spills():
         assert spill == 0 and vgpr <= 256, (n, vgpr, spill)
     # ... and no register array may end up in scratch memory (a `break` inside an unrolled loop, or stores under per-kind branches,
     # turned the per-unit scale / zero-point arrays into private memory in the first versions: round 6)
-    text = open(_asm("bitgemv.hip")).read()
+    text = asm_text("bitgemv.hip")
     assert "scratch_load" not in text and "scratch_store" not in text
     assert all(int(v) == 0 for v in re.findall(r"\.private_segment_fixed_size:\s+(\d+)", text))

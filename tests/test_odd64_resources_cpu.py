@@ -1,37 +1,15 @@
 """Build-time guard (no GPU) on the instantiations the Falcon-shaped routes reach: gemm3 with its half-wide last tile (the same k-loop for
 every wave; the dead half leaves before the epilogue) and the batch-1 kernel's 64-wide-group forms at K % 128 == 64 (T = 142: 8 waves x 24; T = 34:
 4 x 16, both non-EXACT) -- no spills, and the register counts that keep their occupancy."""
-import functools
-import os
 import re
-import shutil
-import subprocess
-import tempfile
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "qllm_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from kernel_resources import resources
 
 
-@functools.lru_cache(maxsize=None)
 def _resources(src):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    with tempfile.TemporaryDirectory(prefix="qllm_odd64_") as d:
-        out = os.path.join(d, src + ".s")
-        subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-S", "--cuda-device-only",
-                        os.path.join(CSRC, src), "-o", out], check=True, capture_output=True)
-        text = open(out).read()
-    res = {}
-    for block in text.split("\n  - ")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", block)
-        vg = re.search(r"\.vgpr_count:\s+(\d+)", block)
-        sp = re.search(r"\.vgpr_spill_count:\s+(\d+)", block)
-        if name and vg and sp:
-            res[name.group(1)] = (int(vg.group(1)), int(sp.group(1)))
-    return res
+    return {n: (r["vgpr_count"], r["vgpr_spill_count"]) for n, r in resources(src).items()}
 
 
 def test_gemm3_with_the_tail_tile_keeps_three_waves_per_simd():
