@@ -309,11 +309,29 @@ int qllm_hqq_quantize(const void *w_nk, int32_t w_dtype, int32_t N, int32_t K, i
  * QLLM_ERR_INVALID; all of it before any device work.  Every buffer aligned to its element size.  Workspace:
  * qllm_gptq_quantize_workspace_bytes() (pure: N x K floats, the error history each row tile keeps for its own rows), 16-byte aligned,
  * needs no initialisation.  No host synchronisation, no atomics, bit-reproducible, hipGraph-capturable.
- * Not served (the reference's other switches): static_groups, mse, trits, Conv layers. */
+ * Not served (the reference's other switches): mse, trits, Conv layers; static_groups is qllm_gptq_quantize_static below. */
 size_t qllm_gptq_quantize_workspace_bytes(int32_t N, int32_t K);
 int qllm_gptq_quantize(const void *w_nk, int32_t w_dtype, const float *u_kk, int32_t N, int32_t K, int32_t bits, int32_t group_size,
                        int32_t sym, int32_t *codes_kn, float *scales_ng, float *zeros_ng, void *wq_nk, float *loss_n, void *workspace,
                        size_t workspace_bytes, void *stream);
+
+/* The same solver with static_groups = True (gptq.py:157-165, 207-211, 230-233; csrc/gptq_static.hip): every group's scale / zero is
+ * found from the weights as given, before the walk, and the walk only looks them up.  The columns are still processed in the caller's
+ * order, so a layer quantized with act-order keeps the trivial g_idx[i] = i / group_size and decodes like a plain one.
+ * w_nk [N,K] is in the ORIGINAL column order (dead columns zeroed); perm_k (nullable: identity) i32 [K] maps processing position j to
+ * the original column perm_k[j] and must be a permutation of 0..K-1 (not checked here: entries are clamped to 0..K-1, so a bad one
+ * gives a wrong result and no access outside the buffers); u_kk (nullable) is in PROCESSING order, as for qllm_gptq_quantize.
+ * Parameters of group c of a row: find_params (above) over columns c*group_size .. c*group_size+group_size-1 of w_nk.  Column j of the
+ * walk loads w_nk[n][perm_k[j]], uses the parameters of group perm_k[j] / group_size, and its quantization, error, in-block and
+ * trailing updates and loss are qllm_gptq_quantize's, rounding for rounding.
+ * Outputs as for qllm_gptq_quantize, but codes_kn and wq_nk are already in the ORIGINAL column order (codes_kn[perm_k[j]][n]) and
+ * scales_ng / zeros_ng in the original group numbering: nothing is left to un-permute.  u_kk == NULL: round-to-nearest; perm_k is then
+ * not consulted and every output equals qllm_gptq_quantize's with u_kk == NULL.  group_size == K: the result of qllm_gptq_quantize on
+ * w_nk[:, perm_k] in the original order.  Validation, the served shapes and the workspace (qllm_gptq_quantize_workspace_bytes) are
+ * qllm_gptq_quantize's; perm_k 4-byte aligned.  No host synchronisation, no atomics, bit-reproducible, hipGraph-capturable. */
+int qllm_gptq_quantize_static(const void *w_nk, int32_t w_dtype, const float *u_kk, const int32_t *perm_k, int32_t N, int32_t K, int32_t bits,
+                              int32_t group_size, int32_t sym, int32_t *codes_kn, float *scales_ng, float *zeros_ng, void *wq_nk,
+                              float *loss_n, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- AWQ quantizer (additive to ABI 7) ----------------------------------------------------------------------------------------------- */
 /* The two device steps of the AWQ search (qllm/quantization/awq/_awq_quantizer.py) with zero_point = True, in fp32 (csrc/awq_quant.hip).

@@ -27,6 +27,7 @@ EXPORTS = (
     "qllm_allreduce_oneshot", "qllm_linear_forward_allreduce", "qllm_convert_bf16_to_f16",
     "qllm_set_knob", "qllm_get_knob", "qllm_reset_knobs",
     "qllm_hqq_quantize_workspace_bytes", "qllm_hqq_quantize", "qllm_gptq_quantize_workspace_bytes", "qllm_gptq_quantize",
+    "qllm_gptq_quantize_static",
     "qllm_awq_clip_search_workspace_bytes", "qllm_awq_clip_search", "qllm_awq_quantize",
 )
 
@@ -139,6 +140,8 @@ def _declare(lib):
     lib.qllm_gptq_quantize_workspace_bytes.argtypes = [i32, i32]
     lib.qllm_gptq_quantize.restype = C.c_int
     lib.qllm_gptq_quantize.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.qllm_gptq_quantize_static.restype = C.c_int
+    lib.qllm_gptq_quantize_static.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.qllm_awq_clip_search_workspace_bytes.restype = sz
     lib.qllm_awq_clip_search_workspace_bytes.argtypes = [i32, i32, i32]
     lib.qllm_awq_clip_search.restype = C.c_int

@@ -456,10 +456,10 @@ int qllm_hqq_quantize(const void *w_nk, int32_t w_dtype, int32_t N, int32_t K, i
 
 size_t qllm_gptq_quantize_workspace_bytes(int32_t N, int32_t K) { return gptq_quant_workspace_bytes(N, K); }
 
-int qllm_gptq_quantize(const void *w_nk, int32_t w_dtype, const float *u_kk, int32_t N, int32_t K, int32_t bits, int32_t group_size, int32_t sym,
-                       int32_t *codes_kn, float *scales_ng, float *zeros_ng, void *wq_nk, float *loss_n, void *workspace, size_t workspace_bytes,
-                       void *stream) {
-  clear_error();
+// what the two GPTQ entry points check alike, in this order, all of it before any device work
+static int gptq_check(const char *fn, const void *w_nk, int32_t w_dtype, const float *u_kk, int32_t N, int32_t K, int32_t bits, int32_t group_size,
+                      int32_t sym, const int32_t *codes_kn, const float *scales_ng, const float *zeros_ng, const void *wq_nk, const float *loss_n,
+                      const void *workspace, size_t workspace_bytes) {
   if (int rc = check_quant_layer("w_nk / codes_kn / scales_ng / zeros_ng", !w_nk || !codes_kn || !scales_ng || !zeros_ng, w_dtype, N, K, group_size))
     return rc;
   if (sym < 0 || sym > 1) return set_error(QLLM_ERR_INVALID, "sym must be 0 or 1 (got %d)", sym);
@@ -473,9 +473,30 @@ int qllm_gptq_quantize(const void *w_nk, int32_t w_dtype, const float *u_kk, int
   if ((uintptr_t)w_nk % esz || (uintptr_t)wq_nk % esz || (uintptr_t)codes_kn % 4 || (uintptr_t)scales_ng % 4 ||
       (uintptr_t)zeros_ng % 4 || (uintptr_t)loss_n % 4)
     return set_error(QLLM_ERR_INVALID, "%s", kElemAligned);
-  if (int rc = check_workspace("qllm_gptq_quantize", workspace, workspace_bytes, gptq_quant_workspace_bytes(N, K))) return rc;
+  return check_workspace(fn, workspace, workspace_bytes, gptq_quant_workspace_bytes(N, K));
+}
+
+int qllm_gptq_quantize(const void *w_nk, int32_t w_dtype, const float *u_kk, int32_t N, int32_t K, int32_t bits, int32_t group_size, int32_t sym,
+                       int32_t *codes_kn, float *scales_ng, float *zeros_ng, void *wq_nk, float *loss_n, void *workspace, size_t workspace_bytes,
+                       void *stream) {
+  clear_error();
+  if (int rc = gptq_check("qllm_gptq_quantize", w_nk, w_dtype, u_kk, N, K, bits, group_size, sym, codes_kn, scales_ng, zeros_ng, wq_nk, loss_n,
+                          workspace, workspace_bytes))
+    return rc;
   return launch_gptq_quantize(w_nk, w_dtype, u_kk, N, K, bits, group_size, sym, codes_kn, scales_ng, zeros_ng, wq_nk, loss_n, workspace,
                               (hipStream_t)stream);
+}
+
+int qllm_gptq_quantize_static(const void *w_nk, int32_t w_dtype, const float *u_kk, const int32_t *perm_k, int32_t N, int32_t K, int32_t bits,
+                              int32_t group_size, int32_t sym, int32_t *codes_kn, float *scales_ng, float *zeros_ng, void *wq_nk, float *loss_n,
+                              void *workspace, size_t workspace_bytes, void *stream) {
+  clear_error();
+  if ((uintptr_t)perm_k % 4) return set_error(QLLM_ERR_INVALID, "perm_k must be 4-byte aligned");
+  if (int rc = gptq_check("qllm_gptq_quantize_static", w_nk, w_dtype, u_kk, N, K, bits, group_size, sym, codes_kn, scales_ng, zeros_ng, wq_nk,
+                          loss_n, workspace, workspace_bytes))
+    return rc;
+  return launch_gptq_quantize_static(w_nk, w_dtype, u_kk, perm_k, N, K, bits, group_size, sym, codes_kn, scales_ng, zeros_ng, wq_nk, loss_n,
+                                     workspace, (hipStream_t)stream);
 }
 
 size_t qllm_awq_clip_search_workspace_bytes(int32_t N, int32_t K, int32_t group_size) { return awq_clip_search_workspace_bytes(N, K, group_size); }

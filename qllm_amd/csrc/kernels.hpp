@@ -273,6 +273,12 @@ size_t gptq_quant_workspace_bytes(int N, int K);                  // pure: the f
 int launch_gptq_quantize(const void *w_nk, int w_dtype, const float *u_kk, int N, int K, int bits, int group_size, int sym, int32_t *codes_kn,
                          float *scales_ng, float *zeros_ng, void *wq_nk, float *loss_n, void *workspace, hipStream_t stream);
 
+// ---- gptq_static.hip (the same solver with static groups: parameters from the original W, columns walked by perm, outputs in the original
+// order; shapes and workspace are gptq_quant.hip's) ----------------------------------------------------------------------------------------
+int launch_gptq_quantize_static(const void *w_nk, int w_dtype, const float *u_kk, const int32_t *perm_k, int N, int K, int bits, int group_size,
+                                int sym, int32_t *codes_kn, float *scales_ng, float *zeros_ng, void *wq_nk, float *loss_n, void *workspace,
+                                hipStream_t stream);
+
 // ---- awq_quant.hip (the AWQ quantizer: the clip search as a quadratic form over per-group Gram matrices, and the pseudo-quantizer) ---------
 constexpr int kAwqGramAlign = 16;                                 // the Gram tiles are staged four floats at a time
 bool awq_quant_shape_ok(int bits, int group_size);                // bits 2..8, group_size 32 / 64 / 128

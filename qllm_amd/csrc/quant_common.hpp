@@ -1,4 +1,4 @@
-// What the quantizer translation units (hqq_quant.hip, gptq_quant.hip, awq_quant.hip) share: the weight's storage types and their
+// What the quantizer translation units (hqq_quant.hip, gptq_quant.hip, gptq_static.hip, awq_quant.hip) share: the weight's storage types and their
 // conversions, the host-side dispatch on the weight's dtype, the 16-lane min / max butterfly and the way codes leave a row tile.
 // Grids differ per quantizer (find_params, grid_of / code_of) and stay with their kernels; so do HQQ's DPP reductions: a sum in another
 // order changes bits, another cross-lane instruction changes speed.

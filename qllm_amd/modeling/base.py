@@ -30,6 +30,7 @@ class QuantConfig:
     by_layer: Dict[str, dict] = field(default_factory=dict)  # quant_config_by_layer.json (mixed precision)
     desc_act: bool = False           # GPTQ act-order / symmetric grid: recorded by quantization/gptq.py; the layers
     sym: bool = False                # themselves carry g_idx and their zero points, so loading needs neither
+    static_groups: bool = False      # GPTQ static groups: with it a desc_act checkpoint's layers have the trivial g_idx
 
     @classmethod
     def from_dir(cls, path: str) -> "QuantConfig":
@@ -54,6 +55,7 @@ class QuantConfig:
         cfg = cls(bits=int(bits), group_size=int(group))
         cfg.compatible_with_autogptq = bool(raw.get("COMPATIBLE_WITH_AUTOGPTQ", False))
         cfg.desc_act, cfg.sym = bool(raw.get("desc_act", False)), bool(raw.get("sym", False))
+        cfg.static_groups = bool(raw.get("static_groups", False))
         if "version" not in raw:  # GPTQ-for-LLaMa / AutoGPTQ checkpoints: GPTQ layout, zeros stored minus one
             cfg.version, cfg.quant_method, cfg.compatible_with_autogptq = "GPTQ", "gptq", True
         else:
@@ -72,6 +74,8 @@ class QuantConfig:
             d["desc_act"] = True
         if self.sym:
             d["sym"] = True
+        if self.static_groups:
+            d["static_groups"] = True
         return d
 
 

@@ -418,6 +418,11 @@ def gptq_quantize(weight: torch.Tensor, u: Optional[torch.Tensor], bits: int, gr
     include/qllm_mi355x.h): (codes i32 [K, N], scales f32 [N, K/g], zeros f32 [N, K/g], wq [N, K] in weight's dtype or None,
     loss f32 [N]).  `out`: that tuple preallocated (wq may be None); `workspace`: a uint8 tensor of at least
     qllm_gptq_quantize_workspace_bytes -- both for callers that capture the call in a graph or own the memory."""
+    return _gptq_call("qllm_gptq_quantize", weight, u, (), bits, group_size, sym, want_wq, out, workspace)
+
+
+def _gptq_call(entry, weight, u, perm_args, bits, group_size, sym, want_wq, out, workspace):
+    """gptq_quantize / gptq_quantize_static: the checks, outputs and workspace both share; perm_args goes between u and N."""
     n, k, code = _check_weight(weight)
     lib = _lib.load()
     g = k if group_size == -1 else int(group_size)
@@ -433,10 +438,35 @@ def gptq_quantize(weight: torch.Tensor, u: Optional[torch.Tensor], bits: int, gr
     need = lib.qllm_gptq_quantize_workspace_bytes(n, k)
     ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev) if workspace is None else workspace
     with torch.cuda.device(dev):
-        rc = lib.qllm_gptq_quantize(weight.data_ptr(), code, _ptr(u), n, k, int(bits), g, 1 if sym else 0, *(_ptr(t) for t in out),
-                                    ws.data_ptr(), ws.numel(), _stream_ptr())
+        rc = getattr(lib, entry)(weight.data_ptr(), code, _ptr(u), *perm_args, n, k, int(bits), g, 1 if sym else 0, *(_ptr(t) for t in out),
+                                 ws.data_ptr(), ws.numel(), _stream_ptr())
     _lib.check(rc)
     return out
+
+
+def gptq_quantize_static(weight: torch.Tensor, u: Optional[torch.Tensor], perm: Optional[torch.Tensor], bits: int, group_size: int = 128,
+                         sym: bool = False, want_wq: bool = True, out=None, workspace: Optional[torch.Tensor] = None,
+                         check_perm: bool = True):
+    """gptq_quantize with static groups (qllm_gptq_quantize_static, include/qllm_mi355x.h): weight [N, K] in the ORIGINAL column order,
+    u [K, K] fp32 in processing order (None: round-to-nearest), perm [K] (int32 or int64 on the device; None: identity) with processing
+    position j -> original column perm[j].  Every group's scale / zero comes from `weight` itself; the columns are walked in perm's
+    order.  Same outputs, `out` and `workspace` as gptq_quantize, but codes and wq are already in the original column order and scales /
+    zeros in the original group numbering.  perm is checked on the device to be a permutation of 0..K-1 (ValueError otherwise; this
+    reads one flag back, so a caller that captures the call in a graph passes check_perm=False and vouches for it)."""
+    perm32 = None
+    if perm is not None:
+        k = weight.shape[-1]
+        if perm.dtype not in (torch.int32, torch.int64) or tuple(perm.shape) != (k,) or perm.device != weight.device:
+            raise RuntimeError(f"perm must be an int32 / int64 [{k}] tensor on {weight.device}, got {tuple(perm.shape)} {perm.dtype} on {perm.device}")
+        if check_perm:
+            p64 = perm.long()
+            inside = (p64 >= 0) & (p64 < k)
+            seen = torch.zeros(k, dtype=torch.bool, device=perm.device)
+            seen[p64.clamp(0, k - 1)] = True
+            if not bool((inside.all() & seen.all()).item()):
+                raise ValueError(f"perm must be a permutation of 0..{k - 1}")
+        perm32 = perm.to(torch.int32).contiguous()
+    return _gptq_call("qllm_gptq_quantize_static", weight, u, (_ptr(perm32),), bits, group_size, sym, want_wq, out, workspace)
 
 
 def _awq_f32(t: Optional[torch.Tensor], name: str, shape, dev):
@@ -543,4 +573,4 @@ def unpack_native(w: QllmWeight, keep, layout: str):
 
 __all__ = ["make_weight", "linear_forward", "linear_forward_grouped", "dequant", "gather_columns", "unpack_qweight", "pack_qweight",
            "workspace", "QllmUnsupported", "LAYOUTS", "plan_describe", "repack_native", "unpack_native", "hqq_quantize", "gptq_quantize",
-           "awq_quantize", "awq_clip_search"]
+           "gptq_quantize_static", "awq_quantize", "awq_clip_search"]

@@ -4,6 +4,12 @@ against a per-column torch loop of the same algorithm on the same inputs (six sm
 replaces).  Events around each leg, one warm-up, `--repeats` timed runs, median reported.
 
     python tools/gptq_quantize_bench.py [--shapes 4096x4096,4096x11008,11008x4096] [--repeats 3] [--no-loop]
+
+--static-groups times, instead of the torch loop, the static-groups solver (qllm_gptq_quantize_static) next to qllm_gptq_quantize on the
+same inputs in the same run, alternating, with the torch work each path needs around its kernel (dynamic + act-order: W[:, perm] before,
+codes[inv] and wq[:, inv] after; static: perm as int32), and then what the feature is for: the batch-1 forward of a 4096 x 4096 4-bit
+g128 layer quantized plain, with act-order, and with act-order + static groups (events around 200 graph-free calls after a warm-up,
+median of three), each next to its qllm_plan_describe line.
 """
 import argparse
 import os
@@ -63,11 +69,70 @@ def timed(fn, repeats):
     return statistics.median(ts), min(ts), max(ts), out
 
 
+def static_leg(W, w, U, perm, repeats):
+    """One line: both solvers on the same (W, U, perm), alternating, and the torch side of each path."""
+    K = W.shape[1]
+    p32 = perm.int() if perm is not None else None
+    t_d, t_s = [], []
+    for _ in range(repeats):
+        t_d.append(timed(lambda: ops.gptq_quantize(w, U, 4, 128, False), 1)[0])
+        t_s.append(timed(lambda: ops.gptq_quantize_static(W, U, p32, 4, 128, False, check_perm=False), 1)[0])
+    codes, _, _, wq, _ = ops.gptq_quantize(w, U, 4, 128, False)
+    torch_d = torch_s = 0.0
+    if perm is not None:
+        inv = torch.argsort(perm)
+        torch_d = timed(lambda: W[:, perm].contiguous(), repeats)[0] + timed(lambda: (codes[inv].contiguous(), wq[:, inv].contiguous()), repeats)[0]
+        torch_s = timed(lambda: perm.int(), repeats)[0]
+    d, s = statistics.median(t_d), statistics.median(t_s)
+    return (f"qllm_gptq_quantize {d:.3f} ms [{min(t_d):.3f}..{max(t_d):.3f}] + torch {torch_d:.3f} ms | qllm_gptq_quantize_static {s:.3f} ms "
+            f"[{min(t_s):.3f}..{max(t_s):.3f}] + torch {torch_s:.3f} ms | static / dynamic kernel x{s / d:.3f}, with torch x{(s + torch_s) / (d + torch_d):.3f}")
+
+
+def forward_leg(N=4096, K=4096, calls=200):
+    """Batch-1 forward of one layer quantized three ways, from the same weights and Hessian."""
+    gen = torch.Generator().manual_seed(N + K)
+    W = (0.02 * torch.randn((N, K), generator=gen)).half()
+    r = K // 8
+    X = ((torch.randn((2048, r), generator=gen) @ (torch.randn((r, K), generator=gen) / r ** 0.5) + 0.35 * torch.randn((2048, K), generator=gen))
+         * torch.exp(0.8 * torch.randn(K, generator=gen))).half().to(DEV)
+    H, _ = gptq.accumulate_hessian(None, 0, X)
+    del X
+    x = torch.randn((1, K), generator=gen).half().to(DEV)
+    layers = {}
+    for name, kw in (("plain", {}), ("act-order", dict(act_order=True)), ("act-order + static groups", dict(act_order=True, static_groups=True))):
+        lin = torch.nn.Linear(K, N, bias=False).half()
+        lin.weight.data = W.clone()
+        layers[name] = gptq.quantize_linear(lin, H, 4, 128, device=DEV, **kw)
+        with torch.no_grad():
+            for _ in range(20):
+                layers[name](x)
+    torch.cuda.synchronize()
+    times = {name: [] for name in layers}
+    with torch.no_grad():
+        for _ in range(3):
+            for name, layer in layers.items():     # (alternating: the three share whatever else the machine is doing)
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(calls):
+                    layer(x)
+                b.record()
+                torch.cuda.synchronize()
+                times[name].append(a.elapsed_time(b) / calls * 1e3)
+    for name, layer in layers.items():
+        act = layer._resolve_act_order()
+        w = layer.native_descriptor(0) if act else layer.decode_descriptor()      # act-order: the row-sorted native copy behind the gather
+        plan = ("column gather of x + " if act else "") + (ops.plan_describe([w], 1) if w is not None else "(no native copy)")
+        t = times[name]
+        print(f"forward M=1 N={N} K={K} w4 g128 {name}: {statistics.median(t):.2f} us per call [{min(t):.2f}..{max(t):.2f}]  act_order={act}  "
+              f"loss {layer.gptq_loss:.4e}  plan: {plan}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="4096x4096,4096x11008,11008x4096", help="NxK (out_features x in_features), comma-separated")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--no-loop", action="store_true")
+    ap.add_argument("--static-groups", action="store_true", help="time qllm_gptq_quantize_static next to qllm_gptq_quantize, and the forward")
     a = ap.parse_args()
     info = _lib.device_info(0)
     print(f"device: {info['arch']} {info['compute_units']} CUs; torch {torch.__version__}")
@@ -82,7 +147,7 @@ def main():
         del X
         for act in (False, True):
             h = H.clone()
-            w = W
+            w, perm = W, None
             if act:
                 perm = torch.argsort(torch.diag(h), descending=True)
                 w, h = W[:, perm].contiguous(), h[perm][:, perm]
@@ -90,6 +155,9 @@ def main():
             h[idx, idx] += 0.01 * torch.mean(torch.diag(h))
             t_fac = timed(lambda: gptq._factor(h), a.repeats)
             U, where = t_fac[3]
+            if a.static_groups:
+                print(f"N={N} K={K} act_order={int(act)}: " + static_leg(W, w, U, perm, a.repeats), flush=True)
+                continue
             t_k = timed(lambda: ops.gptq_quantize(w, U, 4, 128, False), a.repeats)
             t_rtn = timed(lambda: ops.gptq_quantize(w, None, 4, 128, False), a.repeats)
             n_wg, tri = (N + 15) // 16, sum(128 * min(128, K - c) * 4 for b in range(0, K, 128) for c in range(b, K, 128))
@@ -102,6 +170,8 @@ def main():
                 diff = float((t_l[3].to(wq.dtype) != wq).float().mean())     # the loop's fp32 values, rounded as the kernel rounds its own
                 line += f"  torch column loop {t_l[0]:.1f} ms = x{t_l[0] / t_k[0]:.0f}  (dequantized weights differing from the loop's: {diff:.3%})"
             print(line, flush=True)
+    if a.static_groups:
+        forward_leg()
 
 
 if __name__ == "__main__":
