@@ -264,6 +264,24 @@ int qllm_pack_qweight(const int32_t *q_kn, int32_t layout, int32_t bits, int32_t
  * not range-checked).  x, perm, out 16-byte aligned, out must not alias x; K % 8 == 0 and K <= 28672, else QLLM_ERR_UNSUPPORTED. */
 int qllm_gather_columns(const void *x, const int32_t *perm, void *out, int32_t M, int32_t K, int32_t act_dtype, void *stream);
 
+/* y[M,N] = x[:, perm_k] . dequant(w) (+ bias): qllm_gather_columns and qllm_linear_forward in ONE launch, for the layers the bit-stream
+ * matvec serves (csrc/bitgemv_ao.hip: the gather happens while the kernel stages x in LDS; no gathered copy of x is written).  The
+ * act-order entry for the widths without a strip kernel: w describes the row-sorted copy of an act-order layer (a PLAIN descriptor,
+ * g_idx NULL, the layer's own scales / qzeros / bias), perm_k = argsort(g_idx).  The result is bit-identical to qllm_linear_forward on
+ * a qllm_gather_columns copy of x.
+ * When to use it: every column block gathers x for itself, so the saved launch pays at M <= 2 (0.2-2 us faster than the two calls on
+ * Llama-2-7B shapes) and the two calls are faster from about M = 4 on (profiles/bitgemv_actorder.md).
+ * Served: exactly the calls qllm_linear_forward hands to that matvec -- GPTQ / HQQ row-stream layouts, bits 2..8, K % 32 == 0,
+ * group_size % 32 == 0, 1 <= M <= 16, QLLM_BITGEMV not switched off; everything else is QLLM_ERR_UNSUPPORTED (gather with
+ * qllm_gather_columns and call qllm_linear_forward, or qllm_dequant + a GEMM).  w->g_idx set, a NULL or not 16-byte aligned perm_k,
+ * NULL x / y: QLLM_ERR_INVALID.  Every error is raised before any device work.
+ * perm_k: K int32 on the device, a permutation of 0..K-1.  Every entry is clamped to 0..K-1 before it is used: an array that is not
+ * a permutation gives a wrong result, never an access outside x.
+ * Workspace: qllm_workspace_bytes_act(w, M, act_dtype) (the matvec's slabs and counters); NULL: no K split.  No host
+ * synchronisation; hipGraph-capturable.  No reference counterpart (the reference's act-order kernels index scales[g_idx[k]]). */
+int qllm_linear_forward_permuted(const qllm_weight_t *w, const int32_t *perm_k, const void *x, void *y, int32_t M, int32_t act_dtype,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- HQQ quantizer (ABI 7) ---------------------------------------------------------------------------------------------------------- */
 /* W[N,K] (fp16 / bf16 / fp32 by w_dtype, row-major, 16-byte aligned) -> the HQQ layer buffers: qweight i32 [K*bits/32][N], scales f16
  * [K/g][N] = fp16(1/s), zeros f16 [K/g][N] = fp16(z).  The algorithm is HQQQuant.do_quantize's (qllm/quantization/hqq/quant_hqq.py:34-36,

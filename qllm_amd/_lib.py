@@ -28,6 +28,7 @@ EXPORTS = (
     "qllm_set_knob", "qllm_get_knob", "qllm_reset_knobs",
     "qllm_hqq_quantize_workspace_bytes", "qllm_hqq_quantize", "qllm_gptq_quantize_workspace_bytes", "qllm_gptq_quantize",
     "qllm_gptq_quantize_static",
+    "qllm_linear_forward_permuted",
     "qllm_awq_clip_search_workspace_bytes", "qllm_awq_clip_search", "qllm_awq_quantize",
 )
 
@@ -122,6 +123,8 @@ def _declare(lib):
     lib.qllm_pack_qweight.argtypes = [vp, i32, i32, i32, i32, vp, vp]
     lib.qllm_gather_columns.restype = C.c_int
     lib.qllm_gather_columns.argtypes = [vp, vp, vp, i32, i32, i32, vp]
+    lib.qllm_linear_forward_permuted.restype = C.c_int
+    lib.qllm_linear_forward_permuted.argtypes = [wp, vp, vp, vp, i32, i32, vp, sz, vp]
     lib.qllm_plan_describe.restype = C.c_int
     lib.qllm_plan_describe.argtypes = [wp, i32, i32, i32, C.c_char_p, sz]
     lib.qllm_debug_timeline.restype = C.c_int

@@ -259,7 +259,9 @@ static int run_panel(const qllm_weight_t *w, void *const *y, int n, const void *
   return launch_panel(p, stream);
 }
 
-static int run_bitgemv(const qllm_weight_t *w, void *y, const void *x, int M, int act_dtype, void *workspace, size_t workspace_bytes, hipStream_t stream) {
+// perm: NULL, or the permutation the kernel applies to x's columns while it stages them (qllm_linear_forward_permuted)
+static int run_bitgemv(const qllm_weight_t *w, void *y, const void *x, int M, int act_dtype, void *workspace, size_t workspace_bytes, hipStream_t stream,
+                       const int32_t *perm = nullptr) {
   BitGemvParams p;
   fill_call(p, *w, x, M, act_dtype);
   fill_layer(p, *w, y);
@@ -268,7 +270,7 @@ static int run_bitgemv(const qllm_weight_t *w, void *y, const void *x, int M, in
   p.group_size = w->group_size;
   p.ksplit = bitgemv_split_for(M, w->K, w->N, usable_ws(workspace, workspace_bytes));
   if (p.ksplit > 1) carve(workspace, &p.counters, &p.slabs);
-  return launch_bitgemv(p, w->bits, stream);
+  return perm ? launch_bitgemv_permuted(p, perm, w->bits, stream) : launch_bitgemv(p, w->bits, stream);
 }
 
 static int run_tile_group(const qllm_weight_t *w, void *const *y, int n, const void *x, int M, int act_dtype, void *workspace, size_t workspace_bytes,
@@ -422,6 +424,24 @@ int qllm_gather_columns(const void *x, const int32_t *perm, void *out, int32_t M
   if (!gather_columns_ok(K)) return set_error(QLLM_ERR_UNSUPPORTED, "column gather serves K %% 8 == 0, K <= 28672 (got %d)", K);
   if (M == 0) return QLLM_OK;
   return launch_gather_columns(x, perm, out, M, K, (hipStream_t)stream);
+}
+
+int qllm_linear_forward_permuted(const qllm_weight_t *w, const int32_t *perm_k, const void *x, void *y, int32_t M, int32_t act_dtype,
+                                 void *workspace, size_t workspace_bytes, void *stream) {
+  clear_error();
+  int rc = validate_weight(w);
+  if (rc) return rc;
+  if (w->g_idx) return set_error(QLLM_ERR_INVALID, "qllm_linear_forward_permuted takes a plain layer (g_idx must be NULL: sort the rows by group, pass the order as perm_k)");
+  if (!perm_k || (uintptr_t)perm_k % 16) return set_error(QLLM_ERR_INVALID, "perm_k must not be NULL and must be 16-byte aligned");
+  rc = check_io(x, y, M, act_dtype);
+  if (rc) return rc;
+  static const char kInstead[] = "gather x with qllm_gather_columns and call qllm_linear_forward, or use qllm_dequant + GEMM";
+  if (!knob("QLLM_BITGEMV", 1)) return set_error(QLLM_ERR_UNSUPPORTED, "QLLM_BITGEMV is off, and only the bit-stream matvec gathers while it stages x; %s", kInstead);
+  if (!bitgemv_ok(*w, M))
+    return set_error(QLLM_ERR_UNSUPPORTED, "the gathering matvec serves GPTQ / HQQ row-stream layers of 2..8 bits with K %% 32 == 0, group_size %% 32 == 0 and M <= %d "
+                     "(got bits=%d K=%d N=%d g=%d layout=%d M=%d); %s", kBitGemvMaxM, w->bits, w->K, w->N, w->group_size, w->layout, M, kInstead);
+  if ((long long)M * w->K >= (1ll << 31)) return set_error(QLLM_ERR_UNSUPPORTED, "the gathering matvec indexes x with 32 bits: M * K must be below 2^31 (M=%d K=%d); %s", M, w->K, kInstead);
+  return run_bitgemv(w, y, x, M, act_dtype, workspace, workspace_bytes, (hipStream_t)stream, perm_k);
 }
 
 int qllm_convert_bf16_to_f16(const void *src, void *dst, size_t n, void *stream) {

@@ -147,6 +147,9 @@ bool bitgemv_ok(const qllm_weight_t &w, int M);
 int bitgemv_split(int M, int K, int N);
 int bitgemv_cols();
 int launch_bitgemv(const BitGemvParams &p, int bits, hipStream_t stream);
+// bitgemv_ao.hip: the same matvec on x[:, perm] -- the gather of an act-order layer's activations happens in the staging pass (perm: K
+// int32, 16-byte aligned; entries are clamped to 0..K-1)
+int launch_bitgemv_permuted(const BitGemvParams &p, const int32_t *perm, int bits, hipStream_t stream);
 
 // ---- comm.hip: staging buffer of one rank = [2 parities][world][slot_bytes] payload | this control block ----------------------------
 constexpr int kCommMaxWorld = 16;

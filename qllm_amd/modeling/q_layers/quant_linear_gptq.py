@@ -98,7 +98,7 @@ class QuantLinearGPTQ(nn.Module, CompressWeight, HipForwardMixin):
     # sorting the rows by group (perm = argsort(g_idx)) gives a plain contiguous-group layer: the native copy of an act-order
     # layer is built from that row-permuted arrangement of its own integers (library unpack / pack kernels; bit-exact; the
     # row-stream intermediate is dropped) and the forward feeds it x[..., perm] (qllm_gather_columns).  The fused kernels then
-    # run at their no-act-order speed plus one gather of x (3- and 4-bit layers).  Groups that are not uniform, or QLLM_ACTORDER_SHADOW=0: no native
+    # run at their no-act-order speed plus one gather of x (3- and 4-bit layers; the other widths: _ao_descriptor below).  Groups that are not uniform, or QLLM_ACTORDER_SHADOW=0: no native
     # copy -> the in-place gather kernel on the reference buffers.
     _perm = None
 
@@ -109,13 +109,9 @@ class QuantLinearGPTQ(nn.Module, CompressWeight, HipForwardMixin):
             self.act_order = bool(self.g_idx[: self.groupsize].sum() != 0)
         return self.act_order
 
-    def _native_source(self):
-        if not self._resolve_act_order():
-            return HipForwardMixin._native_source(self)
-        self._perm = None
-        bits = self.bits
-        if os.environ.get("QLLM_ACTORDER_SHADOW", "1") == "0" or bits not in (3, 4) or not self.qweight.is_cuda:
-            return None
+    def _sorted_rows(self):
+        """(perm, qweight) of the layer's integers with the rows sorted by group -- perm = argsort(g_idx), interned; qweight in GPTQ
+        layout -- or None when the groups are not uniform (every group exactly `groupsize` rows)."""
         from ... import ops
         dev = self.qweight.device
         g = self.g_idx.to(dev).long()
@@ -124,13 +120,71 @@ class QuantLinearGPTQ(nn.Module, CompressWeight, HipForwardMixin):
         if self.infeatures % self.groupsize != 0 or counts.numel() != groups or not bool((counts == self.groupsize).all()):
             return None
         perm = torch.argsort(g, stable=True)
-        q = ops.unpack_qweight(self.qweight.contiguous(), "GPTQ", bits, self.infeatures, self.outfeatures)
-        qw = ops.pack_qweight(q.index_select(0, perm).contiguous(), "GPTQ", bits)
+        q = ops.unpack_qweight(self.qweight.contiguous(), "GPTQ", self.bits, self.infeatures, self.outfeatures)
+        qw = ops.pack_qweight(q.index_select(0, perm).contiguous(), "GPTQ", self.bits)
         del q
+        return _intern_perm(perm.to(torch.int32).contiguous()), qw
+
+    def _plain_descriptor(self, qw):
+        """Plain GPTQ descriptor (no g_idx) over the row-sorted qweight `qw` and the layer's own scales / qzeros / bias."""
+        from ... import ops
         b = self._f16(self.bias).contiguous() if self.bias is not None else None
-        self._perm = _intern_perm(perm.to(torch.int32).contiguous())
         return ops.make_weight("GPTQ", qw, self._f16(self.scales).contiguous(), self.qzeros.contiguous(), None, b,
-                               self.infeatures, self.outfeatures, self.groupsize, bits, 0)
+                               self.infeatures, self.outfeatures, self.groupsize, self.bits, 0)
+
+    def _native_source(self):
+        if not self._resolve_act_order():
+            return HipForwardMixin._native_source(self)
+        self._perm = None
+        if os.environ.get("QLLM_ACTORDER_SHADOW", "1") == "0" or self.bits not in (3, 4) or not self.qweight.is_cuda:
+            return None
+        src = self._sorted_rows()
+        if src is None:
+            return None
+        self._perm, qw = src
+        return self._plain_descriptor(qw)
+
+    # ---- act-order at 2 / 5 / 6 / 7 / 8 bits: the sorted copy stays in GPTQ layout, the kernel gathers ------------------------
+    # These widths have no strip-major layout; their decode kernel is the bit-stream matvec, which stages x through LDS itself and
+    # can gather x[:, perm] in that pass (ops.linear_forward_permuted: ONE launch, no gathered copy of x, no fp16 W) -- used where
+    # that beats gather_columns + the plain matvec on the same copy (_ao_one_launch).  The sorted copy
+    # sits NEXT TO the original qweight -- such a layer costs 2x its packed bytes (the original is what state_dict() and the
+    # fallback for more than 16 rows read; releasing it is not done here).
+    _ao = None
+    _ao_key = None
+
+    def _ao_one_launch(self, rows: int) -> bool:
+        """Whether `rows` rows go through the gathering matvec (one launch) or through gather_columns + the plain matvec on the same
+        copy (two launches; same bits).  Measured, profiles/bitgemv_actorder.md: every 32-column block of the gathering kernel
+        gathers the whole of x for itself, which costs 0.4-3.6 us more than the plain staging at 1-2 rows -- 0.2-2.1 us less than a
+        gather launch -- and 3.4-32 us more at 8-16 rows, where the separate gather wins by 0.5-27 us; 4 rows go either way by shape.
+        The one case that lost at 1 row, 2 bits with N > K (4096 -> 11008: +0.2 .. +0.4 us), takes two launches as well."""
+        if rows == 1 and self.bits == 2 and self.outfeatures > self.infeatures:
+            return False
+        return rows <= 2
+
+    def _ao_descriptor(self, add_zero_bias: int):
+        """(plain descriptor of the row-sorted copy, perm) for the fused act-order decode, built once and cached on the buffers'
+        identity and version; None for 3- / 4-bit layers (native path), non-uniform groups, QLLM_ACTORDER_SHADOW=0, CPU buffers,
+        QLLM_BITGEMV switched off (asked BEFORE the copy is built: nothing would use it) and a layer the kernel has refused (forward
+        drops the copy and leaves the key: the refusal is remembered until a buffer changes)."""
+        if self.bits in (3, 4) or os.environ.get("QLLM_ACTORDER_SHADOW", "1") == "0" or not self.qweight.is_cuda:
+            return None
+        from ... import ops
+        if ops.get_knob("QLLM_BITGEMV") == 0:
+            return None
+        key = (_tkey(self.qweight), _tkey(self.scales), _tkey(self.qzeros), _tkey(self.bias), _tkey(self.g_idx))
+        if self._ao_key != key:
+            self._ao, self._ao_key = None, key
+            src = self._sorted_rows()
+            if src is not None:
+                self._ao = self._plain_descriptor(src[1]) + (src[0],)   # (descriptor, keepalive, perm)
+        if self._ao is None:
+            return None
+        w, _keep, perm = self._ao
+        if w.add_zero_bias != add_zero_bias:  # (the AutoGPTQ offset is a field of the descriptor, not of the stored zero points)
+            w = ops.QllmWeight(w.qweight, w.scales, w.qzeros, w.g_idx, w.bias, w.K, w.N, w.group_size, w.bits, w.layout, int(add_zero_bias))
+        return w, perm
 
     def _regenerate_reference(self):
         qweight, scales, qzeros = HipForwardMixin._regenerate_reference(self)
@@ -161,5 +215,23 @@ class QuantLinearGPTQ(nn.Module, CompressWeight, HipForwardMixin):
                     return ops.linear_forward_shared(w, x2d).reshape(x.shape[:-1] + (self.outfeatures,))
                 except ops.QllmUnsupported:
                     self._needs_reference = True   # a shape the native kernels do not serve: the in-place gather kernel below
+            elif x.numel() // x.shape[-1] <= 16:
+                # decode sizes at 2 / 5 / 6 / 7 / 8 bits: the bit-stream matvec on the row-sorted copy -- gathering x itself (one
+                # launch) or fed the gathered x (two; siblings share the gather), whichever was measured faster: _ao_one_launch.
+                # Whatever the matvec does not serve takes the path below, as before
+                ao = self._ao_descriptor(azb)
+                if ao is not None:
+                    from ... import ops
+                    x2d = x.reshape(-1, x.shape[-1])
+                    try:
+                        if self._ao_one_launch(x2d.shape[0]):
+                            y = ops.linear_forward_permuted(ao[0], ao[1], x2d if x2d.is_contiguous() else x2d.contiguous())
+                        else:
+                            y = ops.linear_forward(ao[0], _gathered(x, ao[1]))
+                        return y.reshape(x.shape[:-1] + (self.outfeatures,))
+                    except ops.QllmUnsupported:
+                        # (M <= 16 and the knob are settled above: what is left is the layer's shape, K or the group size no multiple
+                        #  of 32 -- the same answer every time.  Drop the copy, keep the key: no rebuild, no exception per forward)
+                        self._ao = None
         g_idx = self.g_idx if self.act_order else None
         return self._hip_linear(x, g_idx, azb)

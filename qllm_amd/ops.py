@@ -131,6 +131,30 @@ def linear_forward(w: QllmWeight, x2d: torch.Tensor, out: Optional[torch.Tensor]
     return out
 
 
+def linear_forward_permuted(w: QllmWeight, perm: torch.Tensor, x2d: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y[M,N] = x2d[:, perm] . dequant(w) (+bias) in ONE launch (qllm_linear_forward_permuted): `w` is a plain descriptor -- the
+    row-sorted copy of an act-order layer -- and `perm` the int32 device permutation `gather_columns` takes.  Bit-identical to
+    `linear_forward(w, gather_columns(x2d, perm))`, and faster than it at 1-2 rows only (profiles/bitgemv_actorder.md).  Raises QllmUnsupported for every call the bit-stream matvec does not serve
+    (more than 16 rows, other layouts, QLLM_BITGEMV = 0): callers then gather and call linear_forward, or dequantise."""
+    _check_x(x2d, (w,))
+    _check_perm(perm, x2d)
+    lib = _lib.load()
+    m = x2d.shape[0]
+    if out is not None:
+        _check_out(out, m, w.N, x2d)
+    if m == 0:
+        return out if out is not None else torch.empty((0, w.N), dtype=x2d.dtype, device=x2d.device)
+    if out is None:
+        out = torch.empty((m, w.N), dtype=x2d.dtype, device=x2d.device)
+    with torch.cuda.device(x2d.device):
+        nbytes = lib.qllm_workspace_bytes_act(C.byref(w), m, _act_dtype(x2d))
+        ws = workspace(x2d.device, nbytes)
+        rc = lib.qllm_linear_forward_permuted(C.byref(w), perm.data_ptr(), x2d.data_ptr(), out.data_ptr(), m, _act_dtype(x2d),
+                                              ws.data_ptr(), ws.numel(), _stream_ptr())
+    _lib.check(rc)
+    return out
+
+
 _LAST_CONVERT: dict = {}
 
 
@@ -310,13 +334,17 @@ def ort_dequantize4bits(qweight: torch.Tensor, scales: torch.Tensor, qzeros: tor
     return out if scales.dtype == torch.float16 else out.to(scales.dtype)
 
 
+def _check_perm(perm: torch.Tensor, x2d: torch.Tensor):
+    if perm.dtype != torch.int32 or perm.device != x2d.device or perm.numel() != x2d.shape[1] or not perm.is_contiguous():
+        raise RuntimeError("perm must be a contiguous int32 tensor of K entries on x's device")
+
+
 def gather_columns(x2d: torch.Tensor, perm: torch.Tensor) -> torch.Tensor:
     """x2d[:, perm] for a contiguous [M, K] fp16 / bf16 matrix and an int32 device permutation (act-order layers: the
     activation side of the row-sorted weight copy).  The library's LDS-staged gather; shapes it does not take
     (K % 8, K > 28672) fall back to index_select."""
     _check_x(x2d, ())
-    if perm.dtype != torch.int32 or perm.device != x2d.device or perm.numel() != x2d.shape[1] or not perm.is_contiguous():
-        raise RuntimeError("perm must be a contiguous int32 tensor of K entries on x's device")
+    _check_perm(perm, x2d)
     out = torch.empty_like(x2d)
     if x2d.shape[0] == 0:
         return out
@@ -571,6 +599,6 @@ def unpack_native(w: QllmWeight, keep, layout: str):
     return qweight, scales, qzeros
 
 
-__all__ = ["make_weight", "linear_forward", "linear_forward_grouped", "dequant", "gather_columns", "unpack_qweight", "pack_qweight",
+__all__ = ["make_weight", "linear_forward", "linear_forward_grouped", "linear_forward_permuted", "linear_forward_shared", "dequant", "gather_columns", "unpack_qweight", "pack_qweight",
            "workspace", "QllmUnsupported", "LAYOUTS", "plan_describe", "repack_native", "unpack_native", "hqq_quantize", "gptq_quantize",
            "gptq_quantize_static", "awq_quantize", "awq_clip_search"]
