@@ -133,6 +133,8 @@ static int fill_strip1_params(Strip1Params &p, const qllm_weight_t *w, void *con
   for (int i = 0; i < n; ++i) {
     fill_layer(p.prob[i], w[i], y[i]);
     p.prob[i].n_strips = w[i].N / 16;
+    // the kernel issues its zero-point load whatever the kind (one address form, no select): a symmetric layer reads a scale word
+    if (p.prob[i].zero_kind == ZK_SYM) p.prob[i].qzeros = w[i].scales;
     max_strips = std::max(max_strips, p.prob[i].n_strips);
   }
   return max_strips;

@@ -103,7 +103,7 @@ int launch_strip_dma_g128(const StripParams &p, int grid, hipStream_t stream);  
 struct Strip1Problem {  // 48 bytes
   const uint32_t *qweight;  // native: [N/16][K/8][16] words (3 bits: [N/16][3 K/32][16])
   const half_t *scales;     // native: [N/16][K/g][16]  (g = 128 or 64)
-  const void *qzeros;       // native: [N/16][K/128][2] words (packed), [N/16][K/128][16] halves (fp16), NULL (symmetric)
+  const void *qzeros;       // native: [N/16][K/128][2] words (packed), [N/16][K/128][16] halves (fp16), the scales (symmetric: loaded, never decoded)
   const half_t *bias;
   void *y;
   int n_strips;             // N / 16

@@ -97,6 +97,10 @@ __global__ __launch_bounds__(NW * 64, (MAXS <= 24 && !G64 && MR == 1 && !B3) ? 8
   const Strip1Problem pr = p.prob[blockIdx.y];
   asm volatile("" ::"s"(pr.qweight), "s"(pr.scales), "s"(pr.qzeros), "s"(pr.bias), "s"(pr.y), "s"(pr.n_strips), "s"(pr.zero_kind), "s"(p.x),
                "s"(p.T), "s"(p.n_groups), "s"(p.add_zero_bias), "s"(p.act_bf16));
+  // the two flags the uniform branches and the tail read: taken from the first batch of scalar loads (as outputs of an asm they cannot
+  // be re-loaded next to their use -- hipcc otherwise sinks a second s_load of each into the decode branch and in front of the y store)
+  int add_zero_bias = p.add_zero_bias, act_bf16 = p.act_bf16;
+  asm volatile("" : "+s"(add_zero_bias), "+s"(act_bf16));
   uint64_t *dbg_slot = nullptr;
   if constexpr (DBG) {
     if (p.dbg && wave == 0 && blockIdx.y == 0) {
@@ -129,27 +133,33 @@ __global__ __launch_bounds__(NW * 64, (MAXS <= 24 && !G64 && MR == 1 && !B3) ? 8
   const int G0 = tb / KPG;
   const size_t grow = (size_t)b * p.n_groups + G0;         // first group row of the wave in the strip's scale / zero tables
   const int zk = pr.zero_kind;
-  const uint32_t *zbase = (zk == ZK_SYM) ? (const uint32_t *)pr.scales : (const uint32_t *)pr.qzeros;
-  const int zmul = (zk == ZK_PACKED) ? 2 : 8;              // dwords per group row
-  const int zoff = (zk == ZK_PACKED) ? (i >> 3) : (i >> 1);
   half_t sc[NPASS][GPL];
   uint32_t zraw[NPASS][GPL], zraw2[B3 ? NPASS : 1][GPL];  // (zraw2: packed 3-bit zero points are bit 3 i of the group row's 64-bit pair)
-#pragma unroll
-  for (int ps = 0; ps < NPASS; ++ps)
-#pragma unroll
-    for (int h = 0; h < GPL; ++h) {
-      // the lane's group(s) of the pass: 4 ps + g (128-wide), 8 ps + 2 g + h (64-wide)
-      const int gj = min((G64 ? 8 * ps + 2 * g + h : 4 * ps + g), NG - 1);  // (lanes past the last group re-read it; their sums of x are zero)
-      sc[ps][h] = pr.scales[(grow + gj) * 16 + i];
-      if constexpr (B3) {
-        // packed: both words of the pair; fp16: the dword holding the half; symmetric: any valid dword
-        zraw[ps][h] = zbase[(grow + gj) * zmul + ((zk == ZK_PACKED) ? 0 : zoff)];
-        zraw2[ps][h] = zbase[(grow + gj) * zmul + ((zk == ZK_PACKED) ? 1 : zoff)];
-      } else {
-        zraw[ps][h] = zbase[(grow + gj) * zmul + zoff];
-      }
-    }
   uint32_t w[MAXS], wh[B3 ? MAXS : 1];
+  {
+    // a wave-uniform base (the wave's first group row) + a 32-bit lane offset: element (gj, i) of the [group][16] scale rows is
+    // 16 gj + i; its zero point sits in dword (16 gj + i) >> 3 of the packed rows (2 dwords per group), >> 1 of the fp16 rows (8).
+    // A symmetric layer has no table: the host points qzeros at the scales (a valid dword, never decoded)
+    const char *sbase = (const char *)(pr.scales + grow * 16);
+    const int zmul = (zk == ZK_PACKED) ? 2 : 8;          // dwords per group row
+    const char *zb = (const char *)((const uint32_t *)pr.qzeros + grow * zmul);
+    const uint32_t zsh = (zk == ZK_PACKED) ? 3u : 1u, pair = (B3 && zk == ZK_PACKED) ? 1u : 0u;
+#pragma unroll
+    for (int ps = 0; ps < NPASS; ++ps)
+#pragma unroll
+      for (int h = 0; h < GPL; ++h) {
+        // the lane's group(s) of the pass: 4 ps + g (128-wide), 8 ps + 2 g + h (64-wide)
+        const uint32_t gj = (uint32_t)min((G64 ? 8 * ps + 2 * g + h : 4 * ps + g), NG - 1);  // (lanes past the last group re-read it; their sums of x are zero)
+        const uint32_t e = gj * 16 + (uint32_t)i;
+        sc[ps][h] = *(const half_t *)(sbase + e * 2);
+        if constexpr (B3) {                              // packed: both words of the pair; fp16 / symmetric: the one dword twice
+          zraw[ps][h] = *(const uint32_t *)(zb + ((e >> zsh) & ~pair) * 4);
+          zraw2[ps][h] = *(const uint32_t *)(zb + ((e >> zsh) | pair) * 4);
+        } else {
+          zraw[ps][h] = *(const uint32_t *)(zb + (e >> zsh) * 4);
+        }
+      }
+  }
   if constexpr (B3) {
     // the strip is [3 T word rows][16]: k-step t = rows 3 t .. 3 t + 2; the lane's 24-bit field straddles rows {0,0,1,2}[g] / {0,1,2,2}[g]
     const uint32_t *wl3 = pr.qweight + ((size_t)b * T + tb) * 48 + i;
@@ -182,12 +192,23 @@ __global__ __launch_bounds__(NW * 64, (MAXS <= 24 && !G64 && MR == 1 && !B3) ? 8
 #pragma unroll
       for (int u = 0; u < XL; ++u) asm volatile("" : "+v"(xa[m][u]));  // (pins the staging below the weight loads: strip_kernel.hpp)
     *(uint32_t *)(zeros + 4 * lane) = 0u;
+    // bf16 activations: converted in place behind ONE wave-uniform branch (the asm keeps hipcc from turning the branch back into
+    // convert-then-select on every launch); fp16 launches execute none of it
+    if (act_bf16) {
+#pragma unroll
+      for (int m = 0; m < MR; ++m)
+#pragma unroll
+        for (int u = 0; u < XL; ++u) {
+          xa[m][u] = __builtin_bit_cast(uint4_t, bf16x8_to_h8(xa[m][u]));
+          asm volatile("" : "+v"(xa[m][u]));
+        }
+    }
 #pragma unroll
     for (int m = 0; m < MR; ++m)
 #pragma unroll
     for (int u = 0; u < XL; ++u) {
       const half8_t zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
-      half8_t xv = p.act_bf16 ? bf16x8_to_h8(xa[m][u]) : __builtin_bit_cast(half8_t, xa[m][u]);
+      half8_t xv = __builtin_bit_cast(half8_t, xa[m][u]);   // (bf16: converted above)
       xv = xkeep[u] ? xv : zero8;
       // fragment slot order and per-slot divisors (the B-fragment construction below):
       //   4 bits: (k0,k4 | k1,k5 | k2,k6 | k3,k7), divisors (1,1 | 16,16 | 1,1 | 16,16);  3 bits: (k0,k5 | k1,k6 | k2,k7 | k3,k4), (2,1 | 16,8 | 128,64 | 1,1)
@@ -236,18 +257,38 @@ __global__ __launch_bounds__(NW * 64, (MAXS <= 24 && !G64 && MR == 1 && !B3) ? 8
   constexpr int NCF = (MR > 1) ? MR : GPL;   // corrections per lane and pass: its group(s), or its four batch rows
   float sf[NPASS][GPL], cf[NPASS][NCF];
   if constexpr (LVL >= 4) {
-    const uint32_t zsel_p = (zk == ZK_PACKED) ? 0xffffffffu : 0u, zsel_h = (zk == ZK_F16) ? 0xffffffffu : 0u;
-    const uint32_t zsel_s = (zk == ZK_SYM) ? __builtin_bit_cast(uint32_t, B3 ? 4.0f : 8.0f) : 0u;
+    // a launch decodes its own kind of zero point only: one wave-uniform three-way branch (the asm keeps it a branch)
+    float zfs[NPASS][GPL];
+    if (zk == ZK_PACKED) {
+#pragma unroll
+      for (int ps = 0; ps < NPASS; ++ps)
+#pragma unroll
+        for (int h = 0; h < GPL; ++h) {
+          const uint32_t zr = zraw[ps][h];
+          if constexpr (B3) zfs[ps][h] = (float)(((uint32_t)(((((uint64_t)zraw2[ps][h]) << 32) | zr) >> (3 * i)) + (uint32_t)add_zero_bias) & 7u);
+          else zfs[ps][h] = (float)(((zr >> (4 * (i & 7))) + (uint32_t)add_zero_bias) & 15u);
+          asm volatile("" : "+v"(zfs[ps][h]));
+        }
+    } else if (zk == ZK_F16) {
+#pragma unroll
+      for (int ps = 0; ps < NPASS; ++ps)
+#pragma unroll
+        for (int h = 0; h < GPL; ++h) {
+          const uint32_t zr = zraw[ps][h];
+          zfs[ps][h] = (float)__builtin_bit_cast(half_t, (uint16_t)((i & 1) ? (zr >> 16) : (zr & 0xffffu)));
+          asm volatile("" : "+v"(zfs[ps][h]));
+        }
+    } else {
+#pragma unroll
+      for (int ps = 0; ps < NPASS; ++ps)
+#pragma unroll
+        for (int h = 0; h < GPL; ++h) zfs[ps][h] = B3 ? 4.0f : 8.0f;
+    }
 #pragma unroll
     for (int ps = 0; ps < NPASS; ++ps)
 #pragma unroll
       for (int h = 0; h < GPL; ++h) {
-        const uint32_t zr = zraw[ps][h];
-        float zp;
-        if constexpr (B3) zp = (float)(((uint32_t)(((((uint64_t)zraw2[ps][h]) << 32) | zr) >> (3 * i)) + (uint32_t)p.add_zero_bias) & 7u);
-        else zp = (float)(((zr >> (4 * (i & 7))) + (uint32_t)p.add_zero_bias) & 15u);
-        const float zh = (float)__builtin_bit_cast(half_t, (uint16_t)((i & 1) ? (zr >> 16) : (zr & 0xffffu)));
-        const float zf = __builtin_bit_cast(float, (__builtin_bit_cast(uint32_t, zp) & zsel_p) | (__builtin_bit_cast(uint32_t, zh) & zsel_h) | zsel_s);
+        const float zf = zfs[ps][h];
         sf[ps][h] = (float)sc[ps][h];
         if constexpr (MR > 1) {
 #pragma unroll
@@ -266,11 +307,14 @@ __global__ __launch_bounds__(NW * 64, (MAXS <= 24 && !G64 && MR == 1 && !B3) ? 8
   // ---- A fragment addresses: lane (g, i) is row i of the A operand; rows 4 j .. 4 j + 3 belong to group j of the pass -----------
   // k-step s reads at byte offset 64 s (an immediate): from the staged chunk if the row belongs to the k-step's group, else from
   // the zero block (whose address is pre-biased by the group's first offset)
-  uint32_t a_addr[NG];
-  const uint32_t xs_lane = (uint32_t)(wbase - (char *)lds) + 16 * g, z_lane = (uint32_t)(zeros - (char *)lds) + 16 * g;
+  // k-step s = KPG j + r of pass ps reads at a_ptr[j] + 1024 ps + 64 r (an immediate): a row of the group finds its staged chunk there
+  // -- the own-group address is ONE per-lane value: row i belongs to group i / 4 (i / 2) of every pass -- and every other row the zero
+  // block at + 64 r: a compare and a select per group.  (Pointers, not offsets: the LDS base is added once, not per group.)
+  const char *a_ptr[NG];
+  const char *xs_own = wbase + 16 * g + 64 * KPG * (G64 ? (i >> 1) : (i >> 2)) + (MR > 1 ? (i & 3) * (XL * 1024) : 0);
 #pragma unroll
-  for (int j = 0; j < NG; ++j)   // (the zero block is read at + 64 s for the k-steps s of group j: bias its address by the group's first offset)
-    a_addr[j] = (G64 ? ((i >> 1) == (j & 7)) : ((i >> 2) == (j & 3))) ? xs_lane + (MR > 1 ? (i & 3) * (XL * 1024) : 0) : z_lane - 64 * KPG * j;
+  for (int j = 0; j < NG; ++j)
+    a_ptr[j] = (G64 ? ((i >> 1) == (j & 7)) : ((i >> 2) == (j & 3))) ? xs_own : zeros + 16 * g - 1024 * ((KPG * j) >> 4);
 
   float4_t acc[NPASS][NCH];
   const uint32_t mask_lo = nib_mask_vgpr();  // 0x000f000f
@@ -284,7 +328,7 @@ __global__ __launch_bounds__(NW * 64, (MAXS <= 24 && !G64 && MR == 1 && !B3) ? 8
   for (int s = 0; s < MAXS; ++s) {
     const int j = s / KPG, ps = s >> 4, ch = s % NCH;
     if constexpr (LVL >= 2) {
-      const half8_t av = *(const half8_t *)((const char *)lds + a_addr[j] + 64 * s);
+      const half8_t av = *(const half8_t *)(a_ptr[j] + 1024 * ps + 64 * (s % KPG));
       if constexpr (LVL >= 3) {
         half2_t b0, b1, b2, b3;
         if constexpr (B3) {
@@ -379,7 +423,7 @@ __global__ __launch_bounds__(NW * 64, (MAXS <= 24 && !G64 && MR == 1 && !B3) ? 8
     if constexpr (!AR) {
       if (MR == 1 || mrow < p.M) {
         const size_t at = (size_t)mrow * pr.n_strips * 16 + n;   // (y is [M][N], N = 16 n_strips)
-        if (p.act_bf16) ((uint16_t *)pr.y)[at] = f32_to_bf16(v);
+        if (act_bf16) ((uint16_t *)pr.y)[at] = f32_to_bf16(v);
         else ((half_t *)pr.y)[at] = (half_t)v;
       }
     }
@@ -395,7 +439,7 @@ __global__ __launch_bounds__(NW * 64, (MAXS <= 24 && !G64 && MR == 1 && !B3) ? 8
     uint16_t *stage = (uint16_t *)(lds + 16 * RS);  // (the first wave's staging area: its activations are long consumed)
     int *s_last = (int *)(lds + 16 * RS) + 16;
     if (wave == 0) {
-      if (lane < 16) stage[lane] = p.act_bf16 ? f32_to_bf16(vfin) : __builtin_bit_cast(uint16_t, (half_t)vfin);
+      if (lane < 16) stage[lane] = act_bf16 ? f32_to_bf16(vfin) : __builtin_bit_cast(uint16_t, (half_t)vfin);
       if (lane < 2) {
         const uint4_t chunk = *(const uint4_t *)(stage + 8 * lane);
         for (int q = 0; q < world; ++q) {
@@ -441,7 +485,7 @@ __global__ __launch_bounds__(NW * 64, (MAXS <= 24 && !G64 && MR == 1 && !B3) ? 8
         const uint32_t wds[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          if (p.act_bf16) {
+          if (act_bf16) {
             a8[2 * j] += __builtin_bit_cast(float, wds[j] << 16);
             a8[2 * j + 1] += __builtin_bit_cast(float, wds[j] & 0xffff0000u);
           } else {
@@ -454,7 +498,7 @@ __global__ __launch_bounds__(NW * 64, (MAXS <= 24 && !G64 && MR == 1 && !B3) ? 8
       uint32_t o[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        if (p.act_bf16) o[j] = (uint32_t)f32_to_bf16(a8[2 * j]) | ((uint32_t)f32_to_bf16(a8[2 * j + 1]) << 16);
+        if (act_bf16) o[j] = (uint32_t)f32_to_bf16(a8[2 * j]) | ((uint32_t)f32_to_bf16(a8[2 * j + 1]) << 16);
         else o[j] = as_u32(half2_t{(half_t)a8[2 * j], (half_t)a8[2 * j + 1]});
       }
       *((uint4_t *)pr.y + c) = uint4_t{o[0], o[1], o[2], o[3]};
