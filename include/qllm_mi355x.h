@@ -122,7 +122,7 @@ int qllm_is_lab_build(void);
  * other threads: set them before serving.  Settable names (values outside the range every built kernel covers are refused):
  *   QLLM_STRIP1 0|1|2, QLLM_STRIP1_MAX_M 1..4, QLLM_STRIP1_3BIT 0|1, QLLM_PANEL 0|1, QLLM_PANEL_MIN_M 17..129, QLLM_PANEL_GROUP_MIN_M 17..129, QLLM_GEMM2 0|1, QLLM_GEMM3 0|1,
  *   QLLM_GEMM2_MIN_M >= 33, QLLM_GEMM3_MIN_M >= 0 (0: the measured 384 / 768 line), QLLM_GEMM2_SPLITK 0|1, QLLM_GEMM3_TAIL 0|1, QLLM_GEMM3_BF16 0|1, QLLM_GEMM3_GROUP 0|1,
- *   QLLM_SKINNY_MAX_M 0..64, QLLM_STRIP_MIN >= 0, QLLM_BITGEMV 0|1.
+ *   QLLM_SKINNY_MAX_M 0..64, QLLM_STRIP_MIN >= 0, QLLM_BITGEMV 0|1, QLLM_BITPANEL 0|1, QLLM_BITPANEL_LDS 0|1, QLLM_BITPANEL_MAX_M 17..512 (the last three: qllm_linear_forward_bitpanel, no route).
  * qllm_plan_describe() reflects them (it asks the same decision functions the forward calls execute).  QLLM_ERR_INVALID for any other name. */
 int qllm_set_knob(const char *name, int32_t value);
 int qllm_get_knob(const char *name, int32_t *value, int32_t *is_set);
@@ -281,6 +281,40 @@ int qllm_gather_columns(const void *x, const int32_t *perm, void *out, int32_t M
  * synchronisation; hipGraph-capturable.  No reference counterpart (the reference's act-order kernels index scales[g_idx[k]]). */
 int qllm_linear_forward_permuted(const qllm_weight_t *w, const int32_t *perm_k, const void *x, void *y, int32_t M, int32_t act_dtype,
                                  void *workspace, size_t workspace_bytes, void *stream);
+
+/* y[M,N] = x[M,K] . dequant(w) (+ bias) for MID-BATCH calls, 17 <= M <= 512, on the row-stream layouts read in place, at every width
+ * from 2 to 8 bits (csrc/bitpanel.hip: 64-column panels x up to 128 rows per block on v_mfma_f32_16x16x32_f16, x tiles shared through
+ * LDS, weight fragments built in registers from the packed words, split-K through the workspace).  An ADDITIVE entry: the planner
+ * does not know it -- qllm_linear_forward and qllm_plan_describe answer these calls as before ("unsupported (no fused kernel ...)"
+ * for 2 / 5 / 6 / 7 / 8 bits above 16 rows), and a caller that used to take qllm_dequant + a dense GEMM there (2 K N bytes of fp16 W
+ * written and read back) may call this instead.  It also serves the in-place 3- / 4-bit layers the planner refuses (ragged N).
+ * Served: GPTQ / HQQ layouts, bits 2..8, K % 32 == 0, group_size % 32 == 0, any N >= 1 (HQQ: even N, 4-byte aligned zeros); packed
+ * (with add_zero_bias), NULL (symmetric) or fp16 zero points; optional bias; fp16 or bf16 activations (bf16 is converted to fp16 while
+ * x is staged, y is bf16: what the bit-stream matvec does); packed words below 2 GiB, 512 x K activations below 1 GiB.
+ * QLLM_ERR_UNSUPPORTED: M < 17 (qllm_linear_forward serves those), M > 512, another layout, shape or alignment, QLLM_BITPANEL = 0 --
+ * the message names the alternative (qllm_dequant + a GEMM).  QLLM_ERR_INVALID: NULL x / y, w->g_idx set (act-order: call it on the
+ * row-sorted copy with a qllm_gather_columns copy of x).  Every error is raised before any device work.
+ * Numerics: the strips' unrounded-W contract -- exact integers q - z (fp16 zero points: the reference's one fp16 rounding of q - z)
+ * into the matrix cores, one fp32 y += s_g * acc_g per group, y rounded once; deterministic with and without a split.
+ * Workspace: qllm_bitpanel_workspace_bytes(w, M) = the 16 KB counter page every route shares (qllm_workspace_init; left zero after
+ * every call) + the fp32 partial panels of the split.  NULL, misaligned (256 bytes) or too small: no K split, the call is still
+ * served.  No host synchronisation; hipGraph-capturable.  Not built: a grouped (sibling) form, M > 512.
+ * Knobs (qllm_set_knob): QLLM_BITPANEL 0|1; QLLM_BITPANEL_LDS 0|1 picks the kernel's ingest of the packed words (0, the default: straight
+ * into registers; 1: staged through LDS; same bits either way, A/B in profiles/bitpanel.md); QLLM_BITPANEL_MAX_M 17..512 is read by CALLERS that route by row count (the Python
+ * modules: the largest row count they send here) -- the entry itself always takes up to 512 rows.  QLLM_BITPANEL_MAX_M_DEFAULT is what
+ * such callers use while the knob is unset (0 would mean they do not call the entry at all): the largest measured row count at which
+ * the entry is at least 5 % faster than qllm_dequant + a dense GEMM on every shape and width of profiles/bitpanel.md (256: 1.07x at
+ * worst; at 512 rows it loses on 4096 x 11008 layers, 0.79-0.86x).
+ * ABI: the three symbols are ADDITIVE within ABI 7 (QLLM_ABI_VERSION is unchanged, as for qllm_linear_forward_permuted and the
+ * quantizer entries before them): an integrator that may meet an older library of the same ABI number probes for them by symbol.
+ * Replaces, for these calls, the dequantise-then-matmul forward of quant_linear_gptq.py:81-85. */
+#define QLLM_BITPANEL_MAX_M_DEFAULT 256
+int qllm_linear_forward_bitpanel(const qllm_weight_t *w, const void *x, void *y, int32_t M, int32_t act_dtype, void *workspace,
+                                 size_t workspace_bytes, void *stream);
+size_t qllm_bitpanel_workspace_bytes(const qllm_weight_t *w, int32_t M);
+/* The geometry that call would launch, as text: "bitpanel bits=5 cols=64 row_tiles=4 row_blocks=1 split_k=4", or "unsupported (...)".
+ * Pure host code (pointers are tested for NULL / alignment only); have_workspace = 0: the call without a workspace (no split). */
+int qllm_bitpanel_describe(const qllm_weight_t *w, int32_t M, int32_t have_workspace, char *buf, size_t buflen);
 
 /* ---- HQQ quantizer (ABI 7) ---------------------------------------------------------------------------------------------------------- */
 /* W[N,K] (fp16 / bf16 / fp32 by w_dtype, row-major, 16-byte aligned) -> the HQQ layer buffers: qweight i32 [K*bits/32][N], scales f16

@@ -446,6 +446,68 @@ int qllm_linear_forward_permuted(const qllm_weight_t *w, const int32_t *perm_k, 
   return run_bitgemv(w, y, x, M, act_dtype, workspace, workspace_bytes, (hipStream_t)stream, perm_k);
 }
 
+// why qllm_linear_forward_bitpanel does not serve (w, M): the status, with the text in qllm_last_error(); QLLM_OK: served
+static int bitpanel_check(const qllm_weight_t *w, int M) {
+  static const char kInstead[] = "use qllm_dequant + a GEMM";
+  if (w->g_idx) return set_error(QLLM_ERR_INVALID, "qllm_linear_forward_bitpanel takes a plain layer (g_idx must be NULL: sort the rows by group and gather x with qllm_gather_columns)");
+  if (!knob("QLLM_BITPANEL", 1)) return set_error(QLLM_ERR_UNSUPPORTED, "QLLM_BITPANEL is off; %s", kInstead);
+  if (M < kBitPanelMinM) return set_error(QLLM_ERR_UNSUPPORTED, "the mid-batch kernel serves %d..%d rows (got M=%d); call qllm_linear_forward, or %s", kBitPanelMinM, kBitPanelMaxM, M, kInstead);
+  if (M > kBitPanelMaxM) return set_error(QLLM_ERR_UNSUPPORTED, "the mid-batch kernel serves %d..%d rows (got M=%d); %s", kBitPanelMinM, kBitPanelMaxM, M, kInstead);
+  if (const char *why = bitpanel_refusal(*w))
+    return set_error(QLLM_ERR_UNSUPPORTED, "the mid-batch kernel: %s (got bits=%d K=%d N=%d g=%d layout=%d); %s", why, w->bits, w->K, w->N, w->group_size, w->layout, kInstead);
+  return QLLM_OK;
+}
+
+int qllm_linear_forward_bitpanel(const qllm_weight_t *w, const void *x, void *y, int32_t M, int32_t act_dtype, void *workspace,
+                                 size_t workspace_bytes, void *stream) {
+  clear_error();
+  int rc = validate_weight(w);
+  if (rc) return rc;
+  rc = check_io(x, y, M, act_dtype);
+  if (rc) return rc;
+  rc = bitpanel_check(w, M);
+  if (rc) return rc;
+  const BitPanelGeom g = bitpanel_geometry(*w, M, usable_ws(workspace, workspace_bytes));
+  BitPanelParams p;
+  fill_call(p, *w, x, M, act_dtype);
+  fill_layer(p, *w, y);
+  p.K = w->K;
+  p.N = w->N;
+  p.group_size = w->group_size;
+  p.bits = w->bits;
+  p.mt = g.mt;
+  p.row_blocks = g.row_blocks;
+  p.split_k = g.split_k;
+  p.chunk = g.chunk;
+  p.n_panels = g.n_panels;
+  if (g.split_k > 1) carve(workspace, &p.counters, &p.slabs);
+  return launch_bitpanel(p, g, (hipStream_t)stream);
+}
+
+size_t qllm_bitpanel_workspace_bytes(const qllm_weight_t *w, int32_t M) {
+  if (!w || validate_weight(w) || M < kBitPanelMinM || M > kBitPanelMaxM || w->g_idx || bitpanel_refusal(*w)) {
+    clear_error();
+    return kCounterBytes;
+  }
+  return kCounterBytes + bitpanel_geometry(*w, M, SIZE_MAX).slab_bytes;
+}
+
+int qllm_bitpanel_describe(const qllm_weight_t *w, int32_t M, int32_t have_workspace, char *buf, size_t buflen) {
+  clear_error();
+  if (!buf || buflen == 0) return set_error(QLLM_ERR_INVALID, "buf must not be NULL");
+  int rc = validate_weight(w);
+  if (rc) return rc;
+  if (M <= 0) return set_error(QLLM_ERR_INVALID, "M must be >= 1 (got %d)", M);
+  if (bitpanel_check(w, M)) {
+    snprintf(buf, buflen, "unsupported (%s)", last_error_text());
+    clear_error();
+    return QLLM_OK;
+  }
+  const BitPanelGeom g = bitpanel_geometry(*w, M, have_workspace ? SIZE_MAX : 0);
+  snprintf(buf, buflen, "bitpanel bits=%d cols=64 row_tiles=%d row_blocks=%d split_k=%d", w->bits, g.mt, g.row_blocks, g.split_k);
+  return QLLM_OK;
+}
+
 int qllm_convert_bf16_to_f16(const void *src, void *dst, size_t n, void *stream) {
   clear_error();
   if (!src || !dst || n % 8 != 0 || (uintptr_t)src % 16 != 0 || (uintptr_t)dst % 16 != 0)

@@ -151,6 +151,35 @@ int launch_bitgemv(const BitGemvParams &p, int bits, hipStream_t stream);
 // int32, 16-byte aligned; entries are clamped to 0..K-1)
 int launch_bitgemv_permuted(const BitGemvParams &p, const int32_t *perm, int bits, hipStream_t stream);
 
+// ---- bitpanel.hip: fused mid-batch GEMM (17..512 rows) for every width 2..8 on the row-stream layouts in place; reached through
+// qllm_linear_forward_bitpanel only (no planner route) ---------------------------------------------------------------------------------
+constexpr int kBitPanelMinM = 17, kBitPanelMaxM = 512;
+struct BitPanelParams {
+  const void *x;
+  const uint32_t *qweight;
+  const half_t *scales;
+  const void *qzeros;
+  const half_t *bias;
+  void *y;
+  float *slabs;   // K-split: [panel x row block][split_k][4 waves x row tiles x 4 x 64] fp32 partial panels
+  int *counters;  // K-split: one arrival counter per (panel, row block) (zero before and after the launch)
+  int M, K, N, group_size, zero_kind, add_zero_bias, act_bf16;
+  int bits, mt, row_blocks, split_k, chunk, n_panels;  // the BitPanelGeom of the call
+};
+struct BitPanelGeom {
+  int mt;          // row tiles of 16 per block: 2, 4 or 8
+  int row_blocks;  // ceil(M / 128)
+  int n_panels;    // ceil(N / 64)
+  int split_k;     // blocks along K per (panel, row block)
+  int chunk;       // units (32 k) per split: even, whole groups where the group size allows
+  int grid;
+  int lds_words;   // 1: the packed words are staged through LDS (QLLM_BITPANEL_LDS), 0: loaded straight into registers
+  size_t lds, slab_bytes;
+};
+const char *bitpanel_refusal(const qllm_weight_t &w);  // NULL: served (for 17..512 rows)
+BitPanelGeom bitpanel_geometry(const qllm_weight_t &w, int M, size_t ws_bytes);
+int launch_bitpanel(const BitPanelParams &p, const BitPanelGeom &g, hipStream_t stream);
+
 // ---- comm.hip: staging buffer of one rank = [2 parities][world][slot_bytes] payload | this control block ----------------------------
 constexpr int kCommMaxWorld = 16;
 struct CommCtl {

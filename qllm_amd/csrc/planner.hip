@@ -35,6 +35,10 @@ static Settable kSettable[] = {
     {"QLLM_SKINNY_MAX_M", 0, 64, 0, 0},        // rows up to which the split-K decode kernel serves the reference layouts in place
     {"QLLM_STRIP_MIN", 0, 1 << 20, 0, 0},      // fewest 16-column strips the full-K strip kernels take (0: never)
     {"QLLM_BITGEMV", 0, 1, 0, 0},              // 0: 2 / 5 / 6 / 7 / 8-bit decode calls refused (callers then dequantise + GEMM: the reference's branch)
+    // (no route: the two knobs of qllm_linear_forward_bitpanel, bitpanel.hip)
+    {"QLLM_BITPANEL", 0, 1, 0, 0},             // 0: the mid-batch entry refuses every call
+    {"QLLM_BITPANEL_LDS", 0, 1, 0, 0},         // 1: that kernel stages the packed words through LDS (the ingest that lost the A/B: profiles/bitpanel.md)
+    {"QLLM_BITPANEL_MAX_M", 17, 512, 0, 0},    // read by callers that route by rows (the Python modules): the most rows they send to that entry
 };
 int g_knob_overrides = 0;
 Settable *find_knob(const char *name) {

@@ -22,7 +22,7 @@ def _tkey(t):
 
 
 # derived, pointer-holding state (ctypes descriptors, shadows, sibling groups): rebuilt on demand, never copied or pickled
-_DERIVED = ("_desc", "_desc_key", "_desc_keep", "_native", "_native_key", "_ao", "_ao_key", "_perm", "_siblings")
+_DERIVED = ("_desc", "_desc_key", "_desc_keep", "_native", "_native_key", "_ao", "_ao_key", "_ao_panel_refused", "_perm", "_siblings")
 # (a released module is materialised before it is pickled / deep-copied: see __getstate__)
 
 
@@ -238,12 +238,28 @@ class HipForwardMixin:
                 w = self._descriptor(act_order_g_idx, add_zero_bias)
                 y = ops.linear_forward(w, x2d)
         except ops.QllmUnsupported:
-            # e.g. 3/5/6/7/8-bit at prefill sizes: dequantise with the library kernel, then a plain library GEMM
-            wt = ops.dequant(w, x.device, torch.float16)
-            y = torch.matmul(x2d, wt.to(x2d.dtype))
-            if self.bias is not None:
-                y = y + self.bias.to(y.dtype)
+            # 2/5/6/7/8-bit layers (and in-place 3/4-bit ones of ragged width) at 17 .. QLLM_BITPANEL_MAX_M rows: the fused mid-batch
+            # kernel, an entry of its own (csrc/bitpanel.hip; bias included)
+            y = self._bitpanel_linear(w, x2d, act_order_g_idx)
+            if y is None:
+                # e.g. 3/5/6/7/8-bit at prefill sizes: dequantise with the library kernel, then a plain library GEMM
+                wt = ops.dequant(w, x.device, torch.float16)
+                y = torch.matmul(x2d, wt.to(x2d.dtype))
+                if self.bias is not None:
+                    y = y + self.bias.to(y.dtype)
         return y.reshape(x.shape[:-1] + (self.outfeatures,))
+
+    @staticmethod
+    def _bitpanel_linear(w, x2d, act_order_g_idx=None):
+        """`ops.linear_forward_bitpanel` for a call no planner route serves, or None: act-order descriptors, other layouts, other row
+        counts, other activation types and the kernel's own refusal all leave the call to dequant + GEMM, exactly as before."""
+        if (act_order_g_idx is not None or w.layout not in (ops.LAYOUTS["GPTQ"], ops.LAYOUTS["HQQ"])
+                or x2d.dtype not in (torch.float16, torch.bfloat16) or not 17 <= x2d.shape[0] <= ops.bitpanel_max_m()):
+            return None
+        try:
+            return ops.linear_forward_bitpanel(w, x2d)
+        except ops.QllmUnsupported:
+            return None
 
 
 def export_module_hooks(cls):

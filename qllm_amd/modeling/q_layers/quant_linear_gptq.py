@@ -41,6 +41,11 @@ def _gathered(x: torch.Tensor, perm: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _ops():
+    from ... import ops
+    return ops
+
+
 @export_module_hooks
 class QuantLinearGPTQ(nn.Module, CompressWeight, HipForwardMixin):
     """Buffers (state-dict compatible with the reference / AutoGPTQ-style checkpoints):
@@ -152,6 +157,7 @@ class QuantLinearGPTQ(nn.Module, CompressWeight, HipForwardMixin):
     # fallback for more than 16 rows read; releasing it is not done here).
     _ao = None
     _ao_key = None
+    _ao_panel_refused = None   # the _ao_key of the copy the mid-batch kernel (ops.linear_forward_bitpanel) has refused
 
     def _ao_one_launch(self, rows: int) -> bool:
         """Whether `rows` rows go through the gathering matvec (one launch) or through gather_columns + the plain matvec on the same
@@ -163,7 +169,7 @@ class QuantLinearGPTQ(nn.Module, CompressWeight, HipForwardMixin):
             return False
         return rows <= 2
 
-    def _ao_descriptor(self, add_zero_bias: int):
+    def _ao_descriptor(self, add_zero_bias: int, mid_batch: bool = False):
         """(plain descriptor of the row-sorted copy, perm) for the fused act-order decode, built once and cached on the buffers'
         identity and version; None for 3- / 4-bit layers (native path), non-uniform groups, QLLM_ACTORDER_SHADOW=0, CPU buffers,
         QLLM_BITGEMV switched off (asked BEFORE the copy is built: nothing would use it) and a layer the kernel has refused (forward
@@ -171,7 +177,7 @@ class QuantLinearGPTQ(nn.Module, CompressWeight, HipForwardMixin):
         if self.bits in (3, 4) or os.environ.get("QLLM_ACTORDER_SHADOW", "1") == "0" or not self.qweight.is_cuda:
             return None
         from ... import ops
-        if ops.get_knob("QLLM_BITGEMV") == 0:
+        if not mid_batch and ops.get_knob("QLLM_BITGEMV") == 0:   # (mid_batch: the caller has asked QLLM_BITPANEL, the knob of ITS kernel)
             return None
         key = (_tkey(self.qweight), _tkey(self.scales), _tkey(self.qzeros), _tkey(self.bias), _tkey(self.g_idx))
         if self._ao_key != key:
@@ -233,5 +239,17 @@ class QuantLinearGPTQ(nn.Module, CompressWeight, HipForwardMixin):
                         # (M <= 16 and the knob are settled above: what is left is the layer's shape, K or the group size no multiple
                         #  of 32 -- the same answer every time.  Drop the copy, keep the key: no rebuild, no exception per forward)
                         self._ao = None
+            elif x.shape[-1] <= 28672 and x.dtype in (torch.float16, torch.bfloat16) and x.numel() // x.shape[-1] <= _ops().bitpanel_max_m():
+                # the 3..16-row scheme carried upward (17 .. QLLM_BITPANEL_MAX_M rows): gather x once -- siblings share the gather --
+                # and run the fused mid-batch kernel on the row-sorted copy.  (qllm_gather_columns stops at K = 28672.)  The kernel's
+                # refusal is a matter of the layer's shape: remembered per copy, the path below runs from then on
+                ao = self._ao_descriptor(azb, mid_batch=True)
+                if ao is not None and self._ao_panel_refused != self._ao_key:
+                    from ... import ops
+                    try:
+                        y = ops.linear_forward_bitpanel(ao[0], _gathered(x, ao[1]))
+                        return y.reshape(x.shape[:-1] + (self.outfeatures,))
+                    except ops.QllmUnsupported:
+                        self._ao_panel_refused = self._ao_key
         g_idx = self.g_idx if self.act_order else None
         return self._hip_linear(x, g_idx, azb)

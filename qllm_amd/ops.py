@@ -155,6 +155,46 @@ def linear_forward_permuted(w: QllmWeight, perm: torch.Tensor, x2d: torch.Tensor
     return out
 
 
+def bitpanel_max_m() -> int:
+    """The most rows module code sends to `linear_forward_bitpanel`: the QLLM_BITPANEL_MAX_M knob, else the library's default
+    (include/qllm_mi355x.h, profiles/bitpanel.md); 0 -- the modules do not use the entry -- where that default is 0 or QLLM_BITPANEL is
+    switched off.  The entry itself takes up to 512 rows whatever this says."""
+    v = get_knob("QLLM_BITPANEL_MAX_M")
+    m = _lib.BITPANEL_MAX_M_DEFAULT if v is None else v
+    if m < 17 or get_knob("QLLM_BITPANEL") == 0:
+        return 0
+    return m
+
+
+def linear_forward_bitpanel(w: QllmWeight, x2d: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y[M,N] = x2d[M,K] . dequant(w) (+bias) through the fused mid-batch kernel (qllm_linear_forward_bitpanel, csrc/bitpanel.hip):
+    17..512 rows, GPTQ / HQQ layouts in place, 2..8 bits, no g_idx.  An entry of its own -- `linear_forward` and `plan_describe` keep
+    refusing these calls.  Raises QllmUnsupported for everything it does not serve (callers then use dequant() + matmul)."""
+    _check_x(x2d, (w,))
+    lib = _lib.load()
+    m = x2d.shape[0]
+    if out is not None:
+        _check_out(out, m, w.N, x2d)
+    elif m > 0:
+        out = torch.empty((m, w.N), dtype=x2d.dtype, device=x2d.device)
+    if m == 0:
+        return out if out is not None else torch.empty((0, w.N), dtype=x2d.dtype, device=x2d.device)
+    with torch.cuda.device(x2d.device):
+        ws = workspace(x2d.device, lib.qllm_bitpanel_workspace_bytes(C.byref(w), m))
+        rc = lib.qllm_linear_forward_bitpanel(C.byref(w), x2d.data_ptr(), out.data_ptr(), m, _act_dtype(x2d), ws.data_ptr(), ws.numel(),
+                                              _stream_ptr())
+    _lib.check(rc)
+    return out
+
+
+def bitpanel_describe(w: QllmWeight, m: int, have_workspace: bool = True) -> str:
+    """The geometry `linear_forward_bitpanel` would launch for m rows ("bitpanel bits=.. cols=64 row_tiles=.. row_blocks=.. split_k=.."),
+    or "unsupported (...)".  Pure host code."""
+    buf = C.create_string_buffer(512)
+    _lib.check(_lib.load().qllm_bitpanel_describe(C.byref(w), int(m), 1 if have_workspace else 0, buf, 512))
+    return buf.value.decode()
+
+
 _LAST_CONVERT: dict = {}
 
 
@@ -599,6 +639,6 @@ def unpack_native(w: QllmWeight, keep, layout: str):
     return qweight, scales, qzeros
 
 
-__all__ = ["make_weight", "linear_forward", "linear_forward_grouped", "linear_forward_permuted", "linear_forward_shared", "dequant", "gather_columns", "unpack_qweight", "pack_qweight",
+__all__ = ["make_weight", "linear_forward", "linear_forward_grouped", "linear_forward_permuted", "linear_forward_bitpanel", "bitpanel_describe", "linear_forward_shared", "dequant", "gather_columns", "unpack_qweight", "pack_qweight",
            "workspace", "QllmUnsupported", "LAYOUTS", "plan_describe", "repack_native", "unpack_native", "hqq_quantize", "gptq_quantize",
            "gptq_quantize_static", "awq_quantize", "awq_clip_search"]
