@@ -122,7 +122,8 @@ int qllm_is_lab_build(void);
  * other threads: set them before serving.  Settable names (values outside the range every built kernel covers are refused):
  *   QLLM_STRIP1 0|1|2, QLLM_STRIP1_MAX_M 1..4, QLLM_STRIP1_3BIT 0|1, QLLM_PANEL 0|1, QLLM_PANEL_MIN_M 17..129, QLLM_PANEL_GROUP_MIN_M 17..129, QLLM_GEMM2 0|1, QLLM_GEMM3 0|1,
  *   QLLM_GEMM2_MIN_M >= 33, QLLM_GEMM3_MIN_M >= 0 (0: the measured 384 / 768 line), QLLM_GEMM2_SPLITK 0|1, QLLM_GEMM3_TAIL 0|1, QLLM_GEMM3_BF16 0|1, QLLM_GEMM3_GROUP 0|1,
- *   QLLM_SKINNY_MAX_M 0..64, QLLM_STRIP_MIN >= 0, QLLM_BITGEMV 0|1, QLLM_BITPANEL 0|1, QLLM_BITPANEL_LDS 0|1, QLLM_BITPANEL_MAX_M 17..512 (the last three: qllm_linear_forward_bitpanel, no route).
+ *   QLLM_SKINNY_MAX_M 0..64, QLLM_STRIP_MIN >= 0, QLLM_BITGEMV 0|1, QLLM_BITPANEL 0|1, QLLM_BITPANEL_LDS 0|1, QLLM_BITPANEL_MAX_M 17..512 (the last three: qllm_linear_forward_bitpanel, no route),
+ *   QLLM_BITGROUP 0|1, QLLM_BITGROUP_MAX_M 0..16 (qllm_linear_forward_bitgroup, no route).
  * qllm_plan_describe() reflects them (it asks the same decision functions the forward calls execute).  QLLM_ERR_INVALID for any other name. */
 int qllm_set_knob(const char *name, int32_t value);
 int qllm_get_knob(const char *name, int32_t *value, int32_t *is_set);
@@ -298,7 +299,8 @@ int qllm_linear_forward_permuted(const qllm_weight_t *w, const int32_t *perm_k, 
  * into the matrix cores, one fp32 y += s_g * acc_g per group, y rounded once; deterministic with and without a split.
  * Workspace: qllm_bitpanel_workspace_bytes(w, M) = the 16 KB counter page every route shares (qllm_workspace_init; left zero after
  * every call) + the fp32 partial panels of the split.  NULL, misaligned (256 bytes) or too small: no K split, the call is still
- * served.  No host synchronisation; hipGraph-capturable.  Not built: a grouped (sibling) form, M > 512.
+ * served.  No host synchronisation; hipGraph-capturable.  Not built: a grouped (sibling) form of THIS kernel (the decode sizes have one:
+ * qllm_linear_forward_bitgroup below), M > 512.
  * Knobs (qllm_set_knob): QLLM_BITPANEL 0|1; QLLM_BITPANEL_LDS 0|1 picks the kernel's ingest of the packed words (0, the default: straight
  * into registers; 1: staged through LDS; same bits either way, A/B in profiles/bitpanel.md); QLLM_BITPANEL_MAX_M 17..512 is read by CALLERS that route by row count (the Python
  * modules: the largest row count they send here) -- the entry itself always takes up to 512 rows.  QLLM_BITPANEL_MAX_M_DEFAULT is what
@@ -315,6 +317,37 @@ size_t qllm_bitpanel_workspace_bytes(const qllm_weight_t *w, int32_t M);
 /* The geometry that call would launch, as text: "bitpanel bits=5 cols=64 row_tiles=4 row_blocks=1 split_k=4", or "unsupported (...)".
  * Pure host code (pointers are tested for NULL / alignment only); have_workspace = 0: the call without a workspace (no split). */
 int qllm_bitpanel_describe(const qllm_weight_t *w, int32_t M, int32_t have_workspace, char *buf, size_t buflen);
+
+/* y_i[M,N_i] = x[M,K] . dequant(w_i) (+ bias_i) for 1..4 layers that read the SAME activations (q/k/v, gate/up) at DECODE sizes,
+ * 1 <= M <= 16, in ONE launch of the bit-stream matvec (csrc/bitgemv_group.hip: the kernel body of csrc/bitgemv.hip; the members' blocks
+ * follow one another, widest member first).  The grouped form of the widths qllm_linear_forward_grouped refuses -- 2, 5, 6, 7, 8 bits
+ * (3 / 4-bit row-stream layers are taken too).  An ADDITIVE entry: the planner does not know it -- qllm_linear_forward_grouped,
+ * qllm_plan_describe and qllm_workspace_bytes* answer as before.  n_weights == 1 is a plain qllm_linear_forward.
+ * The contract: y_i is BIT-IDENTICAL to qllm_linear_forward(&w[i], x, ...) called with that layer's own workspace.  Every member keeps
+ * the K split of its own single launch and has its own counter and slab range of the one workspace; the group is not split as one wide
+ * layer.  Results never depend on which layers were grouped.
+ * Served: every member a call qllm_linear_forward hands to that matvec (GPTQ / HQQ layouts, bits 2..8, K % 32 == 0, group_size % 32 ==
+ * 0, HQQ: even N); packed (with add_zero_bias), NULL or fp16 zero points and the bias may differ per member; fp16 or bf16 activations.
+ * QLLM_ERR_INVALID: NULL x / y[i], n_weights outside 1..4, members that disagree on K, bits, group size, layout family or add_zero_bias,
+ * a g_idx.  QLLM_ERR_UNSUPPORTED: M > 16, another layout or shape, QLLM_BITGROUP = 0 -- the message names the alternative
+ * (qllm_linear_forward layer by layer).  Every error is raised before any device work.
+ * Workspace: qllm_bitgroup_workspace_bytes(w, n_weights, M) = the 16 KB counter page every route shares (qllm_workspace_init; left zero
+ * after every call) + sum_i split_i M N_i 4 bytes of fp32 slabs.  NULL, misaligned (256 bytes), too small for ALL members' slabs, or
+ * more than 4096 column blocks of 32 in the group: NO member splits -- the call is still served and equals the single calls made
+ * without a workspace.  No host synchronisation; hipGraph-capturable.  Not built: act-order members, groups mixing widths.
+ * Knobs (qllm_set_knob): QLLM_BITGROUP 0|1; QLLM_BITGROUP_MAX_M 0..16 is read by CALLERS that route by row count (the Python modules'
+ * sibling groups: the largest row count they send here, 0: never) -- the entry itself always takes up to 16 rows.
+ * QLLM_BITGROUP_MAX_M_DEFAULT is what such callers use while the knob is unset: the largest row count up to which the grouped launch was
+ * not slower than the member launches, by more than the spread of repeated measurements, in any cell of profiles/bitgemv_group.md.
+ * ABI: three ADDITIVE symbols within ABI 7: probe for them by symbol.  No reference counterpart (the reference runs one module per
+ * nn.Linear, qllm/utils/modelutils.py:161-181). */
+#define QLLM_BITGROUP_MAX_M_DEFAULT 16
+int qllm_linear_forward_bitgroup(const qllm_weight_t *w, void *const *y, int32_t n_weights, const void *x, int32_t M, int32_t act_dtype,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+size_t qllm_bitgroup_workspace_bytes(const qllm_weight_t *w, int32_t n_weights, int32_t M);
+/* The geometry that call would launch, as text: "bitgroup bits=8 cols=32 layers=3 blocks=520 split_k=4,4,4" (split_k in the caller's
+ * order), or "unsupported (...)".  Pure host code; have_workspace = 0: the call without a workspace (no member splits). */
+int qllm_bitgroup_describe(const qllm_weight_t *w, int32_t n_weights, int32_t M, int32_t have_workspace, char *buf, size_t buflen);
 
 /* ---- HQQ quantizer (ABI 7) ---------------------------------------------------------------------------------------------------------- */
 /* W[N,K] (fp16 / bf16 / fp32 by w_dtype, row-major, 16-byte aligned) -> the HQQ layer buffers: qweight i32 [K*bits/32][N], scales f16

@@ -18,6 +18,7 @@ LAYOUT_GPTQ, LAYOUT_AWQ_GEMM, LAYOUT_HQQ, LAYOUT_NATIVE, LAYOUT_NATIVE_F16Z = 0,
 DT_F16, DT_BF16, DT_F16_IN_BF16_OUT, DT_F32 = 0, 1, 2, 3
 ABI_VERSION = 7
 BITPANEL_MAX_M_DEFAULT = 256   # QLLM_BITPANEL_MAX_M_DEFAULT of include/qllm_mi355x.h: the measured line of profiles/bitpanel.md (0: modules do not route)
+BITGROUP_MAX_M_DEFAULT = 16    # QLLM_BITGROUP_MAX_M_DEFAULT of include/qllm_mi355x.h: the measured line of profiles/bitgemv_group.md (0: sibling groups do not route)
 
 EXPORTS = (
     "qllm_abi_version", "qllm_is_lab_build", "qllm_last_error", "qllm_device_info", "qllm_workspace_bytes", "qllm_workspace_bytes_act", "qllm_workspace_init",
@@ -31,6 +32,7 @@ EXPORTS = (
     "qllm_gptq_quantize_static",
     "qllm_linear_forward_permuted",
     "qllm_linear_forward_bitpanel", "qllm_bitpanel_workspace_bytes", "qllm_bitpanel_describe",
+    "qllm_linear_forward_bitgroup", "qllm_bitgroup_workspace_bytes", "qllm_bitgroup_describe",
     "qllm_awq_clip_search_workspace_bytes", "qllm_awq_clip_search", "qllm_awq_quantize",
 )
 
@@ -133,6 +135,12 @@ def _declare(lib):
     lib.qllm_bitpanel_workspace_bytes.argtypes = [wp, i32]
     lib.qllm_bitpanel_describe.restype = C.c_int
     lib.qllm_bitpanel_describe.argtypes = [wp, i32, i32, C.c_char_p, sz]
+    lib.qllm_linear_forward_bitgroup.restype = C.c_int
+    lib.qllm_linear_forward_bitgroup.argtypes = [wp, C.POINTER(vp), i32, vp, i32, i32, vp, sz, vp]
+    lib.qllm_bitgroup_workspace_bytes.restype = sz
+    lib.qllm_bitgroup_workspace_bytes.argtypes = [wp, i32, i32]
+    lib.qllm_bitgroup_describe.restype = C.c_int
+    lib.qllm_bitgroup_describe.argtypes = [wp, i32, i32, i32, C.c_char_p, sz]
     lib.qllm_plan_describe.restype = C.c_int
     lib.qllm_plan_describe.argtypes = [wp, i32, i32, i32, C.c_char_p, sz]
     lib.qllm_debug_timeline.restype = C.c_int

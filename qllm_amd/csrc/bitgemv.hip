@@ -29,7 +29,7 @@ namespace bg {
 
 template <int BITS, int MT>
 __global__ __launch_bounds__(kNW * 64) void bitgemv_kernel(const BitGemvParams p) {
-  bitgemv_body<BITS, MT, false>(p, nullptr);
+  bitgemv_body<BITS, MT, false>(p, nullptr, blockIdx.x);
 }
 
 template <int BITS>

@@ -12,7 +12,7 @@ namespace bg {
 
 template <int BITS, int MT>
 __global__ __launch_bounds__(kNW * 64) void bitgemv_ao_kernel(const BitGemvParams p, const int32_t *__restrict__ perm) {
-  bitgemv_body<BITS, MT, true>(p, perm);
+  bitgemv_body<BITS, MT, true>(p, perm, blockIdx.x);
 }
 
 template <int BITS>

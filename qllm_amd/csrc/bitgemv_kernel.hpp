@@ -1,6 +1,6 @@
-// The bit-stream matvec's kernel body, shared by its two translation units: bitgemv.hip (the decomposition is described there) and
-// bitgemv_ao.hip (the gathering form for act-order layers).  Each of them instantiates 7 widths x 5 row tiles under a kernel name of
-// its own.
+// The bit-stream matvec's kernel body, shared by its three translation units: bitgemv.hip (the decomposition is described there),
+// bitgemv_ao.hip (the gathering form for act-order layers) and bitgemv_group.hip (up to four layers sharing x in one launch).  Each of
+// them instantiates 7 widths x 5 row tiles under a kernel name of its own.
 #pragma once
 #include "kernels.hpp"
 
@@ -90,9 +90,10 @@ __device__ __forceinline__ void quad_dot(const uint32_t *w, const uint32_t *xs_u
 
 // The kernel body of bitgemv.hip (GATHER = false: x as it is) and bitgemv_ao.hip (GATHER = true: x[:, perm], an act-order layer served
 // from its row-sorted copy).  The two differ in the staging pass alone -- where a thread's 16 activations come from; the LDS image, the
-// order of every sum and hence the result are those of the plain kernel run on a gathered copy of x.
+// order of every sum and hence the result are those of the plain kernel run on a gathered copy of x.  `bid`: the block's id among the
+// blocks of THIS layer -- blockIdx.x in both of them; bitgemv_group.hip, whose launch carries several layers, passes a local one.
 template <int BITS, int MT, bool GATHER>
-__device__ __forceinline__ void bitgemv_body(const BitGemvParams p, const int32_t *__restrict__ perm) {
+__device__ __forceinline__ void bitgemv_body(const BitGemvParams p, const int32_t *__restrict__ perm, const uint32_t bid) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // (the gathering form of 7 bits x 16 rows does not fit two units' words next to its 16 indices and activations -- 256 registers and
   //  27 spilled, against 212 of the plain kernel: it keeps ONE unit in flight (157).  A lane walks its units in the same order for every
@@ -101,7 +102,7 @@ __device__ __forceinline__ void bitgemv_body(const BitGemvParams p, const int32_
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int col = lane % kCols, slot = wave * kPar + lane / kCols;
   const int nbc = p.n_col_blocks;
-  const int j = blockIdx.x % nbc, kb = blockIdx.x / nbc;
+  const int j = bid % nbc, kb = bid / nbc;
   // block id -> column block: consecutive ids go round the 8 XCDs, so ids j and j + 8 run on one XCD back to back -- give them the two
   // 64-byte halves of one 128-byte line of the word rows (whole multiples of 16 column blocks only; else the identity)
   const int nb = (kCols == 16 && nbc % 16 == 0) ? 2 * (((j >> 3) >> 1) * 8 + (j & 7)) + ((j >> 3) & 1) : j;

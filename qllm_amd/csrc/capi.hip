@@ -508,6 +508,91 @@ int qllm_bitpanel_describe(const qllm_weight_t *w, int32_t M, int32_t have_works
   return QLLM_OK;
 }
 
+// why qllm_linear_forward_bitgroup does not serve (w[0..n), M): the status -- QLLM_ERR_INVALID for arguments no call takes,
+// QLLM_ERR_UNSUPPORTED for calls this kernel does not take --, with the text in qllm_last_error(); QLLM_OK: served
+static int bitgroup_check(const qllm_weight_t *w, int n, int M) {
+  static const char kInstead[] = "call qllm_linear_forward layer by layer";
+  if (!w) return set_error(QLLM_ERR_INVALID, "w / y arrays must not be NULL");
+  if (n < 1 || n > kBitGroupMaxLayers) return set_error(QLLM_ERR_INVALID, "qllm_linear_forward_bitgroup: n_weights must be 1..%d (got %d)", kBitGroupMaxLayers, n);
+  for (int i = 0; i < n; ++i)
+    if (int rc = validate_weight(&w[i])) return rc;
+  if (M <= 0) return set_error(QLLM_ERR_INVALID, "M must be >= 1 (got %d)", M);
+  auto family = [](const qllm_weight_t &l) { return is_native(l) ? 2 : (l.layout == QLLM_LAYOUT_AWQ_GEMM ? 1 : 0); };
+  for (int i = 0; i < n; ++i) {
+    if (w[i].g_idx) return set_error(QLLM_ERR_INVALID, "qllm_linear_forward_bitgroup takes plain layers (layer %d: g_idx must be NULL); %s", i, kInstead);
+    if (w[i].K != w[0].K || w[i].bits != w[0].bits || w[i].group_size != w[0].group_size || family(w[i]) != family(w[0]) ||
+        w[i].add_zero_bias != w[0].add_zero_bias)
+      return set_error(QLLM_ERR_INVALID, "qllm_linear_forward_bitgroup: layers must agree on in_features, bits, group size, layout family and add_zero_bias (layer %d differs)", i);
+  }
+  if (!knob("QLLM_BITGROUP", 1)) return set_error(QLLM_ERR_UNSUPPORTED, "QLLM_BITGROUP is off; %s", kInstead);
+  if (M > kBitGemvMaxM) return set_error(QLLM_ERR_UNSUPPORTED, "the grouped bit-stream matvec serves 1..%d rows (got M=%d); %s", kBitGemvMaxM, M, kInstead);
+  for (int i = 0; i < n; ++i)
+    if (!bitgemv_ok(w[i], M))
+      return set_error(QLLM_ERR_UNSUPPORTED, "the grouped bit-stream matvec serves GPTQ / HQQ row-stream layers of 2..8 bits with K %% 32 == 0 and group_size %% 32 == 0 "
+                       "(layer %d: bits=%d K=%d N=%d g=%d layout=%d); %s", i, w[i].bits, w[i].K, w[i].N, w[i].group_size, w[i].layout, kInstead);
+  return QLLM_OK;
+}
+
+int qllm_linear_forward_bitgroup(const qllm_weight_t *w, void *const *y, int32_t n_weights, const void *x, int32_t M, int32_t act_dtype,
+                                 void *workspace, size_t workspace_bytes, void *stream) {
+  clear_error();
+  if (!y) return set_error(QLLM_ERR_INVALID, "w / y arrays must not be NULL");
+  if (int rc = bitgroup_check(w, n_weights, M)) return rc;
+  for (int i = 0; i < n_weights; ++i)
+    if (int rc = check_io(x, y[i], M, act_dtype)) return rc;
+  const BitGroupGeom g = bitgemv_group_geometry(w, n_weights, M, usable_ws(workspace, workspace_bytes));
+  BitGemvGroupParams gp;
+  memset(&gp, 0, sizeof(gp));
+  gp.x = x;
+  gp.M = M;
+  gp.K = w[0].K;
+  gp.group_size = w[0].group_size;
+  gp.act_bf16 = (act_dtype == QLLM_BF16);
+  gp.n_prob = n_weights;
+  for (int k = 0; k < n_weights; ++k) {  // launch order: widest first
+    const int i = g.order[k];
+    BitGemvGroupMember &q = gp.prob[k];
+    fill_layer(q, w[i], y[i]);
+    q.N = w[i].N;
+    q.add_zero_bias = w[i].add_zero_bias;
+    q.ksplit = g.split[i];
+    q.n_col_blocks = g.n_col_blocks[i];
+    q.chunk_units = g.chunk_units[i];
+    if (g.split[i] > 1) {  // the member's own counters and slabs, carved from the one workspace
+      q.counters = (int *)workspace + g.counter_off[i];
+      q.slabs = (float *)((char *)workspace + kCounterBytes + g.slab_off[i]);
+    }
+    gp.block_begin[k] = g.block_begin[i];
+  }
+  return launch_bitgemv_group(gp, g, w[0].bits, (hipStream_t)stream);
+}
+
+size_t qllm_bitgroup_workspace_bytes(const qllm_weight_t *w, int32_t n_weights, int32_t M) {
+  if (bitgroup_check(w, n_weights, M)) {
+    clear_error();
+    return kCounterBytes;
+  }
+  return kCounterBytes + bitgemv_group_geometry(w, n_weights, M, SIZE_MAX).slab_bytes;
+}
+
+int qllm_bitgroup_describe(const qllm_weight_t *w, int32_t n_weights, int32_t M, int32_t have_workspace, char *buf, size_t buflen) {
+  clear_error();
+  if (!buf || buflen == 0) return set_error(QLLM_ERR_INVALID, "buf must not be NULL");
+  const int rc = bitgroup_check(w, n_weights, M);
+  if (rc == QLLM_ERR_UNSUPPORTED) {
+    snprintf(buf, buflen, "unsupported (%s)", last_error_text());
+    clear_error();
+    return QLLM_OK;
+  }
+  if (rc) return rc;
+  const BitGroupGeom g = bitgemv_group_geometry(w, n_weights, M, have_workspace ? SIZE_MAX : 0);
+  char splits[64] = "";
+  size_t at = 0;
+  for (int i = 0; i < n_weights && at < sizeof(splits); ++i) at += snprintf(splits + at, sizeof(splits) - at, i ? ",%d" : "%d", g.split[i]);
+  snprintf(buf, buflen, "bitgroup bits=%d cols=%d layers=%d blocks=%d split_k=%s", w[0].bits, bitgemv_cols(), n_weights, g.grid, splits);
+  return QLLM_OK;
+}
+
 int qllm_convert_bf16_to_f16(const void *src, void *dst, size_t n, void *stream) {
   clear_error();
   if (!src || !dst || n % 8 != 0 || (uintptr_t)src % 16 != 0 || (uintptr_t)dst % 16 != 0)

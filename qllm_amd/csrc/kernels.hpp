@@ -150,6 +150,37 @@ int launch_bitgemv(const BitGemvParams &p, int bits, hipStream_t stream);
 // bitgemv_ao.hip: the same matvec on x[:, perm] -- the gather of an act-order layer's activations happens in the staging pass (perm: K
 // int32, 16-byte aligned; entries are clamped to 0..K-1)
 int launch_bitgemv_permuted(const BitGemvParams &p, const int32_t *perm, int bits, hipStream_t stream);
+// bitgemv_group.hip: up to four layers that share x (q/k/v, gate/up) in ONE launch of the same kernel body; reached through
+// qllm_linear_forward_bitgroup only (no planner route).  Every member keeps the K split, the chunking and hence the bits of its own
+// single launch; the members' blocks follow one another, widest member first.
+constexpr int kBitGroupMaxLayers = 4;
+struct BitGemvGroupMember {  // (launch order: prob[k] is the k-th widest layer)
+  const uint32_t *qweight;
+  const half_t *scales;
+  const void *qzeros;
+  const half_t *bias;
+  void *y;
+  float *slabs;   // the member's own [ksplit][M][N] range of the workspace
+  int *counters;  // the member's own range of the counter page: one per column block
+  int N, zero_kind, add_zero_bias, ksplit, n_col_blocks, chunk_units;
+};
+struct BitGemvGroupParams {
+  int block_begin[kBitGroupMaxLayers];  // first block id of every member (a prefix sum); at the head: one scalar load finds the member
+  BitGemvGroupMember prob[kBitGroupMaxLayers];
+  const void *x;
+  int M, K, group_size, act_bf16, n_prob;
+};
+struct BitGroupGeom {  // per-layer fields in the CALLER's order
+  int mt, grid;
+  int order[kBitGroupMaxLayers];        // order[k]: the caller's index of the k-th member of the launch (widest first, ties in call order)
+  int split[kBitGroupMaxLayers], n_col_blocks[kBitGroupMaxLayers], chunk_units[kBitGroupMaxLayers], block_begin[kBitGroupMaxLayers];
+  int counter_off[kBitGroupMaxLayers];  // ints from the head of the counter page
+  size_t slab_off[kBitGroupMaxLayers];  // bytes behind the counter page
+  size_t lds, slab_bytes;               // dynamic LDS (the largest member's); the slabs of all members
+};
+// ONE function for the launch, qllm_bitgroup_describe and qllm_bitgroup_workspace_bytes.  `ws_bytes`: bytes of a usable workspace (0: none)
+BitGroupGeom bitgemv_group_geometry(const qllm_weight_t *w, int n, int M, size_t ws_bytes);
+int launch_bitgemv_group(const BitGemvGroupParams &gp, const BitGroupGeom &g, int bits, hipStream_t stream);
 
 // ---- bitpanel.hip: fused mid-batch GEMM (17..512 rows) for every width 2..8 on the row-stream layouts in place; reached through
 // qllm_linear_forward_bitpanel only (no planner route) ---------------------------------------------------------------------------------

@@ -39,6 +39,9 @@ static Settable kSettable[] = {
     {"QLLM_BITPANEL", 0, 1, 0, 0},             // 0: the mid-batch entry refuses every call
     {"QLLM_BITPANEL_LDS", 0, 1, 0, 0},         // 1: that kernel stages the packed words through LDS (the ingest that lost the A/B: profiles/bitpanel.md)
     {"QLLM_BITPANEL_MAX_M", 17, 512, 0, 0},    // read by callers that route by rows (the Python modules): the most rows they send to that entry
+    // (no route: the two knobs of qllm_linear_forward_bitgroup, bitgemv_group.hip)
+    {"QLLM_BITGROUP", 0, 1, 0, 0},             // 0: the grouped bit-stream entry refuses every call
+    {"QLLM_BITGROUP_MAX_M", 0, 16, 0, 0},      // read by callers that route by rows (the Python modules): the most rows they send to that entry (0: never)
 };
 int g_knob_overrides = 0;
 Settable *find_knob(const char *name) {

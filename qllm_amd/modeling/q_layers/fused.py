@@ -4,7 +4,8 @@ decode sizes, without touching the model code or the state dict.
 The reference swaps one module per nn.Linear (qllm/utils/modelutils.py:161-181) and the HF model code calls
 `q_proj(x)`, `k_proj(x)`, `v_proj(x)` one after the other.  Here the modules stay in place (same names, same buffers); they
 additionally share a `SiblingGroup`.  The first sibling called with a tensor `x` launches the grouped kernel for ALL
-siblings (`qllm_linear_forward_grouped`: one launch, x read once, 2-3x more bytes in flight per launch) and parks the others'
+siblings (`qllm_linear_forward_grouped`, at 2 / 5 / 6 / 7 / 8 bits `qllm_linear_forward_bitgroup`: one launch, x read once, 2-3x more
+bytes in flight per launch) and parks the others'
 outputs; when the model then calls the next sibling with the very same tensor object (and the tensor was not modified in
 between: `x._version`), it gets the parked output.  Anything else -- another tensor, a larger M, act-order, a shape the
 grouped kernel does not take -- falls back to the module's own single launch, so results never depend on call patterns.
@@ -21,6 +22,8 @@ from ... import ops
 from ._hip_forward import tensor_version
 
 GROUP_MAX_M = 128  # the grouped entry point serves decode and mid-batch sizes (strips to 32 rows, the panel kernel to 128)
+BITGROUP_MAX_LAYERS = 4          # members of one qllm_linear_forward_bitgroup call
+BITGROUP_BITS = (2, 5, 6, 7, 8)  # widths whose groups go to ops.linear_forward_bitgroup at decode sizes (3 / 4 bits: the planner's grouped routes)
 
 # attribute names of siblings inside one parent module (Llama / Mistral / Qwen2, OPT, Falcon-style MLPs, ...)
 SIBLING_PATTERNS = (("q_proj", "k_proj", "v_proj"), ("gate_proj", "up_proj"), ("w1", "w3"))
@@ -94,6 +97,7 @@ class SiblingGroup:
             return None
         if (not prefill and m >= self._refused_from) or m == 0 or not x2d.is_contiguous() or not self.compatible():
             return None
+        a = self.layers[0]
         try:
             descs = []
             for l in self.layers:
@@ -104,7 +108,14 @@ class SiblingGroup:
                 else:
                     d = l.decode_descriptor(None, add_zero_bias)
                 descs.append(d)
-            outs = ops.linear_forward_grouped(descs, x2d)
+            # 2 / 5 / 6 / 7 / 8 bits at decode sizes: the grouped bit-stream matvec, an entry of its own (csrc/bitgemv_group.hip) -- every
+            # output is bit-identical to the layer's own launch.  Above its cutoff (QLLM_BITGROUP_MAX_M, profiles/bitgemv_group.md) and for
+            # act-order members: the planner's entry, which refuses these widths -- the layers then run on their own.
+            if (a.bits in BITGROUP_BITS and len(descs) <= BITGROUP_MAX_LAYERS and not any(getattr(l, "act_order", None) for l in self.layers)
+                    and 1 <= m <= ops.bitgroup_max_m()):
+                outs = ops.linear_forward_bitgroup(descs, x2d)
+            else:
+                outs = ops.linear_forward_grouped(descs, x2d)
         except ops.QllmUnsupported:
             # no grouped kernel for this many rows (wide groups above 32 rows: the layers run one by one, panel.hip): do not ask
             # again from here up -- but keep grouping the smaller batches.  (Round 4: this used to switch the group off for good,

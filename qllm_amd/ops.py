@@ -313,6 +313,50 @@ def linear_forward_grouped(ws_desc: Sequence[QllmWeight], x2d: torch.Tensor,
     return list(outs)
 
 
+def bitgroup_max_m() -> int:
+    """The most rows the sibling groups send to `linear_forward_bitgroup`: the QLLM_BITGROUP_MAX_M knob, else the library's default
+    (include/qllm_mi355x.h, profiles/bitgemv_group.md); 0: never.  The entry itself takes up to 16 rows whatever this says."""
+    v = get_knob("QLLM_BITGROUP_MAX_M")
+    return _lib.BITGROUP_MAX_M_DEFAULT if v is None else v
+
+
+def linear_forward_bitgroup(ws_desc: Sequence[QllmWeight], x2d: torch.Tensor,
+                            outs: Optional[Sequence[torch.Tensor]] = None):
+    """1..4 layers of 2..8 bits sharing x (q/k/v, gate/up) in ONE launch of the bit-stream matvec at 1..16 rows
+    (qllm_linear_forward_bitgroup, csrc/bitgemv_group.hip).  Every output is bit-identical to `linear_forward` on that layer alone.
+    An entry of its own -- `linear_forward_grouped` and `plan_describe` keep refusing these widths.  Raises QllmUnsupported for
+    everything it does not serve (callers then run the layers one by one)."""
+    _check_x(x2d, ws_desc)
+    lib = _lib.load()
+    n = len(ws_desc)
+    m = x2d.shape[0]
+    if outs is not None:
+        if len(outs) != n:
+            raise RuntimeError(f"outs must hold {n} tensors, got {len(outs)}")
+        for o, w in zip(outs, ws_desc):
+            _check_out(o, m, w.N, x2d)
+    if m == 0:
+        return list(outs) if outs is not None else [torch.empty((0, w.N), dtype=x2d.dtype, device=x2d.device) for w in ws_desc]
+    if outs is None:
+        outs = [torch.empty((m, w.N), dtype=x2d.dtype, device=x2d.device) for w in ws_desc]
+    arr = (QllmWeight * n)(*ws_desc)
+    ys = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
+    with torch.cuda.device(x2d.device):
+        wsp = workspace(x2d.device, lib.qllm_bitgroup_workspace_bytes(arr, n, m))
+        rc = lib.qllm_linear_forward_bitgroup(arr, ys, n, x2d.data_ptr(), m, _act_dtype(x2d), wsp.data_ptr(), wsp.numel(), _stream_ptr())
+    _lib.check(rc)
+    return list(outs)
+
+
+def bitgroup_describe(ws_desc: Sequence[QllmWeight], m: int, have_workspace: bool = True) -> str:
+    """The geometry `linear_forward_bitgroup` would launch for m rows ("bitgroup bits=.. cols=32 layers=.. blocks=.. split_k=a,b,c", the
+    splits in the order of `ws_desc`), or "unsupported (...)".  Pure host code."""
+    arr = (QllmWeight * len(ws_desc))(*ws_desc)
+    buf = C.create_string_buffer(512)
+    _lib.check(_lib.load().qllm_bitgroup_describe(arr, len(ws_desc), int(m), 1 if have_workspace else 0, buf, 512))
+    return buf.value.decode()
+
+
 def dequant(w: QllmWeight, device: torch.device, dtype=torch.float16, transposed: bool = False) -> torch.Tensor:
     """W[K,N] (or [N,K]) bit-identical to the reference's DequantizeLinearBlockWise / unpack()."""
     lib = _lib.load()
@@ -639,6 +683,6 @@ def unpack_native(w: QllmWeight, keep, layout: str):
     return qweight, scales, qzeros
 
 
-__all__ = ["make_weight", "linear_forward", "linear_forward_grouped", "linear_forward_permuted", "linear_forward_bitpanel", "bitpanel_describe", "linear_forward_shared", "dequant", "gather_columns", "unpack_qweight", "pack_qweight",
+__all__ = ["make_weight", "linear_forward", "linear_forward_grouped", "linear_forward_permuted", "linear_forward_bitpanel", "bitpanel_describe", "linear_forward_bitgroup", "bitgroup_describe", "linear_forward_shared", "dequant", "gather_columns", "unpack_qweight", "pack_qweight",
            "workspace", "QllmUnsupported", "LAYOUTS", "plan_describe", "repack_native", "unpack_native", "hqq_quantize", "gptq_quantize",
            "gptq_quantize_static", "awq_quantize", "awq_clip_search"]

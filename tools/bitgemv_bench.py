@@ -6,7 +6,10 @@ dense fp16 GEMM (the reference's branch (B), quant_linear_gptq.py:81-85).  Llama
 --act-order: the one-launch act-order decode (csrc/bitgemv_ao.hip) at 8 and 2 bits, M = 1 / 16 (and 7 bits, M = 16), against its
 alternatives; the table of profiles/bitgemv_actorder.md.
     python tools/bitgemv_bench.py --act-order
-    python tools/bitgemv_bench.py --act-order 2,5,8 1,2,4,8      (other widths / row counts: the table behind the module's rule)"""
+    python tools/bitgemv_bench.py --act-order 2,5,8 1,2,4,8      (other widths / row counts: the table behind the module's rule)
+--group: one grouped launch (csrc/bitgemv_group.hip) against the member launches one after the other, q/k/v, gate/up and a GQA triple;
+the table of profiles/bitgemv_group.md and the row count behind QLLM_BITGROUP_MAX_M_DEFAULT.
+    python tools/bitgemv_bench.py --group"""
 import os
 import sys
 
@@ -87,6 +90,69 @@ def act_order_leg(cases=((8, (1, 16)), (2, (1, 16)), (7, (16,))), rounds=7, wind
             torch.cuda.empty_cache()
 
 
+def group_leg(widths=(2, 5, 8), Ms=(1, 2, 4, 8, 16), rounds=5, window_ms=60.0):
+    """(a) ONE ops.linear_forward_bitgroup for the siblings; (b) their ops.linear_forward calls one after the other -- what served these
+    groups before.  Same kernel body, same splits, same bits (tests/test_bitgemv_group_gpu.py): the difference is launch boundaries
+    against how the members' blocks share the CUs.  One process, hipGraph replay over rotating copies of the group (>= 512 MiB of
+    packed weights per pass, at most 64 groups, against 256 MiB of Infinity Cache: both legs walk the same copies, and a pass has
+    evicted its own head before the next one starts).  The legs alternate round by round; every timed window is `window_ms` of
+    replays at least.  Median (min .. max) per GROUP.  spread(a) = max - min of (a)'s windows: the noise a difference has to beat."""
+    import statistics
+    sets = (("q/k/v", 4096, (4096, 4096, 4096)), ("gate/up", 4096, (11008, 11008)), ("GQA q/k/v", 4096, (4096, 1024, 1024)))
+    print("| bits | group | M | copies | geometry of (a) | (a) one launch us | (b) member launches us | (b)-(a) us | spread(a) us | (a) lost |")
+    print("|---|---|---|---|---|---|---|---|---|---|")
+    lost_at = {}
+    for bits in widths:
+        for name, K, ns in sets:
+            gbytes = sum(K * n * bits // 8 for n in ns)
+            ncopy = max(4, min(64, ((512 << 20) + gbytes - 1) // gbytes))
+            layers = [[bench.make_layer(QuantLinearGPTQ, K, n, dev, gen, bits=bits, group=128) for n in ns] for _ in range(ncopy)]
+            groups = [[l.decode_descriptor() for l in grp] for grp in layers]
+            for M in Ms:
+                x = torch.randn(M, K, device=dev, dtype=torch.float16)
+
+                def leg_a():
+                    for descs in groups:
+                        y = ops.linear_forward_bitgroup(descs, x)
+                    return y
+
+                def leg_b():
+                    for descs in groups:
+                        for w in descs:
+                            y = ops.linear_forward(w, x)
+                    return y
+
+                legs = {"a": leg_a, "b": leg_b}
+                graphs = {k: bench.capture(fn)[0] for k, fn in legs.items()}
+                iters = {k: max(3, int(window_ms / bench.time_events(gph.replay, 2, warm=1)) + 1) for k, gph in graphs.items()}
+                t = {k: [] for k in legs}
+                for r in range(rounds):
+                    for k in ("ab" if r % 2 == 0 else "ba"):
+                        t[k].append(bench.time_events(graphs[k].replay, iters[k], warm=1) / ncopy * 1e3)
+                med = {k: statistics.median(v) for k, v in t.items()}
+                spread = max(t["a"]) - min(t["a"])
+                lost = med["a"] - med["b"] > spread
+                if lost:
+                    lost_at.setdefault(M, []).append((bits, name))
+                cell = lambda k: f"{med[k]:.2f} ({min(t[k]):.2f} .. {max(t[k]):.2f})"  # noqa: E731
+                print(f"| {bits} | {name} | {M} | {ncopy} | {ops.bitgroup_describe(groups[0], M)[9:]} | {cell('a')} | {cell('b')} | "
+                      f"{med['b'] - med['a']:+.2f} | {spread:.2f} | {'yes' if lost else ''} |", flush=True)
+                del graphs
+            del layers, groups
+            torch.cuda.empty_cache()
+    best = 0
+    for M in Ms:   # the largest measured row count with no lost cell at it or below it
+        if M in lost_at:
+            break
+        best = M
+    print()
+    print(f"cells where (a) lost: {lost_at if lost_at else 'none'}")
+    print(f"largest measured row count up to which no cell lost: {best}")
+
+
+if "--group" in sys.argv:
+    group_leg()
+    sys.exit(0)
 if "--act-order" in sys.argv:
     # (--act-order BITS,.. ROWS,..: other widths and row counts, e.g. `--act-order 2,5,8 1,2,4,8` for the table behind the module's rule)
     extra = sys.argv[sys.argv.index("--act-order") + 1:]
