@@ -123,7 +123,8 @@ int qllm_is_lab_build(void);
  *   QLLM_STRIP1 0|1|2, QLLM_STRIP1_MAX_M 1..4, QLLM_STRIP1_3BIT 0|1, QLLM_PANEL 0|1, QLLM_PANEL_MIN_M 17..129, QLLM_PANEL_GROUP_MIN_M 17..129, QLLM_GEMM2 0|1, QLLM_GEMM3 0|1,
  *   QLLM_GEMM2_MIN_M >= 33, QLLM_GEMM3_MIN_M >= 0 (0: the measured 384 / 768 line), QLLM_GEMM2_SPLITK 0|1, QLLM_GEMM3_TAIL 0|1, QLLM_GEMM3_BF16 0|1, QLLM_GEMM3_GROUP 0|1,
  *   QLLM_SKINNY_MAX_M 0..64, QLLM_STRIP_MIN >= 0, QLLM_BITGEMV 0|1, QLLM_BITPANEL 0|1, QLLM_BITPANEL_LDS 0|1, QLLM_BITPANEL_MAX_M 17..512 (the last three: qllm_linear_forward_bitpanel, no route),
- *   QLLM_BITGROUP 0|1, QLLM_BITGROUP_MAX_M 0..16 (qllm_linear_forward_bitgroup, no route).
+ *   QLLM_BITGROUP 0|1, QLLM_BITGROUP_MAX_M 0..16 (qllm_linear_forward_bitgroup, no route),
+ *   QLLM_BITGEMM 0|1, QLLM_BITGEMM_MIN_M 129..65536 (qllm_linear_forward_bitgemm, no route).
  * qllm_plan_describe() reflects them (it asks the same decision functions the forward calls execute).  QLLM_ERR_INVALID for any other name. */
 int qllm_set_knob(const char *name, int32_t value);
 int qllm_get_knob(const char *name, int32_t *value, int32_t *is_set);
@@ -300,7 +301,7 @@ int qllm_linear_forward_permuted(const qllm_weight_t *w, const int32_t *perm_k, 
  * Workspace: qllm_bitpanel_workspace_bytes(w, M) = the 16 KB counter page every route shares (qllm_workspace_init; left zero after
  * every call) + the fp32 partial panels of the split.  NULL, misaligned (256 bytes) or too small: no K split, the call is still
  * served.  No host synchronisation; hipGraph-capturable.  Not built: a grouped (sibling) form of THIS kernel (the decode sizes have one:
- * qllm_linear_forward_bitgroup below), M > 512.
+ * qllm_linear_forward_bitgroup below).  M > 512: qllm_linear_forward_bitgemm below (129 rows and up).
  * Knobs (qllm_set_knob): QLLM_BITPANEL 0|1; QLLM_BITPANEL_LDS 0|1 picks the kernel's ingest of the packed words (0, the default: straight
  * into registers; 1: staged through LDS; same bits either way, A/B in profiles/bitpanel.md); QLLM_BITPANEL_MAX_M 17..512 is read by CALLERS that route by row count (the Python
  * modules: the largest row count they send here) -- the entry itself always takes up to 512 rows.  QLLM_BITPANEL_MAX_M_DEFAULT is what
@@ -317,6 +318,43 @@ size_t qllm_bitpanel_workspace_bytes(const qllm_weight_t *w, int32_t M);
 /* The geometry that call would launch, as text: "bitpanel bits=5 cols=64 row_tiles=4 row_blocks=1 split_k=4", or "unsupported (...)".
  * Pure host code (pointers are tested for NULL / alignment only); have_workspace = 0: the call without a workspace (no split). */
 int qllm_bitpanel_describe(const qllm_weight_t *w, int32_t M, int32_t have_workspace, char *buf, size_t buflen);
+
+/* y[M,N] = x[M,K] . dequant(w) (+ bias) for PREFILL calls, M >= 129, on the row-stream layouts read in place, at every width from 2 to
+ * 8 bits (csrc/bitgemm.hip: the 256 x 128 x 64 tile of the 3- / 4-bit prefill kernel -- eight matrix waves on v_mfma_f32_32x32x16_f16
+ * fed by LDS-DMA, four dequant waves that each own one column and one 32-k unit = `bits` word rows -- with split-K through the
+ * workspace).  An ADDITIVE entry: the planner does not know it -- qllm_linear_forward, qllm_plan_describe and qllm_workspace_bytes*
+ * answer as before -- and a caller that used to take qllm_dequant + a dense GEMM above qllm_linear_forward_bitpanel's rows (2 K N bytes
+ * of fp16 W written and read back on every call) may call this instead.  It also serves the in-place 3- / 4-bit layers whose N is no
+ * multiple of 128.
+ * Served: GPTQ / HQQ layouts, bits 2..8, M >= 129, K % 64 == 0, group_size % 32 == 0 (any such size: group_size == K and a ragged last
+ * group included), N % 8 == 0; packed (with add_zero_bias), NULL (symmetric) or fp16 zero points; optional bias; act_dtype QLLM_F16
+ * (fp16 x, fp16 y) or QLLM_F16_IN_BF16_OUT (fp16 x -- a bf16 caller converts once, qllm_convert_bf16_to_f16 -- and bf16 y rounded
+ * fp32 -> fp16 -> bf16, as the 4-bit prefill kernel does); x and y 16-byte aligned; M K 2 and K N bits / 8 below 2 GiB.
+ * QLLM_ERR_UNSUPPORTED: M < 129 (qllm_linear_forward_bitpanel / qllm_linear_forward serve those), QLLM_BF16 ("convert x to fp16, pass
+ * QLLM_F16_IN_BF16_OUT"), another layout, shape or alignment, QLLM_BITGEMM = 0 -- the message names the alternative.
+ * QLLM_ERR_INVALID: NULL x / y, w->g_idx set (act-order: call it on the row-sorted copy with a qllm_gather_columns copy of x), bits
+ * outside 2..8.  Every error is raised before any device work.
+ * Numerics: the prefill kernel's fp16 contract, not the strips' -- the B tile holds fp16(q s) - fp16(z s), bit for bit what
+ * qllm_dequant writes; fp32 sums; y rounded once; deterministic with and without a split.
+ * Workspace: qllm_bitgemm_workspace_bytes(w, M) = the 16 KB counter page every route shares (left zero after every call) + tiles x S
+ * fp32 partial tiles of 256 x 128.  S is the largest power of two <= 8 with tiles x S <= CUs and at least 8 k-tiles (of 64) per block.
+ * NULL, misaligned (256 bytes) or too small: S = 1, the call is still served.  No host synchronisation; hipGraph-capturable.
+ * Not built: a grouped (sibling) form, native bf16 MFMA, K % 64 != 0, N % 8 != 0, the AWQ layout.
+ * Knobs (qllm_set_knob): QLLM_BITGEMM 0|1; QLLM_BITGEMM_MIN_M 129..65536 is read by CALLERS that route by row count (the Python modules:
+ * the fewest rows they send here, above QLLM_BITPANEL_MAX_M) -- the entry itself always takes M >= 129.  QLLM_BITGEMM_MIN_M_DEFAULT is
+ * what such callers use while the knob is unset; 0 means they do not call the entry at all.  The rule (profiles/bitgemm.md): the
+ * smallest measured M >= 257 from which the entry is at least 5 % faster than qllm_dequant + a dense GEMM on every shape and width,
+ * at that M and every larger measured one; 0 if there is none or while the table is not measured.  Measured: 1.27x at worst from 257 to
+ * 2048 rows, 0.93-1.20x at 4096 -- no such M, hence 0; a deployment whose calls stay below about 2048 rows sets the knob to 257.
+ * ABI: the three symbols are ADDITIVE within ABI 7, like the bitpanel symbols.
+ * Replaces, for these calls, the dequantise-then-matmul forward of quant_linear_gptq.py:81-85. */
+#define QLLM_BITGEMM_MIN_M_DEFAULT 0
+int qllm_linear_forward_bitgemm(const qllm_weight_t *w, const void *x, void *y, int32_t M, int32_t act_dtype, void *workspace,
+                                size_t workspace_bytes, void *stream);
+size_t qllm_bitgemm_workspace_bytes(const qllm_weight_t *w, int32_t M);
+/* The geometry that call would launch, as text: "bitgemm bits=8 tile=256x128 tiles=64 split_k=4", or "unsupported (...)".
+ * Pure host code (pointers are tested for NULL / alignment only); have_workspace = 0: the call without a workspace (no split). */
+int qllm_bitgemm_describe(const qllm_weight_t *w, int32_t M, int32_t have_workspace, char *buf, size_t buflen);
 
 /* y_i[M,N_i] = x[M,K] . dequant(w_i) (+ bias_i) for 1..4 layers that read the SAME activations (q/k/v, gate/up) at DECODE sizes,
  * 1 <= M <= 16, in ONE launch of the bit-stream matvec (csrc/bitgemv_group.hip: the kernel body of csrc/bitgemv.hip; the members' blocks

@@ -18,6 +18,7 @@ LAYOUT_GPTQ, LAYOUT_AWQ_GEMM, LAYOUT_HQQ, LAYOUT_NATIVE, LAYOUT_NATIVE_F16Z = 0,
 DT_F16, DT_BF16, DT_F16_IN_BF16_OUT, DT_F32 = 0, 1, 2, 3
 ABI_VERSION = 7
 BITPANEL_MAX_M_DEFAULT = 256   # QLLM_BITPANEL_MAX_M_DEFAULT of include/qllm_mi355x.h: the measured line of profiles/bitpanel.md (0: modules do not route)
+BITGEMM_MIN_M_DEFAULT = 0      # QLLM_BITGEMM_MIN_M_DEFAULT of include/qllm_mi355x.h: the measured line of profiles/bitgemm.md (0: modules do not route)
 BITGROUP_MAX_M_DEFAULT = 16    # QLLM_BITGROUP_MAX_M_DEFAULT of include/qllm_mi355x.h: the measured line of profiles/bitgemv_group.md (0: sibling groups do not route)
 
 EXPORTS = (
@@ -33,6 +34,7 @@ EXPORTS = (
     "qllm_linear_forward_permuted",
     "qllm_linear_forward_bitpanel", "qllm_bitpanel_workspace_bytes", "qllm_bitpanel_describe",
     "qllm_linear_forward_bitgroup", "qllm_bitgroup_workspace_bytes", "qllm_bitgroup_describe",
+    "qllm_linear_forward_bitgemm", "qllm_bitgemm_workspace_bytes", "qllm_bitgemm_describe",
     "qllm_awq_clip_search_workspace_bytes", "qllm_awq_clip_search", "qllm_awq_quantize",
 )
 
@@ -135,6 +137,12 @@ def _declare(lib):
     lib.qllm_bitpanel_workspace_bytes.argtypes = [wp, i32]
     lib.qllm_bitpanel_describe.restype = C.c_int
     lib.qllm_bitpanel_describe.argtypes = [wp, i32, i32, C.c_char_p, sz]
+    lib.qllm_linear_forward_bitgemm.restype = C.c_int
+    lib.qllm_linear_forward_bitgemm.argtypes = [wp, vp, vp, i32, i32, vp, sz, vp]
+    lib.qllm_bitgemm_workspace_bytes.restype = sz
+    lib.qllm_bitgemm_workspace_bytes.argtypes = [wp, i32]
+    lib.qllm_bitgemm_describe.restype = C.c_int
+    lib.qllm_bitgemm_describe.argtypes = [wp, i32, i32, C.c_char_p, sz]
     lib.qllm_linear_forward_bitgroup.restype = C.c_int
     lib.qllm_linear_forward_bitgroup.argtypes = [wp, C.POINTER(vp), i32, vp, i32, i32, vp, sz, vp]
     lib.qllm_bitgroup_workspace_bytes.restype = sz

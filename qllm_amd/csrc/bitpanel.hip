@@ -2,7 +2,8 @@
 // qweight i32 [K / 32 * bits][N]) at every width from 2 to 8 bits -- the widths the strip-major native layout and panel.hip do not take
 // (2, 5, 6, 7, 8), and the 3- / 4-bit layers the planner refuses (ragged N).  Until now such a call wrote the whole fp16 W with
 // qllm_dequant (2 K N bytes), read it back in a dense GEMM and paid a launch boundary, where the packed words are bits / 16 of that.
-// Reached through qllm_linear_forward_bitpanel only: the planner, its routes and qllm_plan_describe do not know it.
+// Reached through qllm_linear_forward_bitpanel only: the planner, its routes and qllm_plan_describe do not know it.  (More than 512 rows --
+// and, by measurement, the row counts from which every 128-row block rebuilding its panel's fragments loses: bitgemm.hip.)
 //
 //   * block = a panel of 64 columns (wave w: columns 16 w .. 16 w + 15) x a K range (all of K, or one of S splits when the panels
 //     alone leave CUs idle) x a row block of up to 128 rows: MT = 2, 4 or 8 row tiles of v_mfma_f32_16x16x32_f16.  Calls of more

@@ -508,6 +508,71 @@ int qllm_bitpanel_describe(const qllm_weight_t *w, int32_t M, int32_t have_works
   return QLLM_OK;
 }
 
+// why qllm_linear_forward_bitgemm does not serve (w, M): the status, with the text in qllm_last_error(); QLLM_OK: served
+static int bitgemm_check(const qllm_weight_t *w, int M) {
+  static const char kInstead[] = "use qllm_dequant + a GEMM";
+  if (w->g_idx) return set_error(QLLM_ERR_INVALID, "qllm_linear_forward_bitgemm takes a plain layer (g_idx must be NULL: sort the rows by group and gather x with qllm_gather_columns)");
+  if (!knob("QLLM_BITGEMM", 1)) return set_error(QLLM_ERR_UNSUPPORTED, "QLLM_BITGEMM is off; %s", kInstead);
+  if (M < kBitGemmMinM)
+    return set_error(QLLM_ERR_UNSUPPORTED, "the 2..8-bit prefill kernel serves %d rows and up (got M=%d); call qllm_linear_forward_bitpanel (17..512 rows) or qllm_linear_forward, or %s", kBitGemmMinM, M, kInstead);
+  if (const char *why = bitgemm_refusal(*w))
+    return set_error(QLLM_ERR_UNSUPPORTED, "the 2..8-bit prefill kernel: %s (got bits=%d K=%d N=%d g=%d layout=%d); %s", why, w->bits, w->K, w->N, w->group_size, w->layout, kInstead);
+  if ((double)M * w->K * 2 >= 2147483648.0) return set_error(QLLM_ERR_UNSUPPORTED, "the 2..8-bit prefill kernel: M x K activations must be below 2 GiB (M=%d K=%d); %s", M, w->K, kInstead);
+  return QLLM_OK;
+}
+
+int qllm_linear_forward_bitgemm(const qllm_weight_t *w, const void *x, void *y, int32_t M, int32_t act_dtype, void *workspace,
+                                size_t workspace_bytes, void *stream) {
+  clear_error();
+  int rc = validate_weight(w);
+  if (rc) return rc;
+  if (!x || !y) return set_error(QLLM_ERR_INVALID, "x / y must not be NULL");
+  if (M <= 0) return set_error(QLLM_ERR_INVALID, "M must be >= 1 (got %d)", M);
+  if (act_dtype != QLLM_F16 && act_dtype != QLLM_BF16 && act_dtype != QLLM_F16_IN_BF16_OUT)
+    return set_error(QLLM_ERR_INVALID, "act_dtype must be QLLM_F16 or QLLM_F16_IN_BF16_OUT");
+  rc = bitgemm_check(w, M);
+  if (rc) return rc;
+  if (act_dtype == QLLM_BF16)
+    return set_error(QLLM_ERR_UNSUPPORTED, "the 2..8-bit prefill kernel reads fp16 activations: convert x to fp16, pass QLLM_F16_IN_BF16_OUT (qllm_convert_bf16_to_f16), or use qllm_dequant + a GEMM");
+  if ((uintptr_t)x % 16 || (uintptr_t)y % 16) return set_error(QLLM_ERR_UNSUPPORTED, "the 2..8-bit prefill kernel: x and y must be 16-byte aligned; use qllm_dequant + a GEMM");
+  const BitGemmGeom g = bitgemm_geometry(*w, M, usable_ws(workspace, workspace_bytes));
+  BitGemmParams p;
+  fill_call(p, *w, x, M, QLLM_F16);
+  fill_layer(p, *w, y);
+  p.K = w->K;
+  p.N = w->N;
+  p.group_size = w->group_size;
+  p.bits = w->bits;
+  p.out_bf16 = act_dtype == QLLM_F16_IN_BF16_OUT;
+  p.split_k = g.split_k;
+  if (g.split_k > 1) carve(workspace, &p.counters, &p.slabs);
+  return launch_bitgemm(p, g, (hipStream_t)stream);
+}
+
+size_t qllm_bitgemm_workspace_bytes(const qllm_weight_t *w, int32_t M) {
+  if (!w || validate_weight(w) || M <= 0 || bitgemm_check(w, M)) {
+    clear_error();
+    return kCounterBytes;
+  }
+  return kCounterBytes + bitgemm_geometry(*w, M, SIZE_MAX).slab_bytes;
+}
+
+int qllm_bitgemm_describe(const qllm_weight_t *w, int32_t M, int32_t have_workspace, char *buf, size_t buflen) {
+  clear_error();
+  if (!buf || buflen == 0) return set_error(QLLM_ERR_INVALID, "buf must not be NULL");
+  int rc = validate_weight(w);
+  if (rc) return rc;
+  if (M <= 0) return set_error(QLLM_ERR_INVALID, "M must be >= 1 (got %d)", M);
+  if (bitgemm_check(w, M)) {
+    snprintf(buf, buflen, "unsupported (%s)", last_error_text());
+    clear_error();
+    return QLLM_OK;
+  }
+  const BitGemmGeom g = bitgemm_geometry(*w, M, have_workspace ? SIZE_MAX : 0);
+  snprintf(buf, buflen, "bitgemm bits=%d tile=256x128 tiles=%d split_k=%d", w->bits, g.tiles, g.split_k);
+  return QLLM_OK;
+}
+
 // why qllm_linear_forward_bitgroup does not serve (w[0..n), M): the status -- QLLM_ERR_INVALID for arguments no call takes,
 // QLLM_ERR_UNSUPPORTED for calls this kernel does not take --, with the text in qllm_last_error(); QLLM_OK: served
 static int bitgroup_check(const qllm_weight_t *w, int n, int M) {

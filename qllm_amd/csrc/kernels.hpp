@@ -211,6 +211,32 @@ const char *bitpanel_refusal(const qllm_weight_t &w);  // NULL: served (for 17..
 BitPanelGeom bitpanel_geometry(const qllm_weight_t &w, int M, size_t ws_bytes);
 int launch_bitpanel(const BitPanelParams &p, const BitPanelGeom &g, hipStream_t stream);
 
+// ---- bitgemm.hip: fused prefill GEMM (129 rows and up) for every width 2..8 on the row-stream layouts in place -- gemm3's 256 x 128 x 64
+// tile with unit-owning dequant waves; reached through qllm_linear_forward_bitgemm only (no planner route) ------------------------------
+constexpr int kBitGemmMinM = 129;
+struct BitGemmParams {
+  const void *x;  // fp16
+  const uint32_t *qweight;
+  const half_t *scales;
+  const void *qzeros;
+  const half_t *bias;
+  void *y;
+  float *slabs;   // K-split: [tiles][split_k][256 x 128] fp32 partial tiles
+  int *counters;  // K-split: one arrival counter per output tile (zero before and after the launch)
+  int M, K, N, group_size, zero_kind, add_zero_bias, act_bf16;
+  int out_bf16;   // y is bf16 (x was converted to fp16 by the caller: QLLM_F16_IN_BF16_OUT)
+  int bits, split_k;
+};
+struct BitGemmGeom {
+  int tiles;       // ceil(M / 256) * ceil(N / 128)
+  int split_k;     // blocks along K per tile
+  int grid;
+  size_t slab_bytes;
+};
+const char *bitgemm_refusal(const qllm_weight_t &w);  // NULL: served (from 129 rows)
+BitGemmGeom bitgemm_geometry(const qllm_weight_t &w, int M, size_t ws_bytes);
+int launch_bitgemm(const BitGemmParams &p, const BitGemmGeom &g, hipStream_t stream);
+
 // ---- comm.hip: staging buffer of one rank = [2 parities][world][slot_bytes] payload | this control block ----------------------------
 constexpr int kCommMaxWorld = 16;
 struct CommCtl {

@@ -42,6 +42,9 @@ static Settable kSettable[] = {
     // (no route: the two knobs of qllm_linear_forward_bitgroup, bitgemv_group.hip)
     {"QLLM_BITGROUP", 0, 1, 0, 0},             // 0: the grouped bit-stream entry refuses every call
     {"QLLM_BITGROUP_MAX_M", 0, 16, 0, 0},      // read by callers that route by rows (the Python modules): the most rows they send to that entry (0: never)
+    // (no route: the two knobs of qllm_linear_forward_bitgemm, bitgemm.hip)
+    {"QLLM_BITGEMM", 0, 1, 0, 0},              // 0: the 2..8-bit prefill entry refuses every call
+    {"QLLM_BITGEMM_MIN_M", 129, 65536, 0, 0},  // read by callers that route by rows (the Python modules): the fewest rows they send to that entry
 };
 int g_knob_overrides = 0;
 Settable *find_knob(const char *name) {

@@ -22,7 +22,7 @@ def _tkey(t):
 
 
 # derived, pointer-holding state (ctypes descriptors, shadows, sibling groups): rebuilt on demand, never copied or pickled
-_DERIVED = ("_desc", "_desc_key", "_desc_keep", "_native", "_native_key", "_ao", "_ao_key", "_ao_panel_refused", "_perm", "_siblings")
+_DERIVED = ("_desc", "_desc_key", "_desc_keep", "_native", "_native_key", "_ao", "_ao_key", "_ao_panel_refused", "_ao_gemm_refused", "_perm", "_siblings")
 # (a released module is materialised before it is pickled / deep-copied: see __getstate__)
 
 
@@ -242,6 +242,9 @@ class HipForwardMixin:
             # kernel, an entry of its own (csrc/bitpanel.hip; bias included)
             y = self._bitpanel_linear(w, x2d, act_order_g_idx)
             if y is None:
+                # the same layers above those rows, from QLLM_BITGEMM_MIN_M on: the fused 2..8-bit prefill kernel (csrc/bitgemm.hip)
+                y = self._bitgemm_linear(w, x2d, act_order_g_idx, key=x)
+            if y is None:
                 # e.g. 3/5/6/7/8-bit at prefill sizes: dequantise with the library kernel, then a plain library GEMM
                 wt = ops.dequant(w, x.device, torch.float16)
                 y = torch.matmul(x2d, wt.to(x2d.dtype))
@@ -258,6 +261,21 @@ class HipForwardMixin:
             return None
         try:
             return ops.linear_forward_bitpanel(w, x2d)
+        except ops.QllmUnsupported:
+            return None
+
+    @staticmethod
+    def _bitgemm_linear(w, x2d, act_order_g_idx=None, key=None):
+        """`ops.linear_forward_bitgemm` for a call no planner route and not the mid-batch kernel serves, or None: act-order descriptors,
+        other layouts, other activation types, rows below `ops.bitgemm_min_m()` (0: never) or not above `ops.bitpanel_max_m()` and the
+        kernel's own refusal all leave the call to dequant + GEMM, exactly as before."""
+        lo = ops.bitgemm_min_m()
+        if (act_order_g_idx is not None or w.layout not in (ops.LAYOUTS["GPTQ"], ops.LAYOUTS["HQQ"])
+                or x2d.dtype not in (torch.float16, torch.bfloat16) or lo <= 0 or x2d.shape[0] < lo
+                or x2d.shape[0] <= ops.bitpanel_max_m()):
+            return None
+        try:
+            return ops.linear_forward_bitgemm(w, x2d, key=key)
         except ops.QllmUnsupported:
             return None
 

@@ -158,6 +158,7 @@ class QuantLinearGPTQ(nn.Module, CompressWeight, HipForwardMixin):
     _ao = None
     _ao_key = None
     _ao_panel_refused = None   # the _ao_key of the copy the mid-batch kernel (ops.linear_forward_bitpanel) has refused
+    _ao_gemm_refused = None    # ... and of the copy the 2..8-bit prefill kernel (ops.linear_forward_bitgemm) has refused
 
     def _ao_one_launch(self, rows: int) -> bool:
         """Whether `rows` rows go through the gathering matvec (one launch) or through gather_columns + the plain matvec on the same
@@ -251,5 +252,17 @@ class QuantLinearGPTQ(nn.Module, CompressWeight, HipForwardMixin):
                         return y.reshape(x.shape[:-1] + (self.outfeatures,))
                     except ops.QllmUnsupported:
                         self._ao_panel_refused = self._ao_key
+            elif (x.shape[-1] <= 28672 and x.dtype in (torch.float16, torch.bfloat16)
+                  and 0 < _ops().bitgemm_min_m() <= x.numel() // x.shape[-1] and x.numel() // x.shape[-1] > _ops().bitpanel_max_m()):
+                # ... and further, from QLLM_BITGEMM_MIN_M rows on: the same copy and the same shared gather, then the fused 2..8-bit
+                # prefill kernel (csrc/bitgemm.hip).  Its refusal is remembered per copy as well
+                ao = self._ao_descriptor(azb, mid_batch=True)
+                if ao is not None and self._ao_gemm_refused != self._ao_key:
+                    from ... import ops
+                    try:
+                        y = ops.linear_forward_bitgemm(ao[0], _gathered(x, ao[1]))
+                        return y.reshape(x.shape[:-1] + (self.outfeatures,))
+                    except ops.QllmUnsupported:
+                        self._ao_gemm_refused = self._ao_key
         g_idx = self.g_idx if self.act_order else None
         return self._hip_linear(x, g_idx, azb)

@@ -195,6 +195,56 @@ def bitpanel_describe(w: QllmWeight, m: int, have_workspace: bool = True) -> str
     return buf.value.decode()
 
 
+def bitgemm_min_m() -> int:
+    """The fewest rows module code sends to `linear_forward_bitgemm` (above `bitpanel_max_m()`): the QLLM_BITGEMM_MIN_M knob, else the
+    library's default (include/qllm_mi355x.h, profiles/bitgemm.md); 0 -- the modules do not use the entry -- where that default is 0
+    or QLLM_BITGEMM is switched off.  The entry itself takes 129 rows and up whatever this says."""
+    v = get_knob("QLLM_BITGEMM_MIN_M")
+    m = _lib.BITGEMM_MIN_M_DEFAULT if v is None else v
+    if m < 129 or get_knob("QLLM_BITGEMM") == 0:
+        return 0
+    return m
+
+
+def linear_forward_bitgemm(w: QllmWeight, x2d: torch.Tensor, out: Optional[torch.Tensor] = None,
+                           key: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y[M,N] = x2d[M,K] . dequant(w) (+bias) through the fused 2..8-bit prefill kernel (qllm_linear_forward_bitgemm, csrc/bitgemm.hip):
+    129 rows and up, GPTQ / HQQ layouts in place, K % 64 == 0, N % 8 == 0, no g_idx.  An entry of its own -- `linear_forward` and
+    `plan_describe` keep refusing these calls.  A bf16 x goes through the shared fp16 copy (`bf16_as_f16(x2d, key)`: siblings convert
+    once) and gives a bf16 y, as `linear_forward_bf16_via_f16` does.  Raises QllmUnsupported for everything the entry does not serve
+    (callers then use dequant() + matmul) -- decided BEFORE x is converted."""
+    _check_x(x2d, (w,))
+    lib = _lib.load()
+    m = x2d.shape[0]
+    if out is not None:
+        _check_out(out, m, w.N, x2d)
+    if m == 0:
+        return out if out is not None else torch.empty((0, w.N), dtype=x2d.dtype, device=x2d.device)
+    dt = _lib.DT_F16_IN_BF16_OUT if x2d.dtype == torch.bfloat16 else _act_dtype(x2d)
+    if dt != DT_F16:   # (nothing is converted for a call the entry refuses)
+        why = bitgemm_describe(w, m)
+        if why.startswith("unsupported"):
+            raise QllmUnsupported(_lib.QLLM_ERR_UNSUPPORTED, why)
+        xin = bf16_as_f16(x2d, key)
+    else:
+        xin = x2d
+    if out is None:
+        out = torch.empty((m, w.N), dtype=x2d.dtype, device=x2d.device)
+    with torch.cuda.device(x2d.device):
+        ws = workspace(x2d.device, lib.qllm_bitgemm_workspace_bytes(C.byref(w), m))
+        rc = lib.qllm_linear_forward_bitgemm(C.byref(w), xin.data_ptr(), out.data_ptr(), m, dt, ws.data_ptr(), ws.numel(), _stream_ptr())
+    _lib.check(rc)
+    return out
+
+
+def bitgemm_describe(w: QllmWeight, m: int, have_workspace: bool = True) -> str:
+    """The geometry `linear_forward_bitgemm` would launch for m rows ("bitgemm bits=.. tile=256x128 tiles=.. split_k=.."), or
+    "unsupported (...)".  Pure host code."""
+    buf = C.create_string_buffer(512)
+    _lib.check(_lib.load().qllm_bitgemm_describe(C.byref(w), int(m), 1 if have_workspace else 0, buf, 512))
+    return buf.value.decode()
+
+
 _LAST_CONVERT: dict = {}
 
 
@@ -683,6 +733,6 @@ def unpack_native(w: QllmWeight, keep, layout: str):
     return qweight, scales, qzeros
 
 
-__all__ = ["make_weight", "linear_forward", "linear_forward_grouped", "linear_forward_permuted", "linear_forward_bitpanel", "bitpanel_describe", "linear_forward_bitgroup", "bitgroup_describe", "linear_forward_shared", "dequant", "gather_columns", "unpack_qweight", "pack_qweight",
+__all__ = ["make_weight", "linear_forward", "linear_forward_grouped", "linear_forward_permuted", "linear_forward_bitpanel", "bitpanel_describe", "linear_forward_bitgemm", "bitgemm_describe", "bitgemm_min_m", "linear_forward_bitgroup", "bitgroup_describe", "linear_forward_shared", "dequant", "gather_columns", "unpack_qweight", "pack_qweight",
            "workspace", "QllmUnsupported", "LAYOUTS", "plan_describe", "repack_native", "unpack_native", "hqq_quantize", "gptq_quantize",
            "gptq_quantize_static", "awq_quantize", "awq_clip_search"]
