@@ -387,6 +387,31 @@ size_t qllm_bitgroup_workspace_bytes(const qllm_weight_t *w, int32_t n_weights, 
  * order), or "unsupported (...)".  Pure host code; have_workspace = 0: the call without a workspace (no member splits). */
 int qllm_bitgroup_describe(const qllm_weight_t *w, int32_t n_weights, int32_t M, int32_t have_workspace, char *buf, size_t buflen);
 
+/* y[M,N] = act(gate)[M,K] * up[M,K] . dequant(w) (+ bias): the down-projection of a SwiGLU MLP with the elementwise product
+ * act_fn(gate_proj(x)) * up_proj(x) formed INSIDE the linear launch (csrc/strip1_swiglu.hip: the SWIGLU forms of the batch-1 kernel,
+ * csrc/strip1_kernel.hpp).  The kernel routes every element of its input through registers on the way to LDS; the staging pass loads
+ * the matching chunk of `up` in the same batch, computes s = g / (1 + expf(-g)) in fp32, rounds s to act_dtype, multiplies by u in fp32
+ * and rounds again -- the two roundings of the eager expression -- and goes on as the plain kernel: the launch returns BIT FOR BIT what
+ * qllm_linear_forward returns on x = act(gate) * up rounded that way, one dependent launch and one [M, K] round trip less.
+ * `act`: QLLM_ACT_SILU.  gate / up: contiguous [M, K] of act_dtype (QLLM_F16 / QLLM_BF16), 16-byte aligned; y as for
+ * qllm_linear_forward, and it must not alias gate or up.
+ * Served: exactly the calls qllm_linear_forward runs on the batch-1 kernel ("strip1 ..." in qllm_plan_describe), with the same waves x
+ * round -- native-layout layers (NATIVE, NATIVE_F16Z); M = 1: 4 bits with 128- or 64-wide groups, and 3 bits; M = 2..4: 4 bits,
+ * 128-wide groups, K <= 16384.  QLLM_ERR_UNSUPPORTED for everything else -- other layouts, act-order, other widths, M >= 5, a
+ * QLLM_STRIP1* knob that takes the shape off that kernel, another `act` -- and the caller runs the activation and
+ * qllm_linear_forward as before.  QLLM_ERR_INVALID: NULL / misaligned pointers, M < 1, y aliasing an input.  Every error is raised
+ * before any device work.  No workspace, no host synchronisation; hipGraph-capturable.  Not built: GELU gates, the fused all-reduce
+ * form, a norm in front or a residual behind.
+ * ABI: the two symbols are ADDITIVE within ABI 7 (QLLM_ABI_VERSION is unchanged, as for the bitpanel / bitgroup symbols): probe for them
+ * by symbol.  The reference's counterpart was its fused_mlp / QuantLlamaMLP (import left commented out in
+ * qllm/modeling/q_layers/__init__.py:4). */
+#define QLLM_ACT_SILU 0
+int qllm_linear_forward_swiglu(const qllm_weight_t *w, const void *gate, const void *up, void *y, int32_t M, int32_t act_dtype, int32_t act,
+                               void *stream);
+/* What that call (act = QLLM_ACT_SILU) would launch, as text: "swiglu " followed by the plan line of the plain call ("swiglu strip1 nw=15
+ * round=24 grid=strips x 1 layout=strip-major"), or "refused: " and the refusal text.  Pure host code. */
+int qllm_swiglu_describe(const qllm_weight_t *w, int32_t M, char *buf, size_t buflen);
+
 /* ---- HQQ quantizer (ABI 7) ---------------------------------------------------------------------------------------------------------- */
 /* W[N,K] (fp16 / bf16 / fp32 by w_dtype, row-major, 16-byte aligned) -> the HQQ layer buffers: qweight i32 [K*bits/32][N], scales f16
  * [K/g][N] = fp16(1/s), zeros f16 [K/g][N] = fp16(z).  The algorithm is HQQQuant.do_quantize's (qllm/quantization/hqq/quant_hqq.py:34-36,

@@ -19,6 +19,7 @@ DT_F16, DT_BF16, DT_F16_IN_BF16_OUT, DT_F32 = 0, 1, 2, 3
 ABI_VERSION = 7
 BITPANEL_MAX_M_DEFAULT = 256   # QLLM_BITPANEL_MAX_M_DEFAULT of include/qllm_mi355x.h: the measured line of profiles/bitpanel.md (0: modules do not route)
 BITGEMM_MIN_M_DEFAULT = 0      # QLLM_BITGEMM_MIN_M_DEFAULT of include/qllm_mi355x.h: the measured line of profiles/bitgemm.md (0: modules do not route)
+ACT_SILU = 0                   # QLLM_ACT_SILU of include/qllm_mi355x.h (qllm_linear_forward_swiglu)
 BITGROUP_MAX_M_DEFAULT = 16    # QLLM_BITGROUP_MAX_M_DEFAULT of include/qllm_mi355x.h: the measured line of profiles/bitgemv_group.md (0: sibling groups do not route)
 
 EXPORTS = (
@@ -36,6 +37,7 @@ EXPORTS = (
     "qllm_linear_forward_bitgroup", "qllm_bitgroup_workspace_bytes", "qllm_bitgroup_describe",
     "qllm_linear_forward_bitgemm", "qllm_bitgemm_workspace_bytes", "qllm_bitgemm_describe",
     "qllm_awq_clip_search_workspace_bytes", "qllm_awq_clip_search", "qllm_awq_quantize",
+    "qllm_linear_forward_swiglu", "qllm_swiglu_describe",
 )
 
 
@@ -149,6 +151,10 @@ def _declare(lib):
     lib.qllm_bitgroup_workspace_bytes.argtypes = [wp, i32, i32]
     lib.qllm_bitgroup_describe.restype = C.c_int
     lib.qllm_bitgroup_describe.argtypes = [wp, i32, i32, i32, C.c_char_p, sz]
+    lib.qllm_linear_forward_swiglu.restype = C.c_int
+    lib.qllm_linear_forward_swiglu.argtypes = [wp, vp, vp, vp, i32, i32, i32, vp]
+    lib.qllm_swiglu_describe.restype = C.c_int
+    lib.qllm_swiglu_describe.argtypes = [wp, i32, C.c_char_p, sz]
     lib.qllm_plan_describe.restype = C.c_int
     lib.qllm_plan_describe.argtypes = [wp, i32, i32, i32, C.c_char_p, sz]
     lib.qllm_debug_timeline.restype = C.c_int

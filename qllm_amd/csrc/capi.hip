@@ -830,6 +830,50 @@ int qllm_linear_forward_allreduce(const qllm_weight_t *w, const void *x, void *y
   return launch_strip1_allreduce(p, pl.one_nw, pl.one_maxs, w->N / 16, (hipStream_t)stream);
 }
 
+// y = linear(w, act(gate) * up): the SWIGLU forms of the batch-1 kernel (strip1_swiglu.hip); decide_swiglu says what is served
+int qllm_linear_forward_swiglu(const qllm_weight_t *w, const void *gate, const void *up, void *y, int32_t M, int32_t act_dtype, int32_t act,
+                               void *stream) {
+  clear_error();
+  int rc = validate_weight(w);
+  if (rc) return rc;
+  if (!gate || !up) return set_error(QLLM_ERR_INVALID, "gate / up must not be NULL");
+  rc = check_io(gate, y, M, act_dtype);
+  if (rc) return rc;
+  if ((uintptr_t)up % 16 != 0) return set_error(QLLM_ERR_INVALID, "up must be 16-byte aligned");
+  if (y == gate || y == up) return set_error(QLLM_ERR_INVALID, "y must not alias gate / up");
+  StripPlan pl;
+  rc = decide_swiglu(w, M, act, &pl);
+  if (rc) return rc;
+  Strip1Params p;
+  void *ys[1] = {y};
+  fill_strip1_params(p, w, ys, 1, gate, M, act_dtype);
+  p.x2 = up;
+  return launch_strip1_swiglu(p, pl.one_nw, pl.one_maxs, w->N / 16, (hipStream_t)stream);
+}
+
+// what that call would launch, as text ("swiglu " + the plain call's plan line), or why it is refused -- no device work
+int qllm_swiglu_describe(const qllm_weight_t *w, int32_t M, char *buf, size_t buflen) {
+  clear_error();
+  if (!w || !buf || buflen < 64) return set_error(QLLM_ERR_INVALID, "w / buf must not be NULL (buf >= 64 bytes)");
+  if (M <= 0) return set_error(QLLM_ERR_INVALID, "M must be >= 1 (got %d)", M);
+  int rc = validate_weight(w);
+  if (rc == QLLM_OK) {
+    Decision d;
+    memset(&d, 0, sizeof(d));
+    d.route = ROUTE_STRIP;
+    rc = decide_swiglu(w, M, QLLM_ACT_SILU, &d.strip);
+    if (rc == QLLM_OK) {
+      const int n = snprintf(buf, buflen, "swiglu ");
+      describe(d, w, 1, M, 0, buf + n, buflen - n);
+      clear_error();
+      return QLLM_OK;
+    }
+  }
+  if (rc != QLLM_ERR_UNSUPPORTED) return rc;
+  snprintf(buf, buflen, "refused: %s", last_error_text());
+  return QLLM_OK;
+}
+
 int qllm_dequant(const qllm_weight_t *w, void *out, int32_t out_dtype, int32_t out_transposed, void *stream) {
   clear_error();
   int rc = validate_weight(w);

@@ -126,6 +126,9 @@ struct Strip1Params {
   int *ar_status;          // set to 1 if a peer never arrived (nullable)
   int ar_rank, ar_world;
   uint32_t ar_slot_bytes;
+  // act(gate) * up staged in-kernel (the SWIGLU forms, strip1_swiglu.hip: x is the gate vector): the up vector, shaped like x.  Read by
+  // those forms only
+  const void *x2;
 };
 
 // ---- bitgemv.hip (round 6): fused decode matvec for the widths the MFMA strips do not take (2, 5, 6, 7, 8 bits; row-stream layouts) -----
@@ -257,6 +260,7 @@ __device__ __forceinline__ uint4_t load16_sys(const void *p) {
 bool strip1_shape(int K, int blocks, int cus, int *nw, int *maxs, bool odd64 = false);  // (odd64: K % 128 == 64 allowed -- 4-bit 64-wide groups)
 int launch_strip1(const Strip1Params &p, int nw, int maxs, int n_prob, int max_strips, hipStream_t stream);
 int launch_strip1_allreduce(const Strip1Params &p, int nw, int maxs, int n_strips, hipStream_t stream);  // (p.ar_* set; one layer)
+int launch_strip1_swiglu(const Strip1Params &p, int nw, int maxs, int n_strips, hipStream_t stream);     // strip1_swiglu.hip (p.x2 set; one layer)
 
 // ---- native.hip (reference layouts <-> the strip-major native layout) -------------------------------------------------------
 int launch_repack_native(const qllm_weight_t &src, int zero_kind, void *qweight_out, void *scales_out, void *qzeros_out, hipStream_t stream);

@@ -571,6 +571,19 @@ Decision decide_group(const qllm_weight_t *w, int n, int M, int act_dtype) {
   return routed(ROUTE_SKINNY);
 }
 
+// The fused SwiGLU down-projection (strip1_swiglu.hip): exactly the calls the plain entry runs on the batch-1 kernel, with the same
+// waves x round, so that the fused launch is the plain launch's arithmetic on act(gate) * up.  Everything else keeps today's path
+// (the elementwise kernel, then qllm_linear_forward).
+int decide_swiglu(const qllm_weight_t *w, int M, int act, StripPlan *plan) {
+  *plan = StripPlan{};
+  if (act != QLLM_ACT_SILU) return set_error(QLLM_ERR_UNSUPPORTED, "fused SwiGLU: act=%d is not served (QLLM_ACT_SILU only)", act);
+  if (!is_native(*w) || !strip_plan(w, 1, M, plan) || !plan->one_nw)
+    return set_error(QLLM_ERR_UNSUPPORTED, "fused SwiGLU: calls of the batch-1 kernel on native-layout layers only -- M=1: 4 bits with 128- / 64-wide groups and 3 bits, "
+                     "M=2..4: 4 bits with 128-wide groups and K <= 16384 (M=%d bits=%d g=%d K=%d layout=%d); run the activation and qllm_linear_forward",
+                     M, w->bits, w->group_size, w->K, w->layout);
+  return QLLM_OK;
+}
+
 void describe(const Decision &d, const qllm_weight_t *w, int n, int M, size_t ws_bytes, char *buf, size_t buflen) {
   const char *sm = is_native(w[0]) ? " layout=strip-major" : "";
   switch (d.route) {

@@ -141,9 +141,10 @@ def release_reference_layouts(model: torch.nn.Module, on: bool = True) -> int:
 
 
 def load_quantized(model_dir: str, device: Optional[str] = "cuda", torch_dtype: Optional[torch.dtype] = None,
-                   release_reference: bool = True):
+                   release_reference: bool = True, fuse_mlp: bool = False):
     """Local equivalent of AutoQuantizedModelForCausalLM.from_quantized (base.py:226-322).  `release_reference`: see
-    release_reference_layouts (QLLM_RELEASE_REFERENCE=0 in the environment keeps both copies)."""
+    release_reference_layouts (QLLM_RELEASE_REFERENCE=0 in the environment keeps both copies).  `fuse_mlp` (opt-in): fold
+    act_fn(gate) * up of the SwiGLU MLPs into the down_proj launch (q_layers/fused_mlp.py); model.fused_mlps counts the modules."""
     import transformers
 
     hf_cfg = transformers.AutoConfig.from_pretrained(model_dir)
@@ -184,6 +185,9 @@ def load_quantized(model_dir: str, device: Optional[str] = "cuda", torch_dtype: 
         model = model.to(device)
     if release_reference and os.environ.get("QLLM_RELEASE_REFERENCE", "1") != "0":
         release_reference_layouts(model)
+    if fuse_mlp:
+        from .q_layers import install_fused_mlp
+        model.fused_mlps = install_fused_mlp(model, [target])
     return model.eval()
 
 

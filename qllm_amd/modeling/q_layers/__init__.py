@@ -4,3 +4,4 @@ from .quant_linear_awq import WQLinear_GEMM  # noqa: F401
 from .quant_linear_hqq import QuantLinearHQQ  # noqa: F401
 from .quant_linear_onnxruntime import QuantLinearORT  # noqa: F401
 from .fused import SiblingGroup, fuse_siblings, install_sibling_groups  # noqa: F401
+from .fused_mlp import install_fused_mlp, uninstall_fused_mlp  # noqa: F401

@@ -22,7 +22,7 @@ def _tkey(t):
 
 
 # derived, pointer-holding state (ctypes descriptors, shadows, sibling groups): rebuilt on demand, never copied or pickled
-_DERIVED = ("_desc", "_desc_key", "_desc_keep", "_native", "_native_key", "_ao", "_ao_key", "_ao_panel_refused", "_ao_gemm_refused", "_perm", "_siblings")
+_DERIVED = ("_desc", "_desc_key", "_desc_keep", "_native", "_native_key", "_ao", "_ao_key", "_ao_panel_refused", "_ao_gemm_refused", "_perm", "_swiglu_refused_from", "_siblings")
 # (a released module is materialised before it is pickled / deep-copied: see __getstate__)
 
 
@@ -211,6 +211,35 @@ class HipForwardMixin:
         azb = autogptq_compat() if self._layout_name() == "GPTQ" else 0
         w = self.native_descriptor(azb)
         return w is not None and reducer.linear_all_reduce(w, x2d, out.view(1, self.outfeatures))
+
+    # smallest row count the fused SwiGLU entry refused for this layer (what it serves is monotone in the row count: 1, or up to 4 rows)
+    _swiglu_refused_from = 1 << 30
+    # the most rows forward_swiglu sends to the fused entry: measured (profiles/swiglu.md), the fused MLP wins at one row and loses at
+    # four (the prologue computes silu for every batch row in every block) -- the entry itself serves up to four; QLLM_FUSE_MLP_MAX_M moves it
+    swiglu_max_m = int(os.environ.get("QLLM_FUSE_MLP_MAX_M", "1"))
+
+    def forward_swiglu(self, gate: torch.Tensor, up: torch.Tensor) -> torch.Tensor:
+        """forward(silu(gate) * up) -- the down_proj of a SwiGLU MLP.  Where the batch-1 kernel serves the call on the layer's native
+        copy, ONE launch forms the product while it stages its input (ops.linear_forward_swiglu, csrc/strip1_swiglu.hip); everything
+        else -- more rows than `swiglu_max_m`, a refusal (remembered as "nothing from this many rows up", so a refused shape costs one
+        call once), no native copy, an act-order layer, non-contiguous inputs, dtypes or shapes that disagree -- is the elementwise kernel and the layer's own forward."""
+        g2d = gate.reshape(-1, gate.shape[-1])
+        u2d = up.reshape(-1, up.shape[-1])
+        m = g2d.shape[0]
+        resolve = getattr(self, "_resolve_act_order", None)   # (GPTQ detects act-order lazily: do it before branching on it)
+        if resolve is not None:
+            resolve()
+        if (1 <= m <= self.swiglu_max_m and m < self._swiglu_refused_from and gate.shape == up.shape and gate.dtype == up.dtype
+                and gate.dtype in (torch.float16, torch.bfloat16) and g2d.is_contiguous() and u2d.is_contiguous()
+                and not getattr(self, "act_order", None)):
+            azb = autogptq_compat() if self._layout_name() == "GPTQ" else 0
+            w = self.native_descriptor(azb)
+            if w is not None:
+                try:
+                    return ops.linear_forward_swiglu(w, g2d, u2d).reshape(gate.shape[:-1] + (self.outfeatures,))
+                except ops.QllmUnsupported:
+                    self._swiglu_refused_from = m
+        return self(torch.nn.functional.silu(gate) * up)
 
     def _hip_linear(self, x: torch.Tensor, act_order_g_idx=None, add_zero_bias: int = 0) -> torch.Tensor:
         if not x.is_cuda or not self.qweight.is_cuda:

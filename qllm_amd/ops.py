@@ -407,6 +407,37 @@ def bitgroup_describe(ws_desc: Sequence[QllmWeight], m: int, have_workspace: boo
     return buf.value.decode()
 
 
+def linear_forward_swiglu(w: QllmWeight, gate2d: torch.Tensor, up2d: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y[M,N] = (silu(gate2d) * up2d)[M,K] . dequant(w) (+bias) in ONE launch (qllm_linear_forward_swiglu, csrc/strip1_swiglu.hip): the
+    down-projection of a SwiGLU MLP with the elementwise product formed while the batch-1 kernel stages its input.  Bit-identical to
+    `linear_forward(w, F.silu(gate2d) * up2d)` wherever torch's silu rounds like the kernel's.  Raises QllmUnsupported for every call
+    the batch-1 kernel does not serve (callers then run the activation and `linear_forward`)."""
+    _check_x(gate2d, (w,))
+    _check_input(up2d, "up")
+    if up2d.shape != gate2d.shape or up2d.dtype != gate2d.dtype or up2d.device != gate2d.device:
+        raise RuntimeError(f"up must match gate: {tuple(gate2d.shape)} {gate2d.dtype} on {gate2d.device}, got {tuple(up2d.shape)} {up2d.dtype} on {up2d.device}")
+    m = gate2d.shape[0]
+    if out is not None:
+        _check_out(out, m, w.N, gate2d)
+    if m == 0:
+        return out if out is not None else torch.empty((0, w.N), dtype=gate2d.dtype, device=gate2d.device)
+    if out is None:
+        out = torch.empty((m, w.N), dtype=gate2d.dtype, device=gate2d.device)
+    with torch.cuda.device(gate2d.device):
+        rc = _lib.load().qllm_linear_forward_swiglu(C.byref(w), gate2d.data_ptr(), up2d.data_ptr(), out.data_ptr(), m, _act_dtype(gate2d),
+                                                    _lib.ACT_SILU, _stream_ptr())
+    _lib.check(rc)
+    return out
+
+
+def swiglu_describe(w: QllmWeight, m: int) -> str:
+    """What `linear_forward_swiglu` would launch for m rows: "swiglu " + the plan line of the plain call ("swiglu strip1 nw=.. round=..
+    ..."), or "refused: ..." with the entry's refusal text.  Pure host code."""
+    buf = C.create_string_buffer(640)
+    _lib.check(_lib.load().qllm_swiglu_describe(C.byref(w), int(m), buf, 640))
+    return buf.value.decode()
+
+
 def dequant(w: QllmWeight, device: torch.device, dtype=torch.float16, transposed: bool = False) -> torch.Tensor:
     """W[K,N] (or [N,K]) bit-identical to the reference's DequantizeLinearBlockWise / unpack()."""
     lib = _lib.load()
@@ -733,6 +764,6 @@ def unpack_native(w: QllmWeight, keep, layout: str):
     return qweight, scales, qzeros
 
 
-__all__ = ["make_weight", "linear_forward", "linear_forward_grouped", "linear_forward_permuted", "linear_forward_bitpanel", "bitpanel_describe", "linear_forward_bitgemm", "bitgemm_describe", "bitgemm_min_m", "linear_forward_bitgroup", "bitgroup_describe", "linear_forward_shared", "dequant", "gather_columns", "unpack_qweight", "pack_qweight",
+__all__ = ["make_weight", "linear_forward", "linear_forward_grouped", "linear_forward_permuted", "linear_forward_bitpanel", "bitpanel_describe", "linear_forward_bitgemm", "bitgemm_describe", "bitgemm_min_m", "linear_forward_bitgroup", "bitgroup_describe", "linear_forward_swiglu", "swiglu_describe", "linear_forward_shared", "dequant", "gather_columns", "unpack_qweight", "pack_qweight",
            "workspace", "QllmUnsupported", "LAYOUTS", "plan_describe", "repack_native", "unpack_native", "hqq_quantize", "gptq_quantize",
            "gptq_quantize_static", "awq_quantize", "awq_clip_search"]
