@@ -412,6 +412,36 @@ int qllm_linear_forward_swiglu(const qllm_weight_t *w, const void *gate, const v
  * round=24 grid=strips x 1 layout=strip-major"), or "refused: " and the refusal text.  Pure host code. */
 int qllm_swiglu_describe(const qllm_weight_t *w, int32_t M, char *buf, size_t buflen);
 
+/* ---- RMSNorm: standalone, and fused into the launch of the layers it feeds ------------------------------------------------------------ */
+/* y[M,K] = weight[K] * round(x[M,K] * rstd), rstd = rsqrt(mean(x^2) + eps) per row: the RMSNorm of the Llama family as ONE kernel
+ * (csrc/rmsnorm.hip: one block per row, 16-byte loads, the row kept in registers between the reduction and the output), with the eager
+ * LlamaRMSNorm's arithmetic step by step: squares and their sum in fp32 (an fp16 / bf16 square is exact in fp32), rstd in fp32,
+ * h = x * rstd rounded to act_dtype, y = weight * h in fp32 rounded to act_dtype.  The order of the sum depends on K only: results are
+ * deterministic.  x / y: contiguous [M, K] of act_dtype (QLLM_F16 / QLLM_BF16); weight: [K] of the same type; all three 16-byte
+ * aligned; K % 8 == 0, K <= 65536 (QLLM_ERR_UNSUPPORTED above); any M >= 1; y may alias x.  rstd_out: [M] floats, or NULL.
+ * QLLM_ERR_INVALID for NULL / misaligned pointers, M < 1, K % 8 != 0 -- before any device work.  hipGraph-capturable.
+ * The reference's counterpart is TritonLlamaRMSNorm (qllm/modeling/q_layers/triton_norm.py). */
+int qllm_rmsnorm(const void *x, const void *weight, void *y, int32_t M, int32_t K, float eps, int32_t act_dtype, float *rstd_out, void *stream);
+/* y_i[1,N_i] = RMSNorm(x)[1,K] . dequant(w_i) (+ bias_i) for the n_weights layers that share x (q/k/v, gate/up), with the norm formed
+ * INSIDE the grouped launch (csrc/strip1_norm.hip: the NORM forms of the batch-1 kernel, csrc/strip1_kernel.hpp).  The waves of a block
+ * together stage all of x; each sums the fp32 squares of the elements it owns, one barrier and NW partials later every wave of every
+ * block holds the same rstd bit for bit, and each chunk is rewritten in registers as norm_weight * round(x * rstd) -- the two roundings
+ * above -- before the plain kernel's code goes on.  Contract: the launch returns BIT FOR BIT what qllm_linear_forward_grouped returns on
+ * xn = norm_weight * (x.float() * rstd).to(dtype), with rstd the value it reports in rstd_out ([M] floats written by one block, or NULL).
+ * Its order of summation is not qllm_rmsnorm's: the two may differ in rare last-bit roundings of xn.
+ * Served: exactly the M = 1 calls qllm_linear_forward(_grouped) runs on the batch-1 kernel ("strip1 ..." in qllm_plan_describe) for
+ * native-layout layers (NATIVE, NATIVE_F16Z) -- 4 bits with 128- or 64-wide groups, and 3 bits -- with the same waves x round.
+ * QLLM_ERR_UNSUPPORTED for everything else (M >= 2: the four-row forms are not built; other layouts and widths; members that disagree
+ * on K / group_size / bits; a QLLM_STRIP1* knob that takes the shape off that kernel): run qllm_rmsnorm and the plain call.
+ * QLLM_ERR_INVALID: NULL / misaligned pointers, M < 1, a y aliasing x or norm_weight.  Every error is raised before any device work.  No
+ * workspace, no host synchronisation; hipGraph-capturable.
+ * ABI: the three symbols are ADDITIVE within ABI 7 (QLLM_ABI_VERSION is unchanged, as for the SwiGLU symbols): probe for them by symbol. */
+int qllm_linear_forward_rmsnorm(const qllm_weight_t *w, void *const *y, int32_t n_weights, const void *x, const void *norm_weight, float eps,
+                                int32_t M, int32_t act_dtype, float *rstd_out, void *stream);
+/* What that call would launch, as text: "rmsnorm " followed by the plan line of the plain grouped call ("rmsnorm strip1 nw=8 round=16
+ * exact grid=strips x 3 layout=strip-major"), or "refused: " and the refusal text.  Pure host code. */
+int qllm_rmsnorm_describe(const qllm_weight_t *w, int32_t n_weights, int32_t M, char *buf, size_t buflen);
+
 /* ---- HQQ quantizer (ABI 7) ---------------------------------------------------------------------------------------------------------- */
 /* W[N,K] (fp16 / bf16 / fp32 by w_dtype, row-major, 16-byte aligned) -> the HQQ layer buffers: qweight i32 [K*bits/32][N], scales f16
  * [K/g][N] = fp16(1/s), zeros f16 [K/g][N] = fp16(z).  The algorithm is HQQQuant.do_quantize's (qllm/quantization/hqq/quant_hqq.py:34-36,

@@ -38,6 +38,7 @@ EXPORTS = (
     "qllm_linear_forward_bitgemm", "qllm_bitgemm_workspace_bytes", "qllm_bitgemm_describe",
     "qllm_awq_clip_search_workspace_bytes", "qllm_awq_clip_search", "qllm_awq_quantize",
     "qllm_linear_forward_swiglu", "qllm_swiglu_describe",
+    "qllm_rmsnorm", "qllm_linear_forward_rmsnorm", "qllm_rmsnorm_describe",
 )
 
 
@@ -155,6 +156,12 @@ def _declare(lib):
     lib.qllm_linear_forward_swiglu.argtypes = [wp, vp, vp, vp, i32, i32, i32, vp]
     lib.qllm_swiglu_describe.restype = C.c_int
     lib.qllm_swiglu_describe.argtypes = [wp, i32, C.c_char_p, sz]
+    lib.qllm_rmsnorm.restype = C.c_int
+    lib.qllm_rmsnorm.argtypes = [vp, vp, vp, i32, i32, C.c_float, i32, vp, vp]
+    lib.qllm_linear_forward_rmsnorm.restype = C.c_int
+    lib.qllm_linear_forward_rmsnorm.argtypes = [wp, C.POINTER(C.c_void_p), i32, vp, vp, C.c_float, i32, i32, vp, vp]
+    lib.qllm_rmsnorm_describe.restype = C.c_int
+    lib.qllm_rmsnorm_describe.argtypes = [wp, i32, i32, C.c_char_p, sz]
     lib.qllm_plan_describe.restype = C.c_int
     lib.qllm_plan_describe.argtypes = [wp, i32, i32, i32, C.c_char_p, sz]
     lib.qllm_debug_timeline.restype = C.c_int

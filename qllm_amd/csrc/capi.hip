@@ -874,6 +874,72 @@ int qllm_swiglu_describe(const qllm_weight_t *w, int32_t M, char *buf, size_t bu
   return QLLM_OK;
 }
 
+// y = weight * round(x * rstd) per row: the standalone RMSNorm kernel (rmsnorm.hip)
+int qllm_rmsnorm(const void *x, const void *weight, void *y, int32_t M, int32_t K, float eps, int32_t act_dtype, float *rstd_out, void *stream) {
+  clear_error();
+  if (!x || !weight || !y) return set_error(QLLM_ERR_INVALID, "x / weight / y must not be NULL");
+  if (M <= 0 || K <= 0) return set_error(QLLM_ERR_INVALID, "M and K must be >= 1 (got M=%d K=%d)", M, K);
+  if (act_dtype != QLLM_F16 && act_dtype != QLLM_BF16) return set_error(QLLM_ERR_INVALID, "act_dtype must be QLLM_F16 or QLLM_BF16");
+  if ((uintptr_t)x % 16 || (uintptr_t)weight % 16 || (uintptr_t)y % 16) return set_error(QLLM_ERR_INVALID, "x / weight / y must be 16-byte aligned");
+  if ((uintptr_t)rstd_out % 4) return set_error(QLLM_ERR_INVALID, "rstd_out must be 4-byte aligned");
+  if (K % 8 != 0) return set_error(QLLM_ERR_INVALID, "K must be a multiple of 8 (whole 16-byte chunks; got %d)", K);
+  if (!(eps >= 0.f)) return set_error(QLLM_ERR_INVALID, "eps must be >= 0");
+  if (K > kRmsNormMaxK) return set_error(QLLM_ERR_UNSUPPORTED, "rmsnorm serves K <= %d (got %d)", kRmsNormMaxK, K);
+  return launch_rmsnorm(x, weight, y, M, K, eps, act_dtype == QLLM_BF16, rstd_out, (hipStream_t)stream);
+}
+
+// y_i = linear(w_i, RMSNorm(x)): the NORM forms of the batch-1 kernel (strip1_norm.hip); decide_rmsnorm says what is served
+int qllm_linear_forward_rmsnorm(const qllm_weight_t *w, void *const *y, int32_t n_weights, const void *x, const void *norm_weight, float eps,
+                                int32_t M, int32_t act_dtype, float *rstd_out, void *stream) {
+  clear_error();
+  if (!w || !y) return set_error(QLLM_ERR_INVALID, "w / y arrays must not be NULL");
+  if (n_weights < 1 || n_weights > kMaxProblems) return set_error(QLLM_ERR_INVALID, "n_weights must be 1..%d (got %d)", kMaxProblems, n_weights);
+  if (!norm_weight) return set_error(QLLM_ERR_INVALID, "norm_weight must not be NULL");
+  for (int i = 0; i < n_weights; ++i) {
+    int rc = validate_weight(&w[i]);
+    if (rc) return rc;
+    rc = check_io(x, y[i], M, act_dtype);
+    if (rc) return rc;
+    if (y[i] == x || y[i] == norm_weight) return set_error(QLLM_ERR_INVALID, "y must not alias x / norm_weight (every block reads the whole row)");
+  }
+  if ((uintptr_t)norm_weight % 16 != 0) return set_error(QLLM_ERR_INVALID, "norm_weight must be 16-byte aligned");
+  if ((uintptr_t)rstd_out % 4) return set_error(QLLM_ERR_INVALID, "rstd_out must be 4-byte aligned");
+  if (!(eps >= 0.f)) return set_error(QLLM_ERR_INVALID, "eps must be >= 0");
+  if (w[0].K % 8 != 0) return set_error(QLLM_ERR_INVALID, "K must be a multiple of 8 (got %d)", w[0].K);
+  Decision d;
+  int rc = decide_rmsnorm(w, n_weights, M, &d);
+  if (rc) return rc;
+  Strip1Params p;
+  const int max_strips = fill_strip1_params(p, w, y, n_weights, x, M, act_dtype);
+  p.norm_w = norm_weight;
+  p.norm_eps = eps;
+  p.rstd_out = rstd_out;
+  return launch_strip1_norm(p, d.strip.one_nw, d.strip.one_maxs, n_weights, max_strips, (hipStream_t)stream);
+}
+
+// what that call would launch, as text ("rmsnorm " + the plain grouped call's plan line), or why it is refused -- no device work
+int qllm_rmsnorm_describe(const qllm_weight_t *w, int32_t n_weights, int32_t M, char *buf, size_t buflen) {
+  clear_error();
+  if (!w || !buf || buflen < 64) return set_error(QLLM_ERR_INVALID, "w / buf must not be NULL (buf >= 64 bytes)");
+  if (n_weights < 1 || n_weights > kMaxProblems) return set_error(QLLM_ERR_INVALID, "n_weights must be 1..%d (got %d)", kMaxProblems, n_weights);
+  if (M <= 0) return set_error(QLLM_ERR_INVALID, "M must be >= 1 (got %d)", M);
+  int rc = QLLM_OK;
+  for (int i = 0; i < n_weights && rc == QLLM_OK; ++i) rc = validate_weight(&w[i]);
+  if (rc == QLLM_OK) {
+    Decision d;
+    rc = decide_rmsnorm(w, n_weights, M, &d);
+    if (rc == QLLM_OK) {
+      const int n = snprintf(buf, buflen, "rmsnorm ");
+      describe(d, w, n_weights, M, 0, buf + n, buflen - n);
+      clear_error();
+      return QLLM_OK;
+    }
+  }
+  if (rc != QLLM_ERR_UNSUPPORTED) return rc;
+  snprintf(buf, buflen, "refused: %s", last_error_text());
+  return QLLM_OK;
+}
+
 int qllm_dequant(const qllm_weight_t *w, void *out, int32_t out_dtype, int32_t out_transposed, void *stream) {
   clear_error();
   int rc = validate_weight(w);

@@ -129,6 +129,11 @@ struct Strip1Params {
   // act(gate) * up staged in-kernel (the SWIGLU forms, strip1_swiglu.hip: x is the gate vector): the up vector, shaped like x.  Read by
   // those forms only
   const void *x2;
+  // RMSNorm staged in-kernel (the NORM forms, strip1_norm.hip: x is the un-normed row): the norm's weight [K] in the activation type, its
+  // epsilon, and where block 0 of problem 0 reports the row's rstd (nullable).  Read by those forms only
+  const void *norm_w;
+  float norm_eps;
+  float *rstd_out;
 };
 
 // ---- bitgemv.hip (round 6): fused decode matvec for the widths the MFMA strips do not take (2, 5, 6, 7, 8 bits; row-stream layouts) -----
@@ -261,6 +266,11 @@ bool strip1_shape(int K, int blocks, int cus, int *nw, int *maxs, bool odd64 = f
 int launch_strip1(const Strip1Params &p, int nw, int maxs, int n_prob, int max_strips, hipStream_t stream);
 int launch_strip1_allreduce(const Strip1Params &p, int nw, int maxs, int n_strips, hipStream_t stream);  // (p.ar_* set; one layer)
 int launch_strip1_swiglu(const Strip1Params &p, int nw, int maxs, int n_strips, hipStream_t stream);     // strip1_swiglu.hip (p.x2 set; one layer)
+int launch_strip1_norm(const Strip1Params &p, int nw, int maxs, int n_prob, int max_strips, hipStream_t stream);  // strip1_norm.hip (p.norm_* set; M = 1)
+
+// ---- rmsnorm.hip: y = weight * round(x * rstd), one block per row (the standalone counterpart of the NORM forms) ------------------------
+constexpr int kRmsNormMaxK = 65536;
+int launch_rmsnorm(const void *x, const void *weight, void *y, int M, int K, float eps, int act_bf16, float *rstd_out, hipStream_t stream);
 
 // ---- native.hip (reference layouts <-> the strip-major native layout) -------------------------------------------------------
 int launch_repack_native(const qllm_weight_t &src, int zero_kind, void *qweight_out, void *scales_out, void *qzeros_out, hipStream_t stream);

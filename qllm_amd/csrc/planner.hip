@@ -584,6 +584,29 @@ int decide_swiglu(const qllm_weight_t *w, int M, int act, StripPlan *plan) {
   return QLLM_OK;
 }
 
+// The fused RMSNorm in front of a sibling group (strip1_norm.hip): exactly the M = 1 calls decide_single / decide_group put on the batch-1
+// kernel for native-layout layers, with the same waves x round, so that the fused launch is the plain grouped launch's arithmetic on
+// RMSNorm(x).  Everything else keeps qllm_rmsnorm and today's launch.
+int decide_rmsnorm(const qllm_weight_t *w, int n, int M, Decision *d) {
+  static const char kInstead[] = "run qllm_rmsnorm and qllm_linear_forward_grouped";
+  *d = refused(QLLM_ERR_UNSUPPORTED);
+  if (M != 1) return set_error(QLLM_ERR_UNSUPPORTED, "fused RMSNorm: one row only (M=%d; the four-row forms are not built); %s", M, kInstead);
+  for (int i = 0; i < n; ++i) {
+    if (!is_native(w[i]))
+      return set_error(QLLM_ERR_UNSUPPORTED, "fused RMSNorm: native-layout layers only (member %d: layout=%d bits=%d); %s", i, w[i].layout, w[i].bits, kInstead);
+    if (w[i].K != w[0].K || w[i].group_size != w[0].group_size || w[i].bits != w[0].bits || w[i].add_zero_bias != w[0].add_zero_bias)
+      return set_error(QLLM_ERR_UNSUPPORTED, "fused RMSNorm: the members must agree on K, group_size, bits and add_zero_bias (member %d: K=%d g=%d bits=%d against K=%d g=%d bits=%d); %s",
+                       i, w[i].K, w[i].group_size, w[i].bits, w[0].K, w[0].group_size, w[0].bits, kInstead);
+  }
+  const Decision plain = n == 1 ? decide_single(w, 1, QLLM_F16) : decide_group(w, n, 1, QLLM_F16);
+  if (plain.route != ROUTE_STRIP || !plain.strip.one_nw)
+    return set_error(QLLM_ERR_UNSUPPORTED, "fused RMSNorm: calls of the batch-1 kernel only -- 4 bits with 128- / 64-wide groups and 3 bits, K within its shape table, "
+                     "QLLM_STRIP1 on (bits=%d g=%d K=%d layout=%d, %d layers); %s", w[0].bits, w[0].group_size, w[0].K, w[0].layout, n, kInstead);
+  *d = plain;
+  clear_error();
+  return QLLM_OK;
+}
+
 void describe(const Decision &d, const qllm_weight_t *w, int n, int M, size_t ws_bytes, char *buf, size_t buflen) {
   const char *sm = is_native(w[0]) ? " layout=strip-major" : "";
   switch (d.route) {

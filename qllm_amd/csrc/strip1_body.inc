@@ -1,10 +1,11 @@
-// The body of strip1_kernel and strip1_swiglu_kernel (strip1_kernel.hpp, which documents it): included inside both, with NW, MAXS,
-// EXACT, NCH, LVL, DBG, AR, G64, MR, B3 and SWIGLU constants of the enclosing function and `p` its Strip1Params.
+// The body of strip1_kernel, strip1_swiglu_kernel and strip1_norm_kernel (strip1_kernel.hpp, which documents it): included inside all
+// three, with NW, MAXS, EXACT, NCH, LVL, DBG, AR, G64, MR, B3, SWIGLU, NORM and NORM_PARK constants of the enclosing function and `p` its Strip1Params.
   static_assert(MAXS % 4 == 0 && MAXS >= 8 && MAXS <= 64, "rounds are whole 128-wide groups, at most 16 of them (round 6: 40 .. 64 k-steps for K up to 32768)");
   static_assert(!(G64 && AR), "the fused all-reduce form is built for 128-wide groups");
   static_assert(MR == 1 || (MR == 4 && !G64 && !AR && !DBG && LVL == 4), "four batch rows: 128-wide groups, the plain form");
   static_assert(!B3 || (MR == 1 && !AR && !DBG && LVL == 4), "3 bits: the plain batch-1 form");
   static_assert(!SWIGLU || (!AR && !DBG && LVL == 4), "act(gate) * up: the plain forms");
+  static_assert(!NORM || (!SWIGLU && MR == 1 && !AR && !DBG && LVL == 4), "RMSNorm(x): the plain batch-1 forms");
   constexpr int KPG = G64 ? 2 : 4;        // k-steps per group
   constexpr int NG = MAXS / KPG;          // groups per wave
   constexpr int NPASS = (MAXS + 15) / 16; // accumulator sets: one per 16 k-steps (four 128-wide groups / eight 64-wide ones)
@@ -23,6 +24,7 @@
   asm volatile("" ::"s"(pr.qweight), "s"(pr.scales), "s"(pr.qzeros), "s"(pr.bias), "s"(pr.y), "s"(pr.n_strips), "s"(pr.zero_kind), "s"(p.x),
                "s"(p.T), "s"(p.n_groups), "s"(p.add_zero_bias), "s"(p.act_bf16));
   if constexpr (SWIGLU) asm volatile("" ::"s"(p.x2));  // (the up vector's base: the same batch)
+  if constexpr (NORM) asm volatile("" ::"s"(p.norm_w), "s"(p.norm_eps), "s"(p.rstd_out));  // (the norm's weight, epsilon, report slot)
   // the two flags the uniform branches and the tail read: taken from the first batch of scalar loads (as outputs of an asm they cannot
   // be re-loaded next to their use -- hipcc otherwise sinks a second s_load of each into the decode branch and in front of the y store)
   int add_zero_bias = p.add_zero_bias, act_bf16 = p.act_bf16;
@@ -43,7 +45,7 @@
   const int tb = EXACT ? t0 : min(t0, T - MAXS);           // its window [tb, tb + MAXS): shifted back into the strip at the end of K
   // ---- every load of the wave, back to back: x chunk(s), one scale + one zero word per pass, MAXS weight words -----------------
   uint4_t xa[MR][XL];
-  uint4_t xb[SWIGLU ? MR : 1][SWIGLU ? XL : 1];             // (SWIGLU: the up vector's chunks)
+  uint4_t xb[SWIGLU ? MR : 1][(SWIGLU || NORM) ? XL : 1];   // (SWIGLU: the up vector's chunks; NORM: the norm weight's)
   bool xkeep[XL];
 #pragma unroll
   for (int u = 0; u < XL; ++u) {
@@ -58,6 +60,7 @@
         if (MR == 1 || m < p.M) xb[m][u] = *(const uint4_t *)((const uint16_t *)p.x2 + (size_t)m * 32 * T + 32 * tb + 8 * cc);
       }
     }
+    if constexpr (NORM) xb[0][u] = *(const uint4_t *)((const uint16_t *)p.norm_w + 32 * tb + 8 * cc);   // (a [K] vector: no row term)
     const int t = tb + (c >> 2);
     xkeep[u] = EXACT ? (c < MAXS * 4) : (c < MAXS * 4 && t >= t0 && t < T);
   }
@@ -160,6 +163,61 @@
             xa[m][u] = swiglu_chunk<false>(xa[m][u], ub);
             asm volatile("" : "+v"(xa[m][u]));
           }
+      }
+    }
+    if constexpr (NORM) {
+      // RMSNorm(x) in place of the x chunk (strip1_kernel.hpp, NORM).  PARK as for SWIGLU: the weight's chunks wait in the chunk's own slot
+      // of the wave's staging area across the sum and the barrier
+      constexpr bool PARK = NORM_PARK;
+#pragma unroll
+      for (int u = 0; u < XL; ++u) asm volatile("" : "+v"(xb[0][u]));
+      if constexpr (PARK) {
+#pragma unroll
+        for (int u = 0; u < XL; ++u) *(uint4_t *)(wbase + 16 * (lane + 64 * u)) = xb[0][u];
+        asm volatile("" ::: "memory");
+      }
+      float ss = 0.f;   // the lane's kept elements, chunk by chunk, element by element
+      if (act_bf16) {
+#pragma unroll
+        for (int u = 0; u < XL; ++u) { float q = sumsq_chunk<true>(xa[0][u]); asm volatile("" : "+v"(q)); ss += xkeep[u] ? q : 0.f; }
+      } else {
+#pragma unroll
+        for (int u = 0; u < XL; ++u) { float q = sumsq_chunk<false>(xa[0][u]); asm volatile("" : "+v"(q)); ss += xkeep[u] ? q : 0.f; }
+      }
+      // the wave's sum: all-reduce over each 16-lane row (xor 1, xor 2, half-row mirror, row mirror), then the four rows in order
+      ss = dpp_add1<0xB1>(ss);
+      ss = dpp_add1<0x4E>(ss);
+      ss = dpp_add1<0x141>(ss);
+      ss = dpp_add1<0x140>(ss);
+      const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ss), 0));
+      const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ss), 16));
+      const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ss), 32));
+      const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ss), 48));
+      float *part = (float *)((char *)lds + strip1_lds_bytes<NW, MAXS, MR>());   // (LDS of its own: NW floats behind the staging areas)
+      if (lane == 0) part[wave] = (r0 + r1) + (r2 + r3);
+      __syncthreads();   // (every wave of the block is here: the surplus-block test above is block-uniform)
+      float tot = part[0];
+#pragma unroll
+      for (int q = 1; q < NW; ++q) tot += part[q];   // index order: the same bits in every wave of every block of the launch
+      const float rstd = rms_rstd(tot, 32 * T, p.norm_eps);
+      if (p.rstd_out && b == 0 && blockIdx.y == 0 && threadIdx.x == 0) *p.rstd_out = rstd;
+      // (the chunks are opaque again: nothing the sum derived from them -- their fp32 conversions -- is kept in registers across the barrier)
+#pragma unroll
+      for (int u = 0; u < XL; ++u) asm volatile("" : "+v"(xa[0][u]));
+      if (act_bf16) {
+#pragma unroll
+        for (int u = 0; u < XL; ++u) {
+          const uint4_t wb = PARK ? *(const uint4_t *)(wbase + 16 * (lane + 64 * u)) : xb[0][u];
+          xa[0][u] = norm_chunk<true>(xa[0][u], wb, rstd);
+          asm volatile("" : "+v"(xa[0][u]));
+        }
+      } else {
+#pragma unroll
+        for (int u = 0; u < XL; ++u) {
+          const uint4_t wb = PARK ? *(const uint4_t *)(wbase + 16 * (lane + 64 * u)) : xb[0][u];
+          xa[0][u] = norm_chunk<false>(xa[0][u], wb, rstd);
+          asm volatile("" : "+v"(xa[0][u]));
+        }
       }
     }
     // bf16 activations: converted in place behind ONE wave-uniform branch (the asm keeps hipcc from turning the branch back into

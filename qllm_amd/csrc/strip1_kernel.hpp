@@ -76,6 +76,52 @@ __device__ __forceinline__ uint4_t swiglu_chunk(uint4_t g, uint4_t u) {
   return uint4_t{swiglu_pair<BF16>(g.x, u.x), swiglu_pair<BF16>(g.y, u.y), swiglu_pair<BF16>(g.z, u.z), swiglu_pair<BF16>(g.w, u.w)};
 }
 
+// NORM (the fused RMSNorm entry, strip1_norm.hip): the sum of the fp32 squares of one chunk's eight elements, in element order (an fp16 /
+// bf16 square is exact in fp32), and one 32-bit pair of the row and of the norm's weight -> weight * round(x * rstd) as the eager
+// LlamaRMSNorm rounds it: x * rstd in fp32, rounded to the activation type, the product with the weight in fp32, rounded again.
+template <bool BF16>
+__device__ __forceinline__ float sumsq_chunk(uint4_t x) {
+  const uint32_t wds[4] = {x.x, x.y, x.z, x.w};
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    float lo, hi;
+    if constexpr (BF16) {
+      lo = __builtin_bit_cast(float, wds[j] << 16);
+      hi = __builtin_bit_cast(float, wds[j] & 0xffff0000u);
+    } else {
+      const half2_t h = as_h2(wds[j]);
+      lo = (float)h.x;
+      hi = (float)h.y;
+    }
+    s += lo * lo;
+    s += hi * hi;
+  }
+  return s;
+}
+template <bool BF16>
+__device__ __forceinline__ uint32_t norm_pair(uint32_t x2, uint32_t w2, float rstd) {
+  if constexpr (BF16) {
+    const float x0 = __builtin_bit_cast(float, x2 << 16), x1 = __builtin_bit_cast(float, x2 & 0xffff0000u);
+    const float w0 = __builtin_bit_cast(float, w2 << 16), w1 = __builtin_bit_cast(float, w2 & 0xffff0000u);
+    const float h0 = __builtin_bit_cast(float, (uint32_t)f32_to_bf16(x0 * rstd) << 16);
+    const float h1 = __builtin_bit_cast(float, (uint32_t)f32_to_bf16(x1 * rstd) << 16);
+    return (uint32_t)f32_to_bf16(w0 * h0) | ((uint32_t)f32_to_bf16(w1 * h1) << 16);
+  } else {
+    const half2_t x = as_h2(x2), w = as_h2(w2);
+    const half_t h0 = (half_t)((float)x.x * rstd), h1 = (half_t)((float)x.y * rstd);
+    return as_u32(half2_t{(half_t)((float)w.x * (float)h0), (half_t)((float)w.y * (float)h1)});
+  }
+}
+template <bool BF16>
+__device__ __forceinline__ uint4_t norm_chunk(uint4_t x, uint4_t w, float rstd) {
+  return uint4_t{norm_pair<BF16>(x.x, w.x, rstd), norm_pair<BF16>(x.y, w.y, rstd), norm_pair<BF16>(x.z, w.z, rstd), norm_pair<BF16>(x.w, w.w, rstd)};
+}
+// rstd of a row from the sum of its squares (both RMSNorm kernels): the eager rsqrt(mean + eps), in fp32
+__device__ __forceinline__ float rms_rstd(float sumsq, int K, float eps) { return rsqrtf(sumsq / (float)K + eps); }
+// bytes of LDS the NORM forms add behind strip1_lds_bytes: one partial sum of squares per wave (NW <= 16 floats)
+constexpr int kStrip1NormLdsBytes = 64;
+
 // NW waves x MAXS k-steps cover T (host: NW * MAXS >= T >= MAXS; EXACT: NW * MAXS == T, no masking of a shifted window)
 // AR: the row-parallel form (one layer per launch, p.ar_* set): instead of storing y the block pushes its 16 partial outputs, rounded to
 //     the activation type like the unfused path's y, into slot [parity][rank] of EVERY peer's staging buffer (comm.hip's layout and
@@ -102,17 +148,39 @@ __device__ __forceinline__ uint4_t swiglu_chunk(uint4_t g, uint4_t u) {
 //     forms are kernels of their own (strip1_swiglu_kernel below, instantiated in strip1_swiglu.hip) around the same body: the body is
 //     strip1_body.inc, included by both kernels with SWIGLU a constant of the enclosing function, so that strip1_kernel's template
 //     parameters -- and with them the names and the code of every instantiation strip1.hip builds -- stay what they were.
+// NORM: the activation is RMSNorm(x) of the un-normed row p.x with the norm's weight p.norm_w ([K], the activation type) and p.norm_eps;
+//     batch 1 only (M = 2..4 -- the four-row forms -- is not built: it would double the instantiations, and the modules send one row).  The
+//     weight's chunks are loaded with the x chunks (same window, same clamp).  Once its x chunks have arrived a wave sums the fp32 squares of
+//     the elements it KEEPS (xkeep: the windows of non-EXACT forms overlap, and a shifted last window re-reads k-steps of its neighbour --
+//     every k-step is owned by exactly one wave, so every element is counted once), reduces over its lanes (DPP over the 16-lane rows,
+//     then the four rows in order) and writes ONE partial to LDS of its own behind the staging areas (kStrip1NormLdsBytes; the reduction
+//     buffer at the start of `lds` is written by fast waves at the end of the kernel, possibly before a slow wave has read the partials).
+//     One __syncthreads() -- behind the surplus-block test, which a whole block passes or leaves together -- then every wave sums the NW
+//     partials in index order: the order depends on (NW, MAXS, T) only, so every block of the launch, whichever sibling it serves, forms
+//     the same rstd bit for bit; block 0 of problem 0 reports it (p.rstd_out).  Each chunk is then rewritten in registers as
+//     weight * round(x * rstd) (norm_pair: the two roundings of the eager expression, in the activation type, before the bf16 -> fp16
+//     conversion), and from there on the kernel is the plain form's code: a NORM launch returns bit for bit what the plain grouped launch
+//     returns on xn = weight * (x.float() * rstd).to(dtype).  Kernels of their own (strip1_norm_kernel below, strip1_norm.hip), as for SWIGLU.
 template <int NW, int MAXS, bool EXACT, int NCH = 2, int LVL = 4, bool DBG = false, bool AR = false, bool G64 = false, int MR = 1, bool B3 = false>
 // (second launch bound = minimum waves per SIMD: 64 registers up to rounds of 24 k-steps -- a CU full of waves -- 128 above)
 __global__ __launch_bounds__(NW * 64, (MAXS <= 24 && !G64 && MR == 1 && !B3) ? 8 : 4) void strip1_kernel(const Strip1Params p) {
-  constexpr bool SWIGLU = false;
+  constexpr bool SWIGLU = false, NORM = false, NORM_PARK = false;
 #include "strip1_body.inc"
 }
 
 // the SWIGLU forms (WAVES: the second launch bound, chosen per form from the compiler's report -- strip1_swiglu.hip)
 template <int NW, int MAXS, bool EXACT, bool G64, int MR, bool B3, int WAVES>
 __global__ __launch_bounds__(NW * 64, WAVES) void strip1_swiglu_kernel(const Strip1Params p) {
-  constexpr bool SWIGLU = true, DBG = false, AR = false;
+  constexpr bool SWIGLU = true, NORM = false, NORM_PARK = false, DBG = false, AR = false;
+  constexpr int NCH = 2, LVL = 4;
+#include "strip1_body.inc"
+}
+
+// the NORM forms (grouped launch: blockIdx.y is the sibling; WAVES as above -- strip1_norm.hip)
+template <int NW, int MAXS, bool EXACT, bool G64, int MR, bool B3, int WAVES>
+__global__ __launch_bounds__(NW * 64, WAVES) void strip1_norm_kernel(const Strip1Params p) {
+  constexpr bool SWIGLU = false, NORM = true, DBG = false, AR = false;
+  constexpr bool NORM_PARK = MAXS >= 64 || (MAXS == 24 && !G64 && !B3);   // (the forms whose twins sit next to their register bound)
   constexpr int NCH = 2, LVL = 4;
 #include "strip1_body.inc"
 }

@@ -438,6 +438,85 @@ def swiglu_describe(w: QllmWeight, m: int) -> str:
     return buf.value.decode()
 
 
+def _rstd_buffer(return_rstd, m: int, x2d: torch.Tensor):
+    """return_rstd of the two RMSNorm wrappers: False (None), True (a new fp32 [m] tensor) or the caller's contiguous fp32 [m] tensor."""
+    if return_rstd is False or return_rstd is None:
+        return None
+    if return_rstd is True:
+        return torch.empty((m,), dtype=torch.float32, device=x2d.device)
+    r = return_rstd
+    if r.dtype != torch.float32 or tuple(r.shape) != (m,) or r.device != x2d.device or not r.is_contiguous():
+        raise RuntimeError(f"return_rstd must be True or a contiguous float32 [{m}] tensor on {x2d.device}")
+    return r
+
+
+def _check_norm_weight(weight: torch.Tensor, x2d: torch.Tensor):
+    _check_input(weight, "weight")
+    if weight.dim() != 1 or weight.shape[0] != x2d.shape[1] or weight.dtype != x2d.dtype or weight.device != x2d.device:
+        raise RuntimeError(f"weight must be a [{x2d.shape[1]}] {x2d.dtype} tensor on {x2d.device}, got {tuple(weight.shape)} {weight.dtype} on {weight.device}")
+
+
+def rmsnorm(x: torch.Tensor, weight: torch.Tensor, eps: float, out: Optional[torch.Tensor] = None, return_rstd: bool = False):
+    """weight * (x.float() * rsqrt(mean(x^2) + eps)).to(dtype) over the last dimension in ONE kernel (qllm_rmsnorm, csrc/rmsnorm.hip): the
+    eager LlamaRMSNorm's arithmetic, rounding for rounding.  x: contiguous fp16 / bf16 [..., K] on the device, K % 8 == 0, K <= 65536;
+    weight: [K] of x's type; `out` may be x itself.  return_rstd: also the rows' rstd, fp32 [rows] (True, or the caller's tensor to write them into)."""
+    _check_input(x, "x")
+    if x.dim() < 1:
+        raise RuntimeError("x must have at least one dimension")
+    x2d = x.view(-1, x.shape[-1])
+    _check_norm_weight(weight, x2d)
+    m, k = x2d.shape
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape or out.dtype != x.dtype or out.device != x.device or not out.is_contiguous():
+        raise RuntimeError(f"out must be a contiguous {tuple(x.shape)} {x.dtype} tensor on {x.device}, got {tuple(out.shape)} {out.dtype} on {out.device}")
+    rstd = _rstd_buffer(return_rstd, m, x2d)
+    if m > 0:
+        with torch.cuda.device(x.device):
+            rc = _lib.load().qllm_rmsnorm(x2d.data_ptr(), weight.data_ptr(), out.data_ptr(), m, k, float(eps), _act_dtype(x2d),
+                                          rstd.data_ptr() if rstd is not None else None, _stream_ptr())
+        _lib.check(rc)
+    return (out, rstd) if rstd is not None else out
+
+
+def linear_forward_rmsnorm(ws_desc: Sequence[QllmWeight], x2d: torch.Tensor, weight: torch.Tensor, eps: float,
+                           outs: Optional[Sequence[torch.Tensor]] = None, return_rstd: bool = False):
+    """[linear(w, RMSNorm(x2d)) for w in ws_desc] in ONE launch (qllm_linear_forward_rmsnorm, csrc/strip1_norm.hip): the grouped launch of
+    the layers behind a norm (q/k/v, gate/up) with the norm formed while the batch-1 kernel stages its input.  Bit-identical to
+    `linear_forward_grouped(ws_desc, weight * (x2d.float() * rstd).to(x2d.dtype))` with the rstd it reports (return_rstd: fp32 [M]
+    behind the outputs).  One row; raises QllmUnsupported for every call the batch-1 kernel does not serve (callers then run `rmsnorm`
+    and `linear_forward_grouped`)."""
+    _check_x(x2d, ws_desc)
+    _check_norm_weight(weight, x2d)
+    n = len(ws_desc)
+    m = x2d.shape[0]
+    if outs is not None:
+        if len(outs) != n:
+            raise RuntimeError(f"outs must hold {n} tensors, got {len(outs)}")
+        for o, w in zip(outs, ws_desc):
+            _check_out(o, m, w.N, x2d)
+    else:
+        outs = [torch.empty((m, w.N), dtype=x2d.dtype, device=x2d.device) for w in ws_desc]
+    rstd = _rstd_buffer(return_rstd, m, x2d)
+    if m > 0:
+        arr = (QllmWeight * n)(*ws_desc)
+        ys = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
+        with torch.cuda.device(x2d.device):
+            rc = _lib.load().qllm_linear_forward_rmsnorm(arr, ys, n, x2d.data_ptr(), weight.data_ptr(), float(eps), m, _act_dtype(x2d),
+                                                         rstd.data_ptr() if rstd is not None else None, _stream_ptr())
+        _lib.check(rc)
+    return (list(outs), rstd) if rstd is not None else list(outs)
+
+
+def rmsnorm_describe(ws_desc: Sequence[QllmWeight], m: int) -> str:
+    """What `linear_forward_rmsnorm` would launch for m rows: "rmsnorm " + the plan line of the plain grouped call ("rmsnorm strip1 nw=..
+    round=.. ..."), or "refused: ..." with the entry's refusal text.  Pure host code."""
+    n = len(ws_desc)
+    buf = C.create_string_buffer(768)
+    _lib.check(_lib.load().qllm_rmsnorm_describe((QllmWeight * n)(*ws_desc), n, int(m), buf, 768))
+    return buf.value.decode()
+
+
 def dequant(w: QllmWeight, device: torch.device, dtype=torch.float16, transposed: bool = False) -> torch.Tensor:
     """W[K,N] (or [N,K]) bit-identical to the reference's DequantizeLinearBlockWise / unpack()."""
     lib = _lib.load()
@@ -764,6 +843,6 @@ def unpack_native(w: QllmWeight, keep, layout: str):
     return qweight, scales, qzeros
 
 
-__all__ = ["make_weight", "linear_forward", "linear_forward_grouped", "linear_forward_permuted", "linear_forward_bitpanel", "bitpanel_describe", "linear_forward_bitgemm", "bitgemm_describe", "bitgemm_min_m", "linear_forward_bitgroup", "bitgroup_describe", "linear_forward_swiglu", "swiglu_describe", "linear_forward_shared", "dequant", "gather_columns", "unpack_qweight", "pack_qweight",
+__all__ = ["make_weight", "linear_forward", "linear_forward_grouped", "linear_forward_permuted", "linear_forward_bitpanel", "bitpanel_describe", "linear_forward_bitgemm", "bitgemm_describe", "bitgemm_min_m", "linear_forward_bitgroup", "bitgroup_describe", "linear_forward_swiglu", "swiglu_describe", "rmsnorm", "linear_forward_rmsnorm", "rmsnorm_describe", "linear_forward_shared", "dequant", "gather_columns", "unpack_qweight", "pack_qweight",
            "workspace", "QllmUnsupported", "LAYOUTS", "plan_describe", "repack_native", "unpack_native", "hqq_quantize", "gptq_quantize",
            "gptq_quantize_static", "awq_quantize", "awq_clip_search"]
