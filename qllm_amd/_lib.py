@@ -22,25 +22,6 @@ BITGEMM_MIN_M_DEFAULT = 0      # QLLM_BITGEMM_MIN_M_DEFAULT of include/qllm_mi35
 ACT_SILU = 0                   # QLLM_ACT_SILU of include/qllm_mi355x.h (qllm_linear_forward_swiglu)
 BITGROUP_MAX_M_DEFAULT = 16    # QLLM_BITGROUP_MAX_M_DEFAULT of include/qllm_mi355x.h: the measured line of profiles/bitgemv_group.md (0: sibling groups do not route)
 
-EXPORTS = (
-    "qllm_abi_version", "qllm_is_lab_build", "qllm_last_error", "qllm_device_info", "qllm_workspace_bytes", "qllm_workspace_bytes_act", "qllm_workspace_init",
-    "qllm_linear_forward", "qllm_linear_forward_grouped", "qllm_dequant", "qllm_ort_gemv", "qllm_ort_dequant",
-    "qllm_awq_gemm_forward", "qllm_unpack_qweight", "qllm_pack_qweight", "qllm_gather_columns", "qllm_ort_dequantize4bits",
-    "qllm_plan_describe", "qllm_debug_timeline", "qllm_native_sizes", "qllm_repack_native", "qllm_unpack_native",
-    "qllm_comm_buffer_bytes", "qllm_comm_alloc", "qllm_comm_free", "qllm_comm_export", "qllm_comm_import", "qllm_comm_close",
-    "qllm_allreduce_oneshot", "qllm_linear_forward_allreduce", "qllm_convert_bf16_to_f16",
-    "qllm_set_knob", "qllm_get_knob", "qllm_reset_knobs",
-    "qllm_hqq_quantize_workspace_bytes", "qllm_hqq_quantize", "qllm_gptq_quantize_workspace_bytes", "qllm_gptq_quantize",
-    "qllm_gptq_quantize_static",
-    "qllm_linear_forward_permuted",
-    "qllm_linear_forward_bitpanel", "qllm_bitpanel_workspace_bytes", "qllm_bitpanel_describe",
-    "qllm_linear_forward_bitgroup", "qllm_bitgroup_workspace_bytes", "qllm_bitgroup_describe",
-    "qllm_linear_forward_bitgemm", "qllm_bitgemm_workspace_bytes", "qllm_bitgemm_describe",
-    "qllm_awq_clip_search_workspace_bytes", "qllm_awq_clip_search", "qllm_awq_quantize",
-    "qllm_linear_forward_swiglu", "qllm_swiglu_describe",
-    "qllm_rmsnorm", "qllm_linear_forward_rmsnorm", "qllm_rmsnorm_describe",
-)
-
 
 class QllmWeight(C.Structure):
     """struct qllm_weight (include/qllm_mi355x.h)."""
@@ -59,6 +40,73 @@ class QllmDeviceInfo(C.Structure):
     ]
 
 
+# The C ABI as ctypes sees it: name -> (restype, argtypes).  The ONE list of symbols: EXPORTS (what
+# tests/test_capi_symbols.py holds against include/qllm_mi355x.h) is its keys and _declare() walks it, so no symbol can be exported
+# without argtypes -- ctypes would pass its 64-bit pointers as C int.
+vp, i32, sz = C.c_void_p, C.c_int32, C.c_size_t
+wp = C.POINTER(QllmWeight)
+SIGNATURES = {
+    "qllm_abi_version": (C.c_int, []),
+    "qllm_is_lab_build": (C.c_int, []),
+    "qllm_last_error": (C.c_char_p, []),
+    "qllm_device_info": (C.c_int, [C.c_int, C.POINTER(QllmDeviceInfo)]),
+    "qllm_workspace_bytes": (sz, [wp, i32]),
+    "qllm_workspace_bytes_act": (sz, [wp, i32, i32]),
+    "qllm_workspace_init": (C.c_int, [vp, sz, vp]),
+    "qllm_linear_forward": (C.c_int, [wp, vp, vp, i32, i32, vp, sz, vp]),
+    "qllm_linear_forward_grouped": (C.c_int, [wp, C.POINTER(vp), i32, vp, i32, i32, vp, sz, vp]),
+    "qllm_dequant": (C.c_int, [wp, vp, i32, i32, vp]),
+    "qllm_ort_gemv": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, i32, i32, vp, sz, vp]),
+    "qllm_ort_dequant": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp]),
+    "qllm_awq_gemm_forward": (C.c_int, [vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp, sz, vp]),
+    "qllm_unpack_qweight": (C.c_int, [vp, i32, i32, i32, i32, vp, vp]),
+    "qllm_pack_qweight": (C.c_int, [vp, i32, i32, i32, i32, vp, vp]),
+    "qllm_gather_columns": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),
+    "qllm_ort_dequantize4bits": (C.c_int, [vp, vp, vp, i32, vp, i32, i32, i32, vp, vp]),
+    "qllm_plan_describe": (C.c_int, [wp, i32, i32, i32, C.c_char_p, sz]),
+    "qllm_debug_timeline": (C.c_int, [vp, i32]),
+    "qllm_native_sizes": (C.c_int, [wp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]),
+    "qllm_repack_native": (C.c_int, [wp, vp, vp, vp, vp]),
+    "qllm_unpack_native": (C.c_int, [wp, i32, vp, vp, vp, vp]),
+    "qllm_comm_buffer_bytes": (sz, [i32, sz]),
+    "qllm_comm_alloc": (C.c_int, [sz, C.POINTER(vp)]),
+    "qllm_comm_free": (C.c_int, [vp]),
+    "qllm_comm_export": (C.c_int, [vp, vp]),
+    "qllm_comm_import": (C.c_int, [vp, C.POINTER(vp)]),
+    "qllm_comm_close": (C.c_int, [vp]),
+    "qllm_allreduce_oneshot": (C.c_int, [vp, i32, i32, vp, i32, i32, sz, vp, vp]),
+    "qllm_linear_forward_allreduce": (C.c_int, [wp, vp, vp, i32, i32, vp, i32, i32, sz, vp, vp]),
+    "qllm_convert_bf16_to_f16": (C.c_int, [vp, vp, sz, vp]),
+    "qllm_set_knob": (C.c_int, [C.c_char_p, i32]),
+    "qllm_get_knob": (C.c_int, [C.c_char_p, C.POINTER(i32), C.POINTER(i32)]),
+    "qllm_reset_knobs": (None, []),
+    "qllm_hqq_quantize_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "qllm_hqq_quantize": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, C.c_float, C.c_float, C.c_float, vp, vp, vp, vp, vp, sz, vp]),
+    "qllm_gptq_quantize_workspace_bytes": (sz, [i32, i32]),
+    "qllm_gptq_quantize": (C.c_int, [vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "qllm_gptq_quantize_static": (C.c_int, [vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "qllm_linear_forward_permuted": (C.c_int, [wp, vp, vp, vp, i32, i32, vp, sz, vp]),
+    "qllm_linear_forward_bitpanel": (C.c_int, [wp, vp, vp, i32, i32, vp, sz, vp]),
+    "qllm_bitpanel_workspace_bytes": (sz, [wp, i32]),
+    "qllm_bitpanel_describe": (C.c_int, [wp, i32, i32, C.c_char_p, sz]),
+    "qllm_linear_forward_bitgroup": (C.c_int, [wp, C.POINTER(vp), i32, vp, i32, i32, vp, sz, vp]),
+    "qllm_bitgroup_workspace_bytes": (sz, [wp, i32, i32]),
+    "qllm_bitgroup_describe": (C.c_int, [wp, i32, i32, i32, C.c_char_p, sz]),
+    "qllm_linear_forward_bitgemm": (C.c_int, [wp, vp, vp, i32, i32, vp, sz, vp]),
+    "qllm_bitgemm_workspace_bytes": (sz, [wp, i32]),
+    "qllm_bitgemm_describe": (C.c_int, [wp, i32, i32, C.c_char_p, sz]),
+    "qllm_awq_clip_search_workspace_bytes": (sz, [i32, i32, i32]),
+    "qllm_awq_clip_search": (C.c_int, [vp, i32, vp, i32, i32, i32, i32, i32, C.c_float, vp, vp, vp, vp, sz, vp]),
+    "qllm_awq_quantize": (C.c_int, [vp, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "qllm_linear_forward_swiglu": (C.c_int, [wp, vp, vp, vp, i32, i32, i32, vp]),
+    "qllm_swiglu_describe": (C.c_int, [wp, i32, C.c_char_p, sz]),
+    "qllm_rmsnorm": (C.c_int, [vp, vp, vp, i32, i32, C.c_float, i32, vp, vp]),
+    "qllm_linear_forward_rmsnorm": (C.c_int, [wp, C.POINTER(vp), i32, vp, vp, C.c_float, i32, i32, vp, vp]),
+    "qllm_rmsnorm_describe": (C.c_int, [wp, i32, i32, C.c_char_p, sz]),
+}
+EXPORTS = tuple(SIGNATURES)
+
+
 class QllmError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"qllm_mi355x error {code}: {msg}")
@@ -74,122 +122,9 @@ _lock = threading.Lock()
 
 
 def _declare(lib):
-    vp, i32, sz = C.c_void_p, C.c_int32, C.c_size_t
-    wp = C.POINTER(QllmWeight)
-    lib.qllm_abi_version.restype = C.c_int
-    lib.qllm_abi_version.argtypes = []
-    lib.qllm_is_lab_build.restype = C.c_int
-    lib.qllm_is_lab_build.argtypes = []
-    lib.qllm_set_knob.restype = C.c_int
-    lib.qllm_set_knob.argtypes = [C.c_char_p, i32]
-    lib.qllm_get_knob.restype = C.c_int
-    lib.qllm_get_knob.argtypes = [C.c_char_p, C.POINTER(i32), C.POINTER(i32)]
-    lib.qllm_reset_knobs.restype = None
-    lib.qllm_reset_knobs.argtypes = []
-    lib.qllm_last_error.restype = C.c_char_p
-    lib.qllm_last_error.argtypes = []
-    lib.qllm_device_info.restype = C.c_int
-    lib.qllm_device_info.argtypes = [C.c_int, C.POINTER(QllmDeviceInfo)]
-    lib.qllm_workspace_bytes.restype = sz
-    lib.qllm_workspace_bytes.argtypes = [wp, i32]
-    lib.qllm_workspace_bytes_act.restype = sz
-    lib.qllm_workspace_bytes_act.argtypes = [wp, i32, i32]
-    lib.qllm_comm_buffer_bytes.restype = sz
-    lib.qllm_comm_buffer_bytes.argtypes = [i32, sz]
-    lib.qllm_comm_alloc.restype = C.c_int
-    lib.qllm_comm_alloc.argtypes = [sz, C.POINTER(vp)]
-    lib.qllm_comm_free.restype = C.c_int
-    lib.qllm_comm_free.argtypes = [vp]
-    lib.qllm_comm_export.restype = C.c_int
-    lib.qllm_comm_export.argtypes = [vp, vp]
-    lib.qllm_comm_import.restype = C.c_int
-    lib.qllm_comm_import.argtypes = [vp, C.POINTER(vp)]
-    lib.qllm_comm_close.restype = C.c_int
-    lib.qllm_comm_close.argtypes = [vp]
-    lib.qllm_allreduce_oneshot.restype = C.c_int
-    lib.qllm_allreduce_oneshot.argtypes = [vp, i32, i32, vp, i32, i32, sz, vp, vp]
-    lib.qllm_linear_forward_allreduce.restype = C.c_int
-    lib.qllm_linear_forward_allreduce.argtypes = [C.POINTER(QllmWeight), vp, vp, i32, i32, vp, i32, i32, sz, vp, vp]
-    lib.qllm_convert_bf16_to_f16.restype = C.c_int
-    lib.qllm_convert_bf16_to_f16.argtypes = [vp, vp, sz, vp]
-    lib.qllm_workspace_init.restype = C.c_int
-    lib.qllm_workspace_init.argtypes = [vp, sz, vp]
-    lib.qllm_linear_forward.restype = C.c_int
-    lib.qllm_linear_forward.argtypes = [wp, vp, vp, i32, i32, vp, sz, vp]
-    lib.qllm_linear_forward_grouped.restype = C.c_int
-    lib.qllm_linear_forward_grouped.argtypes = [wp, C.POINTER(vp), i32, vp, i32, i32, vp, sz, vp]
-    lib.qllm_dequant.restype = C.c_int
-    lib.qllm_dequant.argtypes = [wp, vp, i32, i32, vp]
-    lib.qllm_ort_gemv.restype = C.c_int
-    lib.qllm_ort_gemv.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, i32, i32, vp, sz, vp]
-    lib.qllm_ort_dequant.restype = C.c_int
-    lib.qllm_ort_dequant.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp]
-    lib.qllm_awq_gemm_forward.restype = C.c_int
-    lib.qllm_awq_gemm_forward.argtypes = [vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp, sz, vp]
-    lib.qllm_unpack_qweight.restype = C.c_int
-    lib.qllm_unpack_qweight.argtypes = [vp, i32, i32, i32, i32, vp, vp]
-    lib.qllm_pack_qweight.restype = C.c_int
-    lib.qllm_pack_qweight.argtypes = [vp, i32, i32, i32, i32, vp, vp]
-    lib.qllm_gather_columns.restype = C.c_int
-    lib.qllm_gather_columns.argtypes = [vp, vp, vp, i32, i32, i32, vp]
-    lib.qllm_linear_forward_permuted.restype = C.c_int
-    lib.qllm_linear_forward_permuted.argtypes = [wp, vp, vp, vp, i32, i32, vp, sz, vp]
-    lib.qllm_linear_forward_bitpanel.restype = C.c_int
-    lib.qllm_linear_forward_bitpanel.argtypes = [wp, vp, vp, i32, i32, vp, sz, vp]
-    lib.qllm_bitpanel_workspace_bytes.restype = sz
-    lib.qllm_bitpanel_workspace_bytes.argtypes = [wp, i32]
-    lib.qllm_bitpanel_describe.restype = C.c_int
-    lib.qllm_bitpanel_describe.argtypes = [wp, i32, i32, C.c_char_p, sz]
-    lib.qllm_linear_forward_bitgemm.restype = C.c_int
-    lib.qllm_linear_forward_bitgemm.argtypes = [wp, vp, vp, i32, i32, vp, sz, vp]
-    lib.qllm_bitgemm_workspace_bytes.restype = sz
-    lib.qllm_bitgemm_workspace_bytes.argtypes = [wp, i32]
-    lib.qllm_bitgemm_describe.restype = C.c_int
-    lib.qllm_bitgemm_describe.argtypes = [wp, i32, i32, C.c_char_p, sz]
-    lib.qllm_linear_forward_bitgroup.restype = C.c_int
-    lib.qllm_linear_forward_bitgroup.argtypes = [wp, C.POINTER(vp), i32, vp, i32, i32, vp, sz, vp]
-    lib.qllm_bitgroup_workspace_bytes.restype = sz
-    lib.qllm_bitgroup_workspace_bytes.argtypes = [wp, i32, i32]
-    lib.qllm_bitgroup_describe.restype = C.c_int
-    lib.qllm_bitgroup_describe.argtypes = [wp, i32, i32, i32, C.c_char_p, sz]
-    lib.qllm_linear_forward_swiglu.restype = C.c_int
-    lib.qllm_linear_forward_swiglu.argtypes = [wp, vp, vp, vp, i32, i32, i32, vp]
-    lib.qllm_swiglu_describe.restype = C.c_int
-    lib.qllm_swiglu_describe.argtypes = [wp, i32, C.c_char_p, sz]
-    lib.qllm_rmsnorm.restype = C.c_int
-    lib.qllm_rmsnorm.argtypes = [vp, vp, vp, i32, i32, C.c_float, i32, vp, vp]
-    lib.qllm_linear_forward_rmsnorm.restype = C.c_int
-    lib.qllm_linear_forward_rmsnorm.argtypes = [wp, C.POINTER(C.c_void_p), i32, vp, vp, C.c_float, i32, i32, vp, vp]
-    lib.qllm_rmsnorm_describe.restype = C.c_int
-    lib.qllm_rmsnorm_describe.argtypes = [wp, i32, i32, C.c_char_p, sz]
-    lib.qllm_plan_describe.restype = C.c_int
-    lib.qllm_plan_describe.argtypes = [wp, i32, i32, i32, C.c_char_p, sz]
-    lib.qllm_debug_timeline.restype = C.c_int
-    lib.qllm_debug_timeline.argtypes = [vp, i32]
-    lib.qllm_native_sizes.restype = C.c_int
-    lib.qllm_native_sizes.argtypes = [wp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
-    lib.qllm_repack_native.restype = C.c_int
-    lib.qllm_repack_native.argtypes = [wp, vp, vp, vp, vp]
-    lib.qllm_unpack_native.restype = C.c_int
-    lib.qllm_unpack_native.argtypes = [wp, i32, vp, vp, vp, vp]
-    lib.qllm_hqq_quantize_workspace_bytes.restype = sz
-    lib.qllm_hqq_quantize_workspace_bytes.argtypes = [i32, i32, i32, i32]
-    lib.qllm_hqq_quantize.restype = C.c_int
-    lib.qllm_hqq_quantize.argtypes = [vp, i32, i32, i32, i32, i32, i32, C.c_float, C.c_float, C.c_float, vp, vp, vp, vp, vp, sz, vp]
-    lib.qllm_gptq_quantize_workspace_bytes.restype = sz
-    lib.qllm_gptq_quantize_workspace_bytes.argtypes = [i32, i32]
-    lib.qllm_gptq_quantize.restype = C.c_int
-    lib.qllm_gptq_quantize.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]
-    lib.qllm_gptq_quantize_static.restype = C.c_int
-    lib.qllm_gptq_quantize_static.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]
-    lib.qllm_awq_clip_search_workspace_bytes.restype = sz
-    lib.qllm_awq_clip_search_workspace_bytes.argtypes = [i32, i32, i32]
-    lib.qllm_awq_clip_search.restype = C.c_int
-    lib.qllm_awq_clip_search.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, C.c_float, vp, vp, vp, vp, sz, vp]
-    lib.qllm_awq_quantize.restype = C.c_int
-    lib.qllm_awq_quantize.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
-    lib.qllm_ort_dequantize4bits.restype = C.c_int
-    lib.qllm_ort_dequantize4bits.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, vp, vp]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
 
 
 def is_built() -> bool:

@@ -2,6 +2,10 @@
 // sites: /root/reference/csrc/ort_cuda/ort_ops.cc:64-73,99-107; csrc/awq_cuda/quantization/gemm_cuda_gen.cu:1128-1135),
 // parameter-block fills, workspace carving, launches.  Which kernel runs is decided in planner.hip.  No allocation, no host sync, no
 // global mutable state beyond thread-local error text.
+// The kernels with an entry of their own (qllm_linear_forward_permuted / _bitpanel / _bitgemm / _bitgroup / _swiglu / _rmsnorm: the planner
+// does not know them) each keep ONE *_check / decide_* that their forward, *_workspace_bytes and *_describe entries all ask.  What those
+// entries do around it is written once: check_layer_count + check_layers (an array of layers), check_describe_args, describe_refusal
+// (a refusal as text), counters_and_slabs (a workspace size) and fill_bit_params (the bit family's parameter blocks).
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -70,6 +74,55 @@ static int check_io(const void *x, const void *y, int M, int act_dtype) {
   if (act_dtype != QLLM_F16 && act_dtype != QLLM_BF16) return set_error(QLLM_ERR_INVALID, "act_dtype must be f16 or bf16");
   if ((uintptr_t)x % 16 != 0) return set_error(QLLM_ERR_INVALID, "x must be 16-byte aligned");
   return QLLM_OK;
+}
+
+// What every entry that takes an ARRAY of layers checks: the arrays (each entry words its own NULL check: a describe entry names its
+// buffer with them), the count against the entry's limit (`entry`: "", or the name its message starts with), then layer by layer the
+// descriptor and -- with `each` -- what the entry asks of that layer (its output through check_io, ...).  Two functions because entries
+// have checks of their own between the count and the layers, and the order in which checks fire is part of the ABI.
+static const char kArraysNull[] = "w / y arrays must not be NULL";
+static int check_layer_count(int n, int limit, const char *entry = "") {
+  if (n < 1 || n > limit) return set_error(QLLM_ERR_INVALID, "%sn_weights must be 1..%d (got %d)", entry, limit, n);
+  return QLLM_OK;
+}
+template <typename Each>
+static int check_layers(const qllm_weight_t *w, int n, Each each) {
+  for (int i = 0; i < n; ++i) {
+    if (int rc = validate_weight(&w[i])) return rc;
+    if (int rc = each(i)) return rc;
+  }
+  return QLLM_OK;
+}
+static int check_layers(const qllm_weight_t *w, int n) { return check_layers(w, n, [](int) { return (int)QLLM_OK; }); }
+
+// what qllm_bitpanel_describe and qllm_bitgemm_describe check before the entry's own *_check
+static int check_describe_args(const qllm_weight_t *w, int M, const char *buf, size_t buflen) {
+  if (!buf || buflen == 0) return set_error(QLLM_ERR_INVALID, "buf must not be NULL");
+  if (int rc = validate_weight(w)) return rc;
+  if (M <= 0) return set_error(QLLM_ERR_INVALID, "M must be >= 1 (got %d)", M);
+  return QLLM_OK;
+}
+
+// The tail of a describe entry whose check said no (rc != QLLM_OK).  A call the kernel does not take is an answer, not a failure:
+// QLLM_ERR_UNSUPPORTED becomes text in buf through `fmt` (kUnsupported, kRefused) with the error's own words, the error is cleared and
+// the entry returns QLLM_OK.  Every other status is returned as it is, its text in qllm_last_error().
+static const char kUnsupported[] = "unsupported (%s)", kRefused[] = "refused: %s";
+static int describe_refusal(int rc, const char *fmt, char *buf, size_t buflen) {
+  if (rc != QLLM_ERR_UNSUPPORTED) return rc;
+  snprintf(buf, buflen, fmt, last_error_text());
+  clear_error();
+  return QLLM_OK;
+}
+
+// What the *_workspace_bytes of the bit family answer: the counter page, and behind it the slabs of the geometry the entry would launch
+// with a workspace of any size (`geometry`: that call, with SIZE_MAX).  A call the entry refuses needs the page alone, and leaves no error.
+template <typename Geometry>
+static size_t counters_and_slabs(bool refused, Geometry geometry) {
+  if (refused) {
+    clear_error();
+    return kCounterBytes;
+  }
+  return kCounterBytes + geometry().slab_bytes;
 }
 
 // What the four quantizer entry points check first, alike: the pointers they require (`required` names them, w_nk among them), the
@@ -261,15 +314,29 @@ static int run_panel(const qllm_weight_t *w, void *const *y, int n, const void *
   return launch_panel(p, stream);
 }
 
-// perm: NULL, or the permutation the kernel applies to x's columns while it stages them (qllm_linear_forward_permuted)
-static int run_bitgemv(const qllm_weight_t *w, void *y, const void *x, int M, int act_dtype, void *workspace, size_t workspace_bytes, hipStream_t stream,
-                       const int32_t *perm = nullptr) {
-  BitGemvParams p;
+// what the bit family's parameter blocks (BitGemvParams, BitPanelParams, BitGemmParams) share: the call, the one layer and its shape
+template <typename Params>
+static void fill_bit_params(Params &p, const qllm_weight_t *w, const void *x, void *y, int M, int act_dtype) {
   fill_call(p, *w, x, M, act_dtype);
   fill_layer(p, *w, y);
   p.K = w->K;
   p.N = w->N;
   p.group_size = w->group_size;
+}
+
+// "<name> " + the plan line of the launch `d`: what qllm_swiglu_describe and qllm_rmsnorm_describe answer where their entries serve
+static int describe_fused(const char *name, const Decision &d, const qllm_weight_t *w, int n, int M, char *buf, size_t buflen) {
+  const int at = snprintf(buf, buflen, "%s ", name);
+  describe(d, w, n, M, 0, buf + at, buflen - at);
+  clear_error();
+  return QLLM_OK;
+}
+
+// perm: NULL, or the permutation the kernel applies to x's columns while it stages them (qllm_linear_forward_permuted)
+static int run_bitgemv(const qllm_weight_t *w, void *y, const void *x, int M, int act_dtype, void *workspace, size_t workspace_bytes, hipStream_t stream,
+                       const int32_t *perm = nullptr) {
+  BitGemvParams p;
+  fill_bit_params(p, w, x, y, M, act_dtype);
   p.ksplit = bitgemv_split_for(M, w->K, w->N, usable_ws(workspace, workspace_bytes));
   if (p.ksplit > 1) carve(workspace, &p.counters, &p.slabs);
   return perm ? launch_bitgemv_permuted(p, perm, w->bits, stream) : launch_bitgemv(p, w->bits, stream);
@@ -403,15 +470,10 @@ int qllm_workspace_init(void *workspace, size_t bytes, void *stream) {
 int qllm_linear_forward_grouped(const qllm_weight_t *w, void *const *y, int32_t n_weights, const void *x, int32_t M,
                                 int32_t act_dtype, void *workspace, size_t workspace_bytes, void *stream) {
   clear_error();
-  if (!w || !y) return set_error(QLLM_ERR_INVALID, "w / y arrays must not be NULL");
-  if (n_weights < 1 || n_weights > kMaxProblems) return set_error(QLLM_ERR_INVALID, "n_weights must be 1..%d (got %d)", kMaxProblems, n_weights);
+  if (!w || !y) return set_error(QLLM_ERR_INVALID, kArraysNull);
+  if (int rc = check_layer_count(n_weights, kMaxProblems)) return rc;
   if (n_weights == 1) return qllm_linear_forward(&w[0], x, y[0], M, act_dtype, workspace, workspace_bytes, stream);  // (a group of one is a plain call)
-  for (int i = 0; i < n_weights; ++i) {
-    int rc = validate_weight(&w[i]);
-    if (rc) return rc;
-    rc = check_io(x, y[i], M, act_dtype);
-    if (rc) return rc;
-  }
+  if (int rc = check_layers(w, n_weights, [&](int i) { return check_io(x, y[i], M, act_dtype); })) return rc;
   const Decision d = decide_group(w, n_weights, M, act_dtype);
   return execute(d, w, y, n_weights, x, M, act_dtype, workspace, workspace_bytes, (hipStream_t)stream);
 }
@@ -469,11 +531,7 @@ int qllm_linear_forward_bitpanel(const qllm_weight_t *w, const void *x, void *y,
   if (rc) return rc;
   const BitPanelGeom g = bitpanel_geometry(*w, M, usable_ws(workspace, workspace_bytes));
   BitPanelParams p;
-  fill_call(p, *w, x, M, act_dtype);
-  fill_layer(p, *w, y);
-  p.K = w->K;
-  p.N = w->N;
-  p.group_size = w->group_size;
+  fill_bit_params(p, w, x, y, M, act_dtype);
   p.bits = w->bits;
   p.mt = g.mt;
   p.row_blocks = g.row_blocks;
@@ -485,24 +543,15 @@ int qllm_linear_forward_bitpanel(const qllm_weight_t *w, const void *x, void *y,
 }
 
 size_t qllm_bitpanel_workspace_bytes(const qllm_weight_t *w, int32_t M) {
-  if (!w || validate_weight(w) || M < kBitPanelMinM || M > kBitPanelMaxM || w->g_idx || bitpanel_refusal(*w)) {
-    clear_error();
-    return kCounterBytes;
-  }
-  return kCounterBytes + bitpanel_geometry(*w, M, SIZE_MAX).slab_bytes;
+  // (the rows, the layer and its shape: not the QLLM_BITPANEL knob)
+  return counters_and_slabs(!w || validate_weight(w) || M < kBitPanelMinM || M > kBitPanelMaxM || w->g_idx || bitpanel_refusal(*w),
+                            [&] { return bitpanel_geometry(*w, M, SIZE_MAX); });
 }
 
 int qllm_bitpanel_describe(const qllm_weight_t *w, int32_t M, int32_t have_workspace, char *buf, size_t buflen) {
   clear_error();
-  if (!buf || buflen == 0) return set_error(QLLM_ERR_INVALID, "buf must not be NULL");
-  int rc = validate_weight(w);
-  if (rc) return rc;
-  if (M <= 0) return set_error(QLLM_ERR_INVALID, "M must be >= 1 (got %d)", M);
-  if (bitpanel_check(w, M)) {
-    snprintf(buf, buflen, "unsupported (%s)", last_error_text());
-    clear_error();
-    return QLLM_OK;
-  }
+  if (int rc = check_describe_args(w, M, buf, buflen)) return rc;
+  if (bitpanel_check(w, M)) return describe_refusal(QLLM_ERR_UNSUPPORTED, kUnsupported, buf, buflen);  // (a g_idx too: its text says what to do)
   const BitPanelGeom g = bitpanel_geometry(*w, M, have_workspace ? SIZE_MAX : 0);
   snprintf(buf, buflen, "bitpanel bits=%d cols=64 row_tiles=%d row_blocks=%d split_k=%d", w->bits, g.mt, g.row_blocks, g.split_k);
   return QLLM_OK;
@@ -537,11 +586,7 @@ int qllm_linear_forward_bitgemm(const qllm_weight_t *w, const void *x, void *y, 
   if ((uintptr_t)x % 16 || (uintptr_t)y % 16) return set_error(QLLM_ERR_UNSUPPORTED, "the 2..8-bit prefill kernel: x and y must be 16-byte aligned; use qllm_dequant + a GEMM");
   const BitGemmGeom g = bitgemm_geometry(*w, M, usable_ws(workspace, workspace_bytes));
   BitGemmParams p;
-  fill_call(p, *w, x, M, QLLM_F16);
-  fill_layer(p, *w, y);
-  p.K = w->K;
-  p.N = w->N;
-  p.group_size = w->group_size;
+  fill_bit_params(p, w, x, y, M, QLLM_F16);
   p.bits = w->bits;
   p.out_bf16 = act_dtype == QLLM_F16_IN_BF16_OUT;
   p.split_k = g.split_k;
@@ -550,24 +595,13 @@ int qllm_linear_forward_bitgemm(const qllm_weight_t *w, const void *x, void *y, 
 }
 
 size_t qllm_bitgemm_workspace_bytes(const qllm_weight_t *w, int32_t M) {
-  if (!w || validate_weight(w) || M <= 0 || bitgemm_check(w, M)) {
-    clear_error();
-    return kCounterBytes;
-  }
-  return kCounterBytes + bitgemm_geometry(*w, M, SIZE_MAX).slab_bytes;
+  return counters_and_slabs(!w || validate_weight(w) || M <= 0 || bitgemm_check(w, M), [&] { return bitgemm_geometry(*w, M, SIZE_MAX); });
 }
 
 int qllm_bitgemm_describe(const qllm_weight_t *w, int32_t M, int32_t have_workspace, char *buf, size_t buflen) {
   clear_error();
-  if (!buf || buflen == 0) return set_error(QLLM_ERR_INVALID, "buf must not be NULL");
-  int rc = validate_weight(w);
-  if (rc) return rc;
-  if (M <= 0) return set_error(QLLM_ERR_INVALID, "M must be >= 1 (got %d)", M);
-  if (bitgemm_check(w, M)) {
-    snprintf(buf, buflen, "unsupported (%s)", last_error_text());
-    clear_error();
-    return QLLM_OK;
-  }
+  if (int rc = check_describe_args(w, M, buf, buflen)) return rc;
+  if (bitgemm_check(w, M)) return describe_refusal(QLLM_ERR_UNSUPPORTED, kUnsupported, buf, buflen);  // (a g_idx too: its text says what to do)
   const BitGemmGeom g = bitgemm_geometry(*w, M, have_workspace ? SIZE_MAX : 0);
   snprintf(buf, buflen, "bitgemm bits=%d tile=256x128 tiles=%d split_k=%d", w->bits, g.tiles, g.split_k);
   return QLLM_OK;
@@ -577,10 +611,9 @@ int qllm_bitgemm_describe(const qllm_weight_t *w, int32_t M, int32_t have_worksp
 // QLLM_ERR_UNSUPPORTED for calls this kernel does not take --, with the text in qllm_last_error(); QLLM_OK: served
 static int bitgroup_check(const qllm_weight_t *w, int n, int M) {
   static const char kInstead[] = "call qllm_linear_forward layer by layer";
-  if (!w) return set_error(QLLM_ERR_INVALID, "w / y arrays must not be NULL");
-  if (n < 1 || n > kBitGroupMaxLayers) return set_error(QLLM_ERR_INVALID, "qllm_linear_forward_bitgroup: n_weights must be 1..%d (got %d)", kBitGroupMaxLayers, n);
-  for (int i = 0; i < n; ++i)
-    if (int rc = validate_weight(&w[i])) return rc;
+  if (!w) return set_error(QLLM_ERR_INVALID, kArraysNull);
+  if (int rc = check_layer_count(n, kBitGroupMaxLayers, "qllm_linear_forward_bitgroup: ")) return rc;
+  if (int rc = check_layers(w, n)) return rc;
   if (M <= 0) return set_error(QLLM_ERR_INVALID, "M must be >= 1 (got %d)", M);
   auto family = [](const qllm_weight_t &l) { return is_native(l) ? 2 : (l.layout == QLLM_LAYOUT_AWQ_GEMM ? 1 : 0); };
   for (int i = 0; i < n; ++i) {
@@ -601,7 +634,7 @@ static int bitgroup_check(const qllm_weight_t *w, int n, int M) {
 int qllm_linear_forward_bitgroup(const qllm_weight_t *w, void *const *y, int32_t n_weights, const void *x, int32_t M, int32_t act_dtype,
                                  void *workspace, size_t workspace_bytes, void *stream) {
   clear_error();
-  if (!y) return set_error(QLLM_ERR_INVALID, "w / y arrays must not be NULL");
+  if (!y) return set_error(QLLM_ERR_INVALID, kArraysNull);
   if (int rc = bitgroup_check(w, n_weights, M)) return rc;
   for (int i = 0; i < n_weights; ++i)
     if (int rc = check_io(x, y[i], M, act_dtype)) return rc;
@@ -633,23 +666,13 @@ int qllm_linear_forward_bitgroup(const qllm_weight_t *w, void *const *y, int32_t
 }
 
 size_t qllm_bitgroup_workspace_bytes(const qllm_weight_t *w, int32_t n_weights, int32_t M) {
-  if (bitgroup_check(w, n_weights, M)) {
-    clear_error();
-    return kCounterBytes;
-  }
-  return kCounterBytes + bitgemv_group_geometry(w, n_weights, M, SIZE_MAX).slab_bytes;
+  return counters_and_slabs(bitgroup_check(w, n_weights, M), [&] { return bitgemv_group_geometry(w, n_weights, M, SIZE_MAX); });
 }
 
 int qllm_bitgroup_describe(const qllm_weight_t *w, int32_t n_weights, int32_t M, int32_t have_workspace, char *buf, size_t buflen) {
   clear_error();
   if (!buf || buflen == 0) return set_error(QLLM_ERR_INVALID, "buf must not be NULL");
-  const int rc = bitgroup_check(w, n_weights, M);
-  if (rc == QLLM_ERR_UNSUPPORTED) {
-    snprintf(buf, buflen, "unsupported (%s)", last_error_text());
-    clear_error();
-    return QLLM_OK;
-  }
-  if (rc) return rc;
+  if (int rc = bitgroup_check(w, n_weights, M)) return describe_refusal(rc, kUnsupported, buf, buflen);
   const BitGroupGeom g = bitgemv_group_geometry(w, n_weights, M, have_workspace ? SIZE_MAX : 0);
   char splits[64] = "";
   size_t at = 0;
@@ -856,22 +879,13 @@ int qllm_swiglu_describe(const qllm_weight_t *w, int32_t M, char *buf, size_t bu
   clear_error();
   if (!w || !buf || buflen < 64) return set_error(QLLM_ERR_INVALID, "w / buf must not be NULL (buf >= 64 bytes)");
   if (M <= 0) return set_error(QLLM_ERR_INVALID, "M must be >= 1 (got %d)", M);
+  Decision d;
+  memset(&d, 0, sizeof(d));
+  d.route = ROUTE_STRIP;
   int rc = validate_weight(w);
-  if (rc == QLLM_OK) {
-    Decision d;
-    memset(&d, 0, sizeof(d));
-    d.route = ROUTE_STRIP;
-    rc = decide_swiglu(w, M, QLLM_ACT_SILU, &d.strip);
-    if (rc == QLLM_OK) {
-      const int n = snprintf(buf, buflen, "swiglu ");
-      describe(d, w, 1, M, 0, buf + n, buflen - n);
-      clear_error();
-      return QLLM_OK;
-    }
-  }
-  if (rc != QLLM_ERR_UNSUPPORTED) return rc;
-  snprintf(buf, buflen, "refused: %s", last_error_text());
-  return QLLM_OK;
+  if (rc == QLLM_OK) rc = decide_swiglu(w, M, QLLM_ACT_SILU, &d.strip);
+  if (rc) return describe_refusal(rc, kRefused, buf, buflen);
+  return describe_fused("swiglu", d, w, 1, M, buf, buflen);
 }
 
 // y = weight * round(x * rstd) per row: the standalone RMSNorm kernel (rmsnorm.hip)
@@ -892,23 +906,21 @@ int qllm_rmsnorm(const void *x, const void *weight, void *y, int32_t M, int32_t 
 int qllm_linear_forward_rmsnorm(const qllm_weight_t *w, void *const *y, int32_t n_weights, const void *x, const void *norm_weight, float eps,
                                 int32_t M, int32_t act_dtype, float *rstd_out, void *stream) {
   clear_error();
-  if (!w || !y) return set_error(QLLM_ERR_INVALID, "w / y arrays must not be NULL");
-  if (n_weights < 1 || n_weights > kMaxProblems) return set_error(QLLM_ERR_INVALID, "n_weights must be 1..%d (got %d)", kMaxProblems, n_weights);
+  if (!w || !y) return set_error(QLLM_ERR_INVALID, kArraysNull);
+  if (int rc = check_layer_count(n_weights, kMaxProblems)) return rc;
   if (!norm_weight) return set_error(QLLM_ERR_INVALID, "norm_weight must not be NULL");
-  for (int i = 0; i < n_weights; ++i) {
-    int rc = validate_weight(&w[i]);
-    if (rc) return rc;
-    rc = check_io(x, y[i], M, act_dtype);
-    if (rc) return rc;
+  auto output_ok = [&](int i) {
+    if (int rc = check_io(x, y[i], M, act_dtype)) return rc;
     if (y[i] == x || y[i] == norm_weight) return set_error(QLLM_ERR_INVALID, "y must not alias x / norm_weight (every block reads the whole row)");
-  }
+    return (int)QLLM_OK;
+  };
+  if (int rc = check_layers(w, n_weights, output_ok)) return rc;
   if ((uintptr_t)norm_weight % 16 != 0) return set_error(QLLM_ERR_INVALID, "norm_weight must be 16-byte aligned");
   if ((uintptr_t)rstd_out % 4) return set_error(QLLM_ERR_INVALID, "rstd_out must be 4-byte aligned");
   if (!(eps >= 0.f)) return set_error(QLLM_ERR_INVALID, "eps must be >= 0");
   if (w[0].K % 8 != 0) return set_error(QLLM_ERR_INVALID, "K must be a multiple of 8 (got %d)", w[0].K);
   Decision d;
-  int rc = decide_rmsnorm(w, n_weights, M, &d);
-  if (rc) return rc;
+  if (int rc = decide_rmsnorm(w, n_weights, M, &d)) return rc;
   Strip1Params p;
   const int max_strips = fill_strip1_params(p, w, y, n_weights, x, M, act_dtype);
   p.norm_w = norm_weight;
@@ -921,23 +933,13 @@ int qllm_linear_forward_rmsnorm(const qllm_weight_t *w, void *const *y, int32_t 
 int qllm_rmsnorm_describe(const qllm_weight_t *w, int32_t n_weights, int32_t M, char *buf, size_t buflen) {
   clear_error();
   if (!w || !buf || buflen < 64) return set_error(QLLM_ERR_INVALID, "w / buf must not be NULL (buf >= 64 bytes)");
-  if (n_weights < 1 || n_weights > kMaxProblems) return set_error(QLLM_ERR_INVALID, "n_weights must be 1..%d (got %d)", kMaxProblems, n_weights);
+  if (int rc = check_layer_count(n_weights, kMaxProblems)) return rc;
   if (M <= 0) return set_error(QLLM_ERR_INVALID, "M must be >= 1 (got %d)", M);
-  int rc = QLLM_OK;
-  for (int i = 0; i < n_weights && rc == QLLM_OK; ++i) rc = validate_weight(&w[i]);
-  if (rc == QLLM_OK) {
-    Decision d;
-    rc = decide_rmsnorm(w, n_weights, M, &d);
-    if (rc == QLLM_OK) {
-      const int n = snprintf(buf, buflen, "rmsnorm ");
-      describe(d, w, n_weights, M, 0, buf + n, buflen - n);
-      clear_error();
-      return QLLM_OK;
-    }
-  }
-  if (rc != QLLM_ERR_UNSUPPORTED) return rc;
-  snprintf(buf, buflen, "refused: %s", last_error_text());
-  return QLLM_OK;
+  Decision d;
+  int rc = check_layers(w, n_weights);
+  if (rc == QLLM_OK) rc = decide_rmsnorm(w, n_weights, M, &d);
+  if (rc) return describe_refusal(rc, kRefused, buf, buflen);
+  return describe_fused("rmsnorm", d, w, n_weights, M, buf, buflen);
 }
 
 int qllm_dequant(const qllm_weight_t *w, void *out, int32_t out_dtype, int32_t out_transposed, void *stream) {
@@ -987,12 +989,9 @@ int qllm_ort_dequantize4bits(const void *qweight, const void *scales, const void
 int qllm_plan_describe(const qllm_weight_t *w, int32_t n_weights, int32_t M, int32_t have_workspace, char *buf, size_t buflen) {
   clear_error();
   if (!w || !buf || buflen < 64) return set_error(QLLM_ERR_INVALID, "w / buf must not be NULL (buf >= 64 bytes)");
-  if (n_weights < 1 || n_weights > kMaxProblems) return set_error(QLLM_ERR_INVALID, "n_weights must be 1..%d (got %d)", kMaxProblems, n_weights);
+  if (int rc = check_layer_count(n_weights, kMaxProblems)) return rc;
   if (M <= 0) return set_error(QLLM_ERR_INVALID, "M must be >= 1 (got %d)", M);
-  for (int i = 0; i < n_weights; ++i) {
-    const int rc = validate_weight(&w[i]);
-    if (rc) return rc;
-  }
+  if (int rc = check_layers(w, n_weights)) return rc;
   const Decision d = n_weights == 1 ? decide_single(&w[0], M, QLLM_F16) : decide_group(w, n_weights, M, QLLM_F16);
   if (d.route == ROUTE_NONE && d.rc == QLLM_ERR_INVALID) return d.rc;  // (layers that cannot share a launch at all: the forward call's own status)
   describe(d, w, n_weights, M, have_workspace ? (size_t)-1 : 0, buf, buflen);

@@ -21,6 +21,28 @@ def _tkey(t):
     return (0, 0) if t is None else (t.data_ptr(), tensor_version(t))
 
 
+def bit_family_entry(layout: int, dtype, rows: int):
+    """Which of the bit family's own entries module code sends a call of `rows` rows to, under the current knobs: "bitpanel"
+    (ops.linear_forward_bitpanel, csrc/bitpanel.hip: 17 .. ops.bitpanel_max_m() rows), "bitgemm" (ops.linear_forward_bitgemm,
+    csrc/bitgemm.hip: from ops.bitgemm_min_m() rows -- 0: never -- and above ops.bitpanel_max_m()) or None.  Both read GPTQ / HQQ buffers in
+    place and fp16 / bf16 activations; a descriptor with g_idx is not theirs (the callers ask with the row-sorted copy, or not at all).
+    The ONE place this rule is written: `_hip_linear` asks it for plain layers, `QuantLinearGPTQ.forward` for act-order ones."""
+    if layout not in (ops.LAYOUTS["GPTQ"], ops.LAYOUTS["HQQ"]) or dtype not in (torch.float16, torch.bfloat16):
+        return None
+    if 17 <= rows <= ops.bitpanel_max_m():
+        return "bitpanel"
+    if 0 < ops.bitgemm_min_m() <= rows and rows > ops.bitpanel_max_m():
+        return "bitgemm"
+    return None
+
+
+def bitgroup_serves(bits: int, n_layers: int, act_order: bool, rows: int) -> bool:
+    """Whether a sibling group's launch goes to ops.linear_forward_bitgroup (csrc/bitgemv_group.hip: 2 / 5 / 6 / 7 / 8 bits, up to four
+    members, no act-order member, 1 .. ops.bitgroup_max_m() rows -- profiles/bitgemv_group.md) or to ops.linear_forward_grouped, the
+    planner's entry, which refuses these widths (the layers then run on their own).  Asked by `SiblingGroup.forward_for` (fused.py)."""
+    return bits in (2, 5, 6, 7, 8) and n_layers <= 4 and not act_order and 1 <= rows <= ops.bitgroup_max_m()
+
+
 # derived, pointer-holding state (ctypes descriptors, shadows, sibling groups): rebuilt on demand, never copied or pickled
 _DERIVED = ("_desc", "_desc_key", "_desc_keep", "_native", "_native_key", "_ao", "_ao_key", "_ao_panel_refused", "_ao_gemm_refused", "_perm", "_swiglu_refused_from", "_siblings")
 # (a released module is materialised before it is pickled / deep-copied: see __getstate__)
@@ -268,11 +290,8 @@ class HipForwardMixin:
                 y = ops.linear_forward(w, x2d)
         except ops.QllmUnsupported:
             # 2/5/6/7/8-bit layers (and in-place 3/4-bit ones of ragged width) at 17 .. QLLM_BITPANEL_MAX_M rows: the fused mid-batch
-            # kernel, an entry of its own (csrc/bitpanel.hip; bias included)
-            y = self._bitpanel_linear(w, x2d, act_order_g_idx)
-            if y is None:
-                # the same layers above those rows, from QLLM_BITGEMM_MIN_M on: the fused 2..8-bit prefill kernel (csrc/bitgemm.hip)
-                y = self._bitgemm_linear(w, x2d, act_order_g_idx, key=x)
+            # kernel (bias included); the same layers above those rows, from QLLM_BITGEMM_MIN_M on: the fused 2..8-bit prefill kernel
+            y = self._bit_family_linear(w, x2d, act_order_g_idx, key=x)
             if y is None:
                 # e.g. 3/5/6/7/8-bit at prefill sizes: dequantise with the library kernel, then a plain library GEMM
                 wt = ops.dequant(w, x.device, torch.float16)
@@ -282,31 +301,19 @@ class HipForwardMixin:
         return y.reshape(x.shape[:-1] + (self.outfeatures,))
 
     @staticmethod
-    def _bitpanel_linear(w, x2d, act_order_g_idx=None):
-        """`ops.linear_forward_bitpanel` for a call no planner route serves, or None: act-order descriptors, other layouts, other row
-        counts, other activation types and the kernel's own refusal all leave the call to dequant + GEMM, exactly as before."""
-        if (act_order_g_idx is not None or w.layout not in (ops.LAYOUTS["GPTQ"], ops.LAYOUTS["HQQ"])
-                or x2d.dtype not in (torch.float16, torch.bfloat16) or not 17 <= x2d.shape[0] <= ops.bitpanel_max_m()):
-            return None
+    def _bit_family_linear(w, x2d, act_order_g_idx=None, key=None):
+        """The bit family's entry for a call no planner route serves (`bit_family_entry`: the mid-batch kernel, above its rows the
+        2..8-bit prefill kernel), or None: act-order descriptors, other layouts, other row counts, other activation types and the
+        kernel's own refusal all leave the call to dequant + GEMM.  `key`: see ops.linear_forward_bitgemm."""
+        entry = None if act_order_g_idx is not None else bit_family_entry(w.layout, x2d.dtype, x2d.shape[0])
         try:
-            return ops.linear_forward_bitpanel(w, x2d)
+            if entry == "bitpanel":
+                return ops.linear_forward_bitpanel(w, x2d)
+            if entry == "bitgemm":
+                return ops.linear_forward_bitgemm(w, x2d, key=key)
         except ops.QllmUnsupported:
-            return None
-
-    @staticmethod
-    def _bitgemm_linear(w, x2d, act_order_g_idx=None, key=None):
-        """`ops.linear_forward_bitgemm` for a call no planner route and not the mid-batch kernel serves, or None: act-order descriptors,
-        other layouts, other activation types, rows below `ops.bitgemm_min_m()` (0: never) or not above `ops.bitpanel_max_m()` and the
-        kernel's own refusal all leave the call to dequant + GEMM, exactly as before."""
-        lo = ops.bitgemm_min_m()
-        if (act_order_g_idx is not None or w.layout not in (ops.LAYOUTS["GPTQ"], ops.LAYOUTS["HQQ"])
-                or x2d.dtype not in (torch.float16, torch.bfloat16) or lo <= 0 or x2d.shape[0] < lo
-                or x2d.shape[0] <= ops.bitpanel_max_m()):
-            return None
-        try:
-            return ops.linear_forward_bitgemm(w, x2d, key=key)
-        except ops.QllmUnsupported:
-            return None
+            pass
+        return None
 
 
 def export_module_hooks(cls):

@@ -19,11 +19,9 @@ from typing import Optional, Sequence
 import torch
 
 from ... import ops
-from ._hip_forward import tensor_version
+from ._hip_forward import bitgroup_serves, tensor_version
 
 GROUP_MAX_M = 128  # the grouped entry point serves decode and mid-batch sizes (strips to 32 rows, the panel kernel to 128)
-BITGROUP_MAX_LAYERS = 4          # members of one qllm_linear_forward_bitgroup call
-BITGROUP_BITS = (2, 5, 6, 7, 8)  # widths whose groups go to ops.linear_forward_bitgroup at decode sizes (3 / 4 bits: the planner's grouped routes)
 
 # attribute names of siblings inside one parent module (Llama / Mistral / Qwen2, OPT, Falcon-style MLPs, ...)
 SIBLING_PATTERNS = (("q_proj", "k_proj", "v_proj"), ("gate_proj", "up_proj"), ("w1", "w3"))
@@ -111,8 +109,7 @@ class SiblingGroup:
             # 2 / 5 / 6 / 7 / 8 bits at decode sizes: the grouped bit-stream matvec, an entry of its own (csrc/bitgemv_group.hip) -- every
             # output is bit-identical to the layer's own launch.  Above its cutoff (QLLM_BITGROUP_MAX_M, profiles/bitgemv_group.md) and for
             # act-order members: the planner's entry, which refuses these widths -- the layers then run on their own.
-            if (a.bits in BITGROUP_BITS and len(descs) <= BITGROUP_MAX_LAYERS and not any(getattr(l, "act_order", None) for l in self.layers)
-                    and 1 <= m <= ops.bitgroup_max_m()):
+            if bitgroup_serves(a.bits, len(descs), any(getattr(l, "act_order", None) for l in self.layers), m):
                 outs = ops.linear_forward_bitgroup(descs, x2d)
             else:
                 outs = ops.linear_forward_grouped(descs, x2d)

@@ -9,7 +9,7 @@ import weakref
 import torch
 import torch.nn as nn
 
-from ._hip_forward import HipForwardMixin, export_module_hooks, _tkey, autogptq_compat, tensor_version
+from ._hip_forward import HipForwardMixin, bit_family_entry, export_module_hooks, _tkey, autogptq_compat, tensor_version
 from .compress_weight import CompressWeight, general_pack_on_row, general_unpack_on_row
 
 
@@ -240,29 +240,19 @@ class QuantLinearGPTQ(nn.Module, CompressWeight, HipForwardMixin):
                         # (M <= 16 and the knob are settled above: what is left is the layer's shape, K or the group size no multiple
                         #  of 32 -- the same answer every time.  Drop the copy, keep the key: no rebuild, no exception per forward)
                         self._ao = None
-            elif x.shape[-1] <= 28672 and x.dtype in (torch.float16, torch.bfloat16) and x.numel() // x.shape[-1] <= _ops().bitpanel_max_m():
-                # the 3..16-row scheme carried upward (17 .. QLLM_BITPANEL_MAX_M rows): gather x once -- siblings share the gather --
-                # and run the fused mid-batch kernel on the row-sorted copy.  (qllm_gather_columns stops at K = 28672.)  The kernel's
-                # refusal is a matter of the layer's shape: remembered per copy, the path below runs from then on
-                ao = self._ao_descriptor(azb, mid_batch=True)
-                if ao is not None and self._ao_panel_refused != self._ao_key:
-                    from ... import ops
+            elif x.shape[-1] <= 28672:
+                # the 3..16-row scheme carried upward: gather x once -- siblings share the gather -- and run the row-sorted copy (a plain
+                # GPTQ layer) through the entry `bit_family_entry` names: the fused mid-batch kernel at 17 .. QLLM_BITPANEL_MAX_M rows,
+                # from QLLM_BITGEMM_MIN_M rows on the fused 2..8-bit prefill kernel.  (qllm_gather_columns stops at K = 28672.)  A
+                # kernel's refusal is a matter of the layer's shape: remembered per copy and per kernel, the path below runs from then on
+                entry = bit_family_entry(_ops().LAYOUTS["GPTQ"], x.dtype, x.numel() // x.shape[-1])
+                refused = {"bitpanel": "_ao_panel_refused", "bitgemm": "_ao_gemm_refused"}.get(entry)
+                ao = self._ao_descriptor(azb, mid_batch=True) if entry else None
+                if ao is not None and getattr(self, refused) != self._ao_key:
                     try:
-                        y = ops.linear_forward_bitpanel(ao[0], _gathered(x, ao[1]))
+                        y = getattr(_ops(), "linear_forward_" + entry)(ao[0], _gathered(x, ao[1]))
                         return y.reshape(x.shape[:-1] + (self.outfeatures,))
-                    except ops.QllmUnsupported:
-                        self._ao_panel_refused = self._ao_key
-            elif (x.shape[-1] <= 28672 and x.dtype in (torch.float16, torch.bfloat16)
-                  and 0 < _ops().bitgemm_min_m() <= x.numel() // x.shape[-1] and x.numel() // x.shape[-1] > _ops().bitpanel_max_m()):
-                # ... and further, from QLLM_BITGEMM_MIN_M rows on: the same copy and the same shared gather, then the fused 2..8-bit
-                # prefill kernel (csrc/bitgemm.hip).  Its refusal is remembered per copy as well
-                ao = self._ao_descriptor(azb, mid_batch=True)
-                if ao is not None and self._ao_gemm_refused != self._ao_key:
-                    from ... import ops
-                    try:
-                        y = ops.linear_forward_bitgemm(ao[0], _gathered(x, ao[1]))
-                        return y.reshape(x.shape[:-1] + (self.outfeatures,))
-                    except ops.QllmUnsupported:
-                        self._ao_gemm_refused = self._ao_key
+                    except _ops().QllmUnsupported:
+                        setattr(self, refused, self._ao_key)
         g_idx = self.g_idx if self.act_order else None
         return self._hip_linear(x, g_idx, azb)

@@ -110,25 +110,56 @@ def _check_out(o: torch.Tensor, m: int, n_cols: int, x2d: torch.Tensor):
                            f"got {tuple(o.shape)} {o.dtype} on {o.device}")
 
 
+def _forward(ws_desc: Sequence[QllmWeight], x2d: torch.Tensor, outs, size, call, many: bool = False, prepare=None):
+    """The body every forward wrapper shares.  One descriptor: `outs` is the caller's output or None, and the output is returned; with
+    `many`, `outs` is a sequence of outputs, one per descriptor, or None, and a sequence is returned.  The outputs are checked (None:
+    allocated, [M, w.N] of x2d's type), zero rows return without a library call, then inside x2d's device the workspace is fetched --
+    `size(w_ref, m, dt)` bytes; None: the entry takes no workspace -- and `call(w_ref, y_ref, x, m, dt, ws)` makes the library call,
+    whose status is checked.  w_ref / y_ref: `byref(w)` and the output's pointer, or with `many` the descriptor array and the array of
+    output pointers; dt: x2d's type for the library.  `prepare()`: what a wrapper does once the outputs are checked and before anything
+    is allocated (also at zero rows); it returns the tensor passed as x instead of x2d."""
+    m = x2d.shape[0]
+    if outs is not None:
+        if many and len(outs) != len(ws_desc):
+            raise RuntimeError(f"outs must hold {len(ws_desc)} tensors, got {len(outs)}")
+        for o, w in zip(outs if many else (outs,), ws_desc):
+            _check_out(o, m, w.N, x2d)
+    x = x2d if prepare is None else prepare()
+    if outs is None:
+        outs = [torch.empty((m, w.N), dtype=x2d.dtype, device=x2d.device) for w in ws_desc]
+        outs = outs if many else outs[0]
+    if m == 0:
+        return outs
+    if many:
+        w_ref, y_ref = _array(ws_desc), (C.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
+    else:
+        w_ref, y_ref = C.byref(ws_desc[0]), outs.data_ptr()
+    dt = _act_dtype(x2d)
+    with torch.cuda.device(x2d.device):
+        rc = call(w_ref, y_ref, x, m, dt, workspace(x2d.device, size(w_ref, m, dt)) if size is not None else None)
+    if rc:
+        _lib.check(rc)
+    return outs
+
+
+def _describe(symbol: str, buflen: int, *args) -> str:
+    """A *_describe entry's text: `args` are its arguments in front of the buffer."""
+    buf = C.create_string_buffer(buflen)
+    _lib.check(getattr(_lib.load(), symbol)(*args, buf, buflen))
+    return buf.value.decode()
+
+
+def _array(ws_desc: Sequence[QllmWeight]):
+    return (QllmWeight * len(ws_desc))(*ws_desc)
+
+
 def linear_forward(w: QllmWeight, x2d: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """y[M,N] = x2d[M,K] . dequant(w) (+bias) through the fused HIP kernels.  Raises QllmUnsupported when the
     library has no fused kernel for the configuration (caller may then use dequant() + matmul)."""
     _check_x(x2d, (w,))
     lib = _lib.load()
-    m = x2d.shape[0]
-    if out is not None:
-        _check_out(out, m, w.N, x2d)
-    if m == 0:
-        return out if out is not None else torch.empty((0, w.N), dtype=x2d.dtype, device=x2d.device)
-    if out is None:
-        out = torch.empty((m, w.N), dtype=x2d.dtype, device=x2d.device)
-    with torch.cuda.device(x2d.device):
-        nbytes = lib.qllm_workspace_bytes_act(C.byref(w), m, _act_dtype(x2d))
-        ws = workspace(x2d.device, nbytes)
-        rc = lib.qllm_linear_forward(C.byref(w), x2d.data_ptr(), out.data_ptr(), m, _act_dtype(x2d), ws.data_ptr(),
-                                     ws.numel(), _stream_ptr())
-    _lib.check(rc)
-    return out
+    return _forward((w,), x2d, out, lib.qllm_workspace_bytes_act,
+                    lambda wr, y, x, m, dt, ws: lib.qllm_linear_forward(wr, x.data_ptr(), y, m, dt, ws.data_ptr(), ws.numel(), _stream_ptr()))
 
 
 def linear_forward_permuted(w: QllmWeight, perm: torch.Tensor, x2d: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -139,20 +170,9 @@ def linear_forward_permuted(w: QllmWeight, perm: torch.Tensor, x2d: torch.Tensor
     _check_x(x2d, (w,))
     _check_perm(perm, x2d)
     lib = _lib.load()
-    m = x2d.shape[0]
-    if out is not None:
-        _check_out(out, m, w.N, x2d)
-    if m == 0:
-        return out if out is not None else torch.empty((0, w.N), dtype=x2d.dtype, device=x2d.device)
-    if out is None:
-        out = torch.empty((m, w.N), dtype=x2d.dtype, device=x2d.device)
-    with torch.cuda.device(x2d.device):
-        nbytes = lib.qllm_workspace_bytes_act(C.byref(w), m, _act_dtype(x2d))
-        ws = workspace(x2d.device, nbytes)
-        rc = lib.qllm_linear_forward_permuted(C.byref(w), perm.data_ptr(), x2d.data_ptr(), out.data_ptr(), m, _act_dtype(x2d),
-                                              ws.data_ptr(), ws.numel(), _stream_ptr())
-    _lib.check(rc)
-    return out
+    return _forward((w,), x2d, out, lib.qllm_workspace_bytes_act,
+                    lambda wr, y, x, m, dt, ws: lib.qllm_linear_forward_permuted(wr, perm.data_ptr(), x.data_ptr(), y, m, dt, ws.data_ptr(),
+                                                                                 ws.numel(), _stream_ptr()))
 
 
 def bitpanel_max_m() -> int:
@@ -172,27 +192,15 @@ def linear_forward_bitpanel(w: QllmWeight, x2d: torch.Tensor, out: Optional[torc
     refusing these calls.  Raises QllmUnsupported for everything it does not serve (callers then use dequant() + matmul)."""
     _check_x(x2d, (w,))
     lib = _lib.load()
-    m = x2d.shape[0]
-    if out is not None:
-        _check_out(out, m, w.N, x2d)
-    elif m > 0:
-        out = torch.empty((m, w.N), dtype=x2d.dtype, device=x2d.device)
-    if m == 0:
-        return out if out is not None else torch.empty((0, w.N), dtype=x2d.dtype, device=x2d.device)
-    with torch.cuda.device(x2d.device):
-        ws = workspace(x2d.device, lib.qllm_bitpanel_workspace_bytes(C.byref(w), m))
-        rc = lib.qllm_linear_forward_bitpanel(C.byref(w), x2d.data_ptr(), out.data_ptr(), m, _act_dtype(x2d), ws.data_ptr(), ws.numel(),
-                                              _stream_ptr())
-    _lib.check(rc)
-    return out
+    return _forward((w,), x2d, out, lambda wr, m, dt: lib.qllm_bitpanel_workspace_bytes(wr, m),
+                    lambda wr, y, x, m, dt, ws: lib.qllm_linear_forward_bitpanel(wr, x.data_ptr(), y, m, dt, ws.data_ptr(), ws.numel(),
+                                                                                 _stream_ptr()))
 
 
 def bitpanel_describe(w: QllmWeight, m: int, have_workspace: bool = True) -> str:
     """The geometry `linear_forward_bitpanel` would launch for m rows ("bitpanel bits=.. cols=64 row_tiles=.. row_blocks=.. split_k=.."),
     or "unsupported (...)".  Pure host code."""
-    buf = C.create_string_buffer(512)
-    _lib.check(_lib.load().qllm_bitpanel_describe(C.byref(w), int(m), 1 if have_workspace else 0, buf, 512))
-    return buf.value.decode()
+    return _describe("qllm_bitpanel_describe", 512, C.byref(w), int(m), 1 if have_workspace else 0)
 
 
 def bitgemm_min_m() -> int:
@@ -215,41 +223,31 @@ def linear_forward_bitgemm(w: QllmWeight, x2d: torch.Tensor, out: Optional[torch
     (callers then use dequant() + matmul) -- decided BEFORE x is converted."""
     _check_x(x2d, (w,))
     lib = _lib.load()
-    m = x2d.shape[0]
-    if out is not None:
-        _check_out(out, m, w.N, x2d)
-    if m == 0:
-        return out if out is not None else torch.empty((0, w.N), dtype=x2d.dtype, device=x2d.device)
-    dt = _lib.DT_F16_IN_BF16_OUT if x2d.dtype == torch.bfloat16 else _act_dtype(x2d)
-    if dt != DT_F16:   # (nothing is converted for a call the entry refuses)
-        why = bitgemm_describe(w, m)
+    dt = DT_F16
+
+    def fp16_x():
+        nonlocal dt
+        if x2d.shape[0] == 0:
+            return x2d
+        dt = _lib.DT_F16_IN_BF16_OUT if x2d.dtype == torch.bfloat16 else _act_dtype(x2d)
+        if dt == DT_F16:
+            return x2d
+        why = bitgemm_describe(w, x2d.shape[0])   # (nothing is converted for a call the entry refuses)
         if why.startswith("unsupported"):
             raise QllmUnsupported(_lib.QLLM_ERR_UNSUPPORTED, why)
-        xin = bf16_as_f16(x2d, key)
-    else:
-        xin = x2d
-    if out is None:
-        out = torch.empty((m, w.N), dtype=x2d.dtype, device=x2d.device)
-    with torch.cuda.device(x2d.device):
-        ws = workspace(x2d.device, lib.qllm_bitgemm_workspace_bytes(C.byref(w), m))
-        rc = lib.qllm_linear_forward_bitgemm(C.byref(w), xin.data_ptr(), out.data_ptr(), m, dt, ws.data_ptr(), ws.numel(), _stream_ptr())
-    _lib.check(rc)
-    return out
+        return bf16_as_f16(x2d, key)
+    return _forward((w,), x2d, out, lambda wr, m, _: lib.qllm_bitgemm_workspace_bytes(wr, m),
+                    lambda wr, y, x, m, _, ws: lib.qllm_linear_forward_bitgemm(wr, x.data_ptr(), y, m, dt, ws.data_ptr(), ws.numel(), _stream_ptr()),
+                    prepare=fp16_x)
 
 
 def bitgemm_describe(w: QllmWeight, m: int, have_workspace: bool = True) -> str:
     """The geometry `linear_forward_bitgemm` would launch for m rows ("bitgemm bits=.. tile=256x128 tiles=.. split_k=.."), or
     "unsupported (...)".  Pure host code."""
-    buf = C.create_string_buffer(512)
-    _lib.check(_lib.load().qllm_bitgemm_describe(C.byref(w), int(m), 1 if have_workspace else 0, buf, 512))
-    return buf.value.decode()
+    return _describe("qllm_bitgemm_describe", 512, C.byref(w), int(m), 1 if have_workspace else 0)
 
 
 _LAST_CONVERT: dict = {}
-
-
-def _tensor_version(t) -> int:
-    return 0 if t.is_inference() else t._version
 
 
 def bf16_as_f16(x2d: torch.Tensor, key: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -294,17 +292,11 @@ def linear_forward_bf16_via_f16(w: QllmWeight, x2d: torch.Tensor, key: Optional[
         raise QllmUnsupported(_lib.QLLM_ERR_UNSUPPORTED, "bf16 prefill calls only")
     if w.bits != 4 or not plan_describe([w], x2d.shape[0]).startswith("gemm3"):
         raise QllmUnsupported(_lib.QLLM_ERR_UNSUPPORTED, "not a call of the 256x128 prefill kernel")
+    # (the workspace is sized for fp16 activations: the copy the plain bf16 call would stage there is made here, and shared)
     lib = _lib.load()
-    m = x2d.shape[0]
-    xh = bf16_as_f16(x2d, key)
-    out = torch.empty((m, w.N), dtype=torch.bfloat16, device=x2d.device)
-    with torch.cuda.device(x2d.device):
-        nbytes = lib.qllm_workspace_bytes_act(C.byref(w), m, DT_F16)
-        ws = workspace(x2d.device, nbytes)
-        rc = lib.qllm_linear_forward(C.byref(w), xh.data_ptr(), out.data_ptr(), m, _lib.DT_F16_IN_BF16_OUT, ws.data_ptr(), ws.numel(),
-                                     _stream_ptr())
-    _lib.check(rc)
-    return out
+    return _forward((w,), x2d, None, lambda wr, m, _: lib.qllm_workspace_bytes_act(wr, m, DT_F16),
+                    lambda wr, y, xh, m, _, ws: lib.qllm_linear_forward(wr, xh.data_ptr(), y, m, _lib.DT_F16_IN_BF16_OUT, ws.data_ptr(), ws.numel(),
+                                                                        _stream_ptr()), prepare=lambda: bf16_as_f16(x2d, key))
 
 
 def _bf16_native(w: QllmWeight) -> bool:
@@ -340,27 +332,10 @@ def linear_forward_grouped(ws_desc: Sequence[QllmWeight], x2d: torch.Tensor,
                            outs: Optional[Sequence[torch.Tensor]] = None):
     """Several layers sharing x (q/k/v, gate/up) in ONE launch (decode sizes only)."""
     _check_x(x2d, ws_desc)
-    lib = _lib.load()
-    n = len(ws_desc)
-    m = x2d.shape[0]
-    if outs is not None:
-        if len(outs) != n:
-            raise RuntimeError(f"outs must hold {n} tensors, got {len(outs)}")
-        for o, w in zip(outs, ws_desc):
-            _check_out(o, m, w.N, x2d)
-    if m == 0:
-        return list(outs) if outs is not None else [torch.empty((0, w.N), dtype=x2d.dtype, device=x2d.device) for w in ws_desc]
-    if outs is None:
-        outs = [torch.empty((m, w.N), dtype=x2d.dtype, device=x2d.device) for w in ws_desc]
-    arr = (QllmWeight * n)(*ws_desc)
-    ys = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
-    with torch.cuda.device(x2d.device):
-        nbytes = grouped_workspace_bytes(ws_desc, m, _act_dtype(x2d), x2d.device)
-        wsp = workspace(x2d.device, nbytes)
-        rc = lib.qllm_linear_forward_grouped(arr, ys, n, x2d.data_ptr(), m, _act_dtype(x2d), wsp.data_ptr(),
-                                             wsp.numel(), _stream_ptr())
-    _lib.check(rc)
-    return list(outs)
+    lib, n = _lib.load(), len(ws_desc)
+    return list(_forward(ws_desc, x2d, outs, lambda arr, m, dt: grouped_workspace_bytes(ws_desc, m, dt, x2d.device),
+                         lambda arr, ys, x, m, dt, ws: lib.qllm_linear_forward_grouped(arr, ys, n, x.data_ptr(), m, dt, ws.data_ptr(), ws.numel(),
+                                                                                       _stream_ptr()), many=True))
 
 
 def bitgroup_max_m() -> int:
@@ -377,34 +352,16 @@ def linear_forward_bitgroup(ws_desc: Sequence[QllmWeight], x2d: torch.Tensor,
     An entry of its own -- `linear_forward_grouped` and `plan_describe` keep refusing these widths.  Raises QllmUnsupported for
     everything it does not serve (callers then run the layers one by one)."""
     _check_x(x2d, ws_desc)
-    lib = _lib.load()
-    n = len(ws_desc)
-    m = x2d.shape[0]
-    if outs is not None:
-        if len(outs) != n:
-            raise RuntimeError(f"outs must hold {n} tensors, got {len(outs)}")
-        for o, w in zip(outs, ws_desc):
-            _check_out(o, m, w.N, x2d)
-    if m == 0:
-        return list(outs) if outs is not None else [torch.empty((0, w.N), dtype=x2d.dtype, device=x2d.device) for w in ws_desc]
-    if outs is None:
-        outs = [torch.empty((m, w.N), dtype=x2d.dtype, device=x2d.device) for w in ws_desc]
-    arr = (QllmWeight * n)(*ws_desc)
-    ys = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
-    with torch.cuda.device(x2d.device):
-        wsp = workspace(x2d.device, lib.qllm_bitgroup_workspace_bytes(arr, n, m))
-        rc = lib.qllm_linear_forward_bitgroup(arr, ys, n, x2d.data_ptr(), m, _act_dtype(x2d), wsp.data_ptr(), wsp.numel(), _stream_ptr())
-    _lib.check(rc)
-    return list(outs)
+    lib, n = _lib.load(), len(ws_desc)
+    return list(_forward(ws_desc, x2d, outs, lambda arr, m, dt: lib.qllm_bitgroup_workspace_bytes(arr, n, m),
+                         lambda arr, ys, x, m, dt, ws: lib.qllm_linear_forward_bitgroup(arr, ys, n, x.data_ptr(), m, dt, ws.data_ptr(), ws.numel(),
+                                                                                        _stream_ptr()), many=True))
 
 
 def bitgroup_describe(ws_desc: Sequence[QllmWeight], m: int, have_workspace: bool = True) -> str:
     """The geometry `linear_forward_bitgroup` would launch for m rows ("bitgroup bits=.. cols=32 layers=.. blocks=.. split_k=a,b,c", the
     splits in the order of `ws_desc`), or "unsupported (...)".  Pure host code."""
-    arr = (QllmWeight * len(ws_desc))(*ws_desc)
-    buf = C.create_string_buffer(512)
-    _lib.check(_lib.load().qllm_bitgroup_describe(arr, len(ws_desc), int(m), 1 if have_workspace else 0, buf, 512))
-    return buf.value.decode()
+    return _describe("qllm_bitgroup_describe", 512, _array(ws_desc), len(ws_desc), int(m), 1 if have_workspace else 0)
 
 
 def linear_forward_swiglu(w: QllmWeight, gate2d: torch.Tensor, up2d: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -416,26 +373,16 @@ def linear_forward_swiglu(w: QllmWeight, gate2d: torch.Tensor, up2d: torch.Tenso
     _check_input(up2d, "up")
     if up2d.shape != gate2d.shape or up2d.dtype != gate2d.dtype or up2d.device != gate2d.device:
         raise RuntimeError(f"up must match gate: {tuple(gate2d.shape)} {gate2d.dtype} on {gate2d.device}, got {tuple(up2d.shape)} {up2d.dtype} on {up2d.device}")
-    m = gate2d.shape[0]
-    if out is not None:
-        _check_out(out, m, w.N, gate2d)
-    if m == 0:
-        return out if out is not None else torch.empty((0, w.N), dtype=gate2d.dtype, device=gate2d.device)
-    if out is None:
-        out = torch.empty((m, w.N), dtype=gate2d.dtype, device=gate2d.device)
-    with torch.cuda.device(gate2d.device):
-        rc = _lib.load().qllm_linear_forward_swiglu(C.byref(w), gate2d.data_ptr(), up2d.data_ptr(), out.data_ptr(), m, _act_dtype(gate2d),
-                                                    _lib.ACT_SILU, _stream_ptr())
-    _lib.check(rc)
-    return out
+    lib = _lib.load()
+    return _forward((w,), gate2d, out, None,
+                    lambda wr, y, gate, m, dt, ws: lib.qllm_linear_forward_swiglu(wr, gate.data_ptr(), up2d.data_ptr(), y, m, dt, _lib.ACT_SILU,
+                                                                                  _stream_ptr()))
 
 
 def swiglu_describe(w: QllmWeight, m: int) -> str:
     """What `linear_forward_swiglu` would launch for m rows: "swiglu " + the plan line of the plain call ("swiglu strip1 nw=.. round=..
     ..."), or "refused: ..." with the entry's refusal text.  Pure host code."""
-    buf = C.create_string_buffer(640)
-    _lib.check(_lib.load().qllm_swiglu_describe(C.byref(w), int(m), buf, 640))
-    return buf.value.decode()
+    return _describe("qllm_swiglu_describe", 640, C.byref(w), int(m))
 
 
 def _rstd_buffer(return_rstd, m: int, x2d: torch.Tensor):
@@ -488,33 +435,22 @@ def linear_forward_rmsnorm(ws_desc: Sequence[QllmWeight], x2d: torch.Tensor, wei
     and `linear_forward_grouped`)."""
     _check_x(x2d, ws_desc)
     _check_norm_weight(weight, x2d)
-    n = len(ws_desc)
-    m = x2d.shape[0]
-    if outs is not None:
-        if len(outs) != n:
-            raise RuntimeError(f"outs must hold {n} tensors, got {len(outs)}")
-        for o, w in zip(outs, ws_desc):
-            _check_out(o, m, w.N, x2d)
-    else:
-        outs = [torch.empty((m, w.N), dtype=x2d.dtype, device=x2d.device) for w in ws_desc]
-    rstd = _rstd_buffer(return_rstd, m, x2d)
-    if m > 0:
-        arr = (QllmWeight * n)(*ws_desc)
-        ys = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
-        with torch.cuda.device(x2d.device):
-            rc = _lib.load().qllm_linear_forward_rmsnorm(arr, ys, n, x2d.data_ptr(), weight.data_ptr(), float(eps), m, _act_dtype(x2d),
-                                                         rstd.data_ptr() if rstd is not None else None, _stream_ptr())
-        _lib.check(rc)
-    return (list(outs), rstd) if rstd is not None else list(outs)
+    lib, n, rstd = _lib.load(), len(ws_desc), None
+
+    def rstd_buffer():   # (also at zero rows, where the outputs and rstd come back empty)
+        nonlocal rstd
+        rstd = _rstd_buffer(return_rstd, x2d.shape[0], x2d)
+        return x2d
+    outs = list(_forward(ws_desc, x2d, outs, None,
+                         lambda arr, ys, x, m, dt, ws: lib.qllm_linear_forward_rmsnorm(arr, ys, n, x.data_ptr(), weight.data_ptr(), float(eps), m, dt,
+                                                                                       _ptr(rstd), _stream_ptr()), many=True, prepare=rstd_buffer))
+    return (outs, rstd) if rstd is not None else outs
 
 
 def rmsnorm_describe(ws_desc: Sequence[QllmWeight], m: int) -> str:
     """What `linear_forward_rmsnorm` would launch for m rows: "rmsnorm " + the plan line of the plain grouped call ("rmsnorm strip1 nw=..
     round=.. ..."), or "refused: ..." with the entry's refusal text.  Pure host code."""
-    n = len(ws_desc)
-    buf = C.create_string_buffer(768)
-    _lib.check(_lib.load().qllm_rmsnorm_describe((QllmWeight * n)(*ws_desc), n, int(m), buf, 768))
-    return buf.value.decode()
+    return _describe("qllm_rmsnorm_describe", 768, _array(ws_desc), len(ws_desc), int(m))
 
 
 def dequant(w: QllmWeight, device: torch.device, dtype=torch.float16, transposed: bool = False) -> torch.Tensor:
@@ -533,10 +469,7 @@ def dequant(w: QllmWeight, device: torch.device, dtype=torch.float16, transposed
 
 def plan_describe(ws_desc: Sequence[QllmWeight], m: int, have_workspace: bool = True) -> str:
     """Which kernel `linear_forward` (one descriptor) / `linear_forward_grouped` (several) would run for m rows."""
-    arr = (QllmWeight * len(ws_desc))(*ws_desc)
-    buf = C.create_string_buffer(256)
-    _lib.check(_lib.load().qllm_plan_describe(arr, len(ws_desc), int(m), 1 if have_workspace else 0, buf, 256))
-    return buf.value.decode()
+    return _describe("qllm_plan_describe", 256, _array(ws_desc), len(ws_desc), int(m), 1 if have_workspace else 0)
 
 
 def set_knob(name: str, value: int) -> None:

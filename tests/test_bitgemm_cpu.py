@@ -11,6 +11,8 @@ import sys
 
 import pytest
 
+import capi_fakes
+from capi_fakes import W
 from qllm_amd import _lib
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
@@ -24,18 +26,12 @@ def lib():
     return _lib.load()
 
 
-def W(bits=8, K=4096, N=4096, g=128, layout=_lib.LAYOUT_GPTQ, g_idx=None, qzeros=12288, qweight=4096):
-    return _lib.QllmWeight(qweight, 8192, qzeros, g_idx, None, K, N, g, bits, layout, 0)
-
-
 def call(lib, w, x=20480, y=24576, m=300, dt=_lib.DT_F16):
     return lib.qllm_linear_forward_bitgemm(C.byref(w), x, y, m, dt, None, 0, None)
 
 
 def describe(lib, w, m, have_ws=1):
-    buf = C.create_string_buffer(512)
-    assert lib.qllm_bitgemm_describe(C.byref(w), m, have_ws, buf, 512) == 0, _lib.last_error()
-    return buf.value.decode()
+    return capi_fakes.describe(lib, "bitgemm", w, m, have_ws)
 
 
 def test_symbols_are_exported_and_declared(lib):

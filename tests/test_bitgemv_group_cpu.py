@@ -8,11 +8,13 @@ import re
 
 import pytest
 
+import capi_fakes
+from capi_fakes import W, arr
 from kernel_resources import resources
 from qllm_amd import _lib
 
 HEADER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "qllm_mi355x.h")
-X, Y0 = 20480, 24576   # fake device addresses (16-byte aligned)
+X, Y0 = capi_fakes.X, capi_fakes.Y   # fake device addresses (16-byte aligned)
 
 # Llama-2-7B q/k/v, gate/up and a GQA triple
 SHAPE_SETS = {"qkv": (4096, (4096, 4096, 4096)), "gate_up": (4096, (11008, 11008)), "gqa": (4096, (4096, 1024, 1024))}
@@ -25,14 +27,6 @@ def lib():
     return _lib.load()
 
 
-def W(bits=8, K=4096, N=4096, g=128, layout=_lib.LAYOUT_GPTQ, g_idx=None, qzeros=12288, azb=0):
-    return _lib.QllmWeight(4096, 8192, qzeros, g_idx, None, K, N, g, bits, layout, azb)
-
-
-def arr(ws):
-    return (_lib.QllmWeight * len(ws))(*ws)
-
-
 def call(lib, ws, x=X, ys=None, m=1, n=None):
     n = len(ws) if n is None else n
     ys = [Y0 + 4096 * i for i in range(len(ws))] if ys is None else ys
@@ -40,9 +34,7 @@ def call(lib, ws, x=X, ys=None, m=1, n=None):
 
 
 def describe(lib, ws, m, have_ws=1):
-    buf = C.create_string_buffer(512)
-    assert lib.qllm_bitgroup_describe(arr(ws), len(ws), m, have_ws, buf, 512) == 0, _lib.last_error()
-    return buf.value.decode()
+    return capi_fakes.describe(lib, "bitgroup", ws, m, have_ws)
 
 
 def geometry(lib, ws, m, have_ws=1):

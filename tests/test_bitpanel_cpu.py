@@ -7,6 +7,8 @@ import re
 
 import pytest
 
+import capi_fakes
+from capi_fakes import W
 from qllm_amd import _lib
 
 HEADER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "qllm_mi355x.h")
@@ -19,18 +21,12 @@ def lib():
     return _lib.load()
 
 
-def W(bits=8, K=4096, N=4096, g=128, layout=_lib.LAYOUT_GPTQ, g_idx=None, qzeros=12288):
-    return _lib.QllmWeight(4096, 8192, qzeros, g_idx, None, K, N, g, bits, layout, 0)
-
-
 def call(lib, w, x=20480, y=24576, m=64):
     return lib.qllm_linear_forward_bitpanel(C.byref(w), x, y, m, _lib.DT_F16, None, 0, None)
 
 
 def describe(lib, w, m, have_ws=1):
-    buf = C.create_string_buffer(512)
-    assert lib.qllm_bitpanel_describe(C.byref(w), m, have_ws, buf, 512) == 0, _lib.last_error()
-    return buf.value.decode()
+    return capi_fakes.describe(lib, "bitpanel", w, m, have_ws)
 
 
 def geometry(lib, w, m, have_ws=1):
