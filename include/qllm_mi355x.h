@@ -122,7 +122,7 @@ int qllm_is_lab_build(void);
  * other threads: set them before serving.  Settable names (values outside the range every built kernel covers are refused):
  *   QLLM_STRIP1 0|1|2, QLLM_STRIP1_MAX_M 1..4, QLLM_STRIP1_3BIT 0|1, QLLM_PANEL 0|1, QLLM_PANEL_MIN_M 17..129, QLLM_PANEL_GROUP_MIN_M 17..129, QLLM_GEMM2 0|1, QLLM_GEMM3 0|1,
  *   QLLM_GEMM2_MIN_M >= 33, QLLM_GEMM3_MIN_M >= 0 (0: the measured 384 / 768 line), QLLM_GEMM2_SPLITK 0|1, QLLM_GEMM3_TAIL 0|1, QLLM_GEMM3_BF16 0|1, QLLM_GEMM3_GROUP 0|1,
- *   QLLM_SKINNY_MAX_M 0..64, QLLM_STRIP_MIN >= 0, QLLM_BITGEMV 0|1, QLLM_BITPANEL 0|1, QLLM_BITPANEL_LDS 0|1, QLLM_BITPANEL_MAX_M 17..512 (the last three: qllm_linear_forward_bitpanel, no route),
+ *   QLLM_SKINNY_MAX_M 0..64, QLLM_STRIP_MIN >= 0, QLLM_S1_T256_NW16 0|1 (batch 1, K = 6272..8192: 16 waves x 16 k-steps instead of 8 x 32), QLLM_BITGEMV 0|1, QLLM_BITPANEL 0|1, QLLM_BITPANEL_LDS 0|1, QLLM_BITPANEL_MAX_M 17..512 (the last three: qllm_linear_forward_bitpanel, no route),
  *   QLLM_BITGROUP 0|1, QLLM_BITGROUP_MAX_M 0..16 (qllm_linear_forward_bitgroup, no route),
  *   QLLM_BITGEMM 0|1, QLLM_BITGEMM_MIN_M 129..65536 (qllm_linear_forward_bitgemm, no route).
  * qllm_plan_describe() reflects them (it asks the same decision functions the forward calls execute).  QLLM_ERR_INVALID for any other name. */

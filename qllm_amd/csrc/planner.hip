@@ -34,6 +34,7 @@ static Settable kSettable[] = {
     {"QLLM_GEMM3_BF16", 0, 1, 0, 0},           // 0: bf16 prefill through the fp16 conversion pre-pass (the reference's shim) instead of bf16 MFMA
     {"QLLM_SKINNY_MAX_M", 0, 64, 0, 0},        // rows up to which the split-K decode kernel serves the reference layouts in place
     {"QLLM_STRIP_MIN", 0, 1 << 20, 0, 0},      // fewest 16-column strips the full-K strip kernels take (0: never)
+    {"QLLM_S1_T256_NW16", 0, 1, 0, 0},         // 1: the batch-1 kernel takes K = 6272..8192 with 16 waves x 16 k-steps instead of 8 x 32 (every form table builds both)
     {"QLLM_BITGEMV", 0, 1, 0, 0},              // 0: 2 / 5 / 6 / 7 / 8-bit decode calls refused (callers then dequantise + GEMM: the reference's branch)
     // (no route: the two knobs of qllm_linear_forward_bitpanel, bitpanel.hip)
     {"QLLM_BITPANEL", 0, 1, 0, 0},             // 0: the mid-batch entry refuses every call
