@@ -401,7 +401,7 @@ int qllm_bitgroup_describe(const qllm_weight_t *w, int32_t n_weights, int32_t M,
  * QLLM_STRIP1* knob that takes the shape off that kernel, another `act` -- and the caller runs the activation and
  * qllm_linear_forward as before.  QLLM_ERR_INVALID: NULL / misaligned pointers, M < 1, y aliasing an input.  Every error is raised
  * before any device work.  No workspace, no host synchronisation; hipGraph-capturable.  Not built: GELU gates, the fused all-reduce
- * form, a norm in front or a residual behind.
+ * form, a norm in front (a residual behind: qllm_linear_forward_residual below).
  * ABI: the two symbols are ADDITIVE within ABI 7 (QLLM_ABI_VERSION is unchanged, as for the bitpanel / bitgroup symbols): probe for them
  * by symbol.  The reference's counterpart was its fused_mlp / QuantLlamaMLP (import left commented out in
  * qllm/modeling/q_layers/__init__.py:4). */
@@ -441,6 +441,36 @@ int qllm_linear_forward_rmsnorm(const qllm_weight_t *w, void *const *y, int32_t 
 /* What that call would launch, as text: "rmsnorm " followed by the plan line of the plain grouped call ("rmsnorm strip1 nw=8 round=16
  * exact grid=strips x 3 layout=strip-major"), or "refused: " and the refusal text.  Pure host code. */
 int qllm_rmsnorm_describe(const qllm_weight_t *w, int32_t n_weights, int32_t M, char *buf, size_t buflen);
+
+/* ---- the residual add of a decoder layer, fused into the launch in front of it --------------------------------------------------------- */
+/* y[1,N] = residual[1,N] + x[1,K] . dequant(w) (+ bias)                    (up == NULL)
+ * y[1,N] = residual[1,N] + (act(x) * up)[1,K] . dequant(w) (+ bias)        (up != NULL: x is the gate vector, act = QLLM_ACT_SILU)
+ * with the add formed INSIDE the linear launch (csrc/strip1_resid.hip, csrc/strip1_swiglu_resid.hip: the RESID forms of the batch-1
+ * kernel, csrc/strip1_kernel.hpp) -- hidden = residual + o_proj(attn) and hidden = residual + down_proj(act(gate) * up) of a decoder
+ * layer without the elementwise kernel behind the launch.  The 16 threads of a block that store its outputs round their fp32 value to
+ * act_dtype as the plain launch does, add their element of `residual` in fp32 and round again: the eager add of two tensors.
+ * Contract: the launch returns BIT FOR BIT residual + qllm_linear_forward(w, x) (residual + qllm_linear_forward_swiglu(w, x, up))
+ * as torch adds two fp16 / bf16 tensors, on all finite inputs.  The element is loaded with the kernel's first loads, so the epilogue
+ * waits for nothing new -- except in the ten SWIGLU forms that sit at their register bound (plain 128-wide groups with rounds of 24,
+ * 56 and 64 k-steps; Llama-2-7B's down_proj, K = 11008, is one), which issue the load behind their last MFMA, ahead of the cross-wave
+ * sum it is needed after.
+ * x / up: contiguous [1, K] of act_dtype (QLLM_F16 / QLLM_BF16), 16-byte aligned; residual / y: [1, N] of act_dtype, aligned to the
+ * element.  y may be `residual` itself (the thread that writes an element is the only one that reads it, and it reads first); any other
+ * overlap of y with residual, x or up is QLLM_ERR_INVALID.
+ * Served: exactly the M = 1 calls qllm_linear_forward runs on the batch-1 kernel ("strip1 ..." in qllm_plan_describe) for native-layout
+ * layers (NATIVE, NATIVE_F16Z) -- 4 bits with 128- or 64-wide groups, and 3 bits -- with the same waves x round: what
+ * qllm_linear_forward_swiglu serves at one row.  QLLM_ERR_UNSUPPORTED for everything else (M >= 2, other layouts and widths, act-order,
+ * a QLLM_STRIP1* knob that takes the shape off that kernel): run the launch and add.  QLLM_ERR_INVALID: NULL x / residual / y,
+ * misaligned x / up (16 bytes) or residual / y (the element), M < 1, a bad act_dtype, an overlap as above, act != QLLM_ACT_SILU with up
+ * set.  Every error is raised before any device work.  No workspace, no host synchronisation; hipGraph-capturable.  Not built: M > 1,
+ * the fused all-reduce form with a residual, the 2/5/6/7/8-bit widths.
+ * ABI: the two symbols are ADDITIVE within ABI 7 (QLLM_ABI_VERSION is unchanged, as for the SwiGLU and RMSNorm symbols): probe for them
+ * by symbol. */
+int qllm_linear_forward_residual(const qllm_weight_t *w, const void *x, const void *up, const void *residual, void *y, int32_t M,
+                                 int32_t act_dtype, int32_t act, void *stream);
+/* What that call would launch, as text: "residual " (swiglu != 0: "residual swiglu ") followed by the plan line of the plain call
+ * ("residual strip1 nw=8 round=16 exact grid=strips x 1 layout=strip-major"), or "refused: " and the refusal text.  Pure host code. */
+int qllm_residual_describe(const qllm_weight_t *w, int32_t M, int32_t swiglu, char *buf, size_t buflen);
 
 /* ---- HQQ quantizer (ABI 7) ---------------------------------------------------------------------------------------------------------- */
 /* W[N,K] (fp16 / bf16 / fp32 by w_dtype, row-major, 16-byte aligned) -> the HQQ layer buffers: qweight i32 [K*bits/32][N], scales f16

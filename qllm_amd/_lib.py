@@ -103,6 +103,8 @@ SIGNATURES = {
     "qllm_rmsnorm": (C.c_int, [vp, vp, vp, i32, i32, C.c_float, i32, vp, vp]),
     "qllm_linear_forward_rmsnorm": (C.c_int, [wp, C.POINTER(vp), i32, vp, vp, C.c_float, i32, i32, vp, vp]),
     "qllm_rmsnorm_describe": (C.c_int, [wp, i32, i32, C.c_char_p, sz]),
+    "qllm_linear_forward_residual": (C.c_int, [wp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "qllm_residual_describe": (C.c_int, [wp, i32, i32, C.c_char_p, sz]),
 }
 EXPORTS = tuple(SIGNATURES)
 

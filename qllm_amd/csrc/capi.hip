@@ -2,7 +2,7 @@
 // sites: /root/reference/csrc/ort_cuda/ort_ops.cc:64-73,99-107; csrc/awq_cuda/quantization/gemm_cuda_gen.cu:1128-1135),
 // parameter-block fills, workspace carving, launches.  Which kernel runs is decided in planner.hip.  No allocation, no host sync, no
 // global mutable state beyond thread-local error text.
-// The kernels with an entry of their own (qllm_linear_forward_permuted / _bitpanel / _bitgemm / _bitgroup / _swiglu / _rmsnorm: the planner
+// The kernels with an entry of their own (qllm_linear_forward_permuted / _bitpanel / _bitgemm / _bitgroup / _swiglu / _rmsnorm / _residual: the planner
 // does not know them) each keep ONE *_check / decide_* that their forward, *_workspace_bytes and *_describe entries all ask.  What those
 // entries do around it is written once: check_layer_count + check_layers (an array of layers), check_describe_args, describe_refusal
 // (a refusal as text), counters_and_slabs (a workspace size) and fill_bit_params (the bit family's parameter blocks).
@@ -886,6 +886,50 @@ int qllm_swiglu_describe(const qllm_weight_t *w, int32_t M, char *buf, size_t bu
   if (rc == QLLM_OK) rc = decide_swiglu(w, M, QLLM_ACT_SILU, &d.strip);
   if (rc) return describe_refusal(rc, kRefused, buf, buflen);
   return describe_fused("swiglu", d, w, 1, M, buf, buflen);
+}
+
+// y = residual + linear(w, x), or residual + linear(w, act(x) * up): the RESID forms of the batch-1 kernel (strip1_resid.hip,
+// strip1_swiglu_resid.hip); decide_residual says what is served
+int qllm_linear_forward_residual(const qllm_weight_t *w, const void *x, const void *up, const void *residual, void *y, int32_t M, int32_t act_dtype,
+                                 int32_t act, void *stream) {
+  clear_error();
+  int rc = validate_weight(w);
+  if (rc) return rc;
+  if (!residual) return set_error(QLLM_ERR_INVALID, "residual must not be NULL");
+  rc = check_io(x, y, M, act_dtype);
+  if (rc) return rc;
+  if ((uintptr_t)up % 16 != 0) return set_error(QLLM_ERR_INVALID, "up must be 16-byte aligned");
+  if ((uintptr_t)residual % 2 != 0 || (uintptr_t)y % 2 != 0) return set_error(QLLM_ERR_INVALID, "residual / y must be aligned to the element size");
+  // y may BE the residual row (the thread that writes element n is the only one that reads it, and reads first); nothing else may overlap
+  auto overlap = [](const void *a, size_t na, const void *b, size_t nb) { return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na; };
+  const size_t ybytes = (size_t)M * w->N * 2, xbytes = (size_t)M * w->K * 2;
+  if (y != residual && overlap(y, ybytes, residual, ybytes)) return set_error(QLLM_ERR_INVALID, "y may be residual itself, but must not overlap it otherwise");
+  if (overlap(y, ybytes, x, xbytes) || (up && overlap(y, ybytes, up, xbytes))) return set_error(QLLM_ERR_INVALID, "y must not alias x / up (every block reads the whole row)");
+  if (up && act != QLLM_ACT_SILU) return set_error(QLLM_ERR_INVALID, "act=%d is not an activation (QLLM_ACT_SILU) for the up vector", act);
+  StripPlan pl;
+  rc = decide_residual(w, M, &pl);
+  if (rc) return rc;
+  Strip1Params p;
+  void *ys[1] = {y};
+  fill_strip1_params(p, w, ys, 1, x, M, act_dtype);
+  p.x2 = up;
+  p.residual = residual;
+  return up ? launch_strip1_swiglu_resid(p, pl.one_nw, pl.one_maxs, w->N / 16, (hipStream_t)stream)
+            : launch_strip1_resid(p, pl.one_nw, pl.one_maxs, w->N / 16, (hipStream_t)stream);
+}
+
+// what that call would launch, as text ("residual " / "residual swiglu " + the plain call's plan line), or why it is refused -- no device work
+int qllm_residual_describe(const qllm_weight_t *w, int32_t M, int32_t swiglu, char *buf, size_t buflen) {
+  clear_error();
+  if (!w || !buf || buflen < 64) return set_error(QLLM_ERR_INVALID, "w / buf must not be NULL (buf >= 64 bytes)");
+  if (M <= 0) return set_error(QLLM_ERR_INVALID, "M must be >= 1 (got %d)", M);
+  Decision d;
+  memset(&d, 0, sizeof(d));
+  d.route = ROUTE_STRIP;
+  int rc = validate_weight(w);
+  if (rc == QLLM_OK) rc = decide_residual(w, M, &d.strip);
+  if (rc) return describe_refusal(rc, kRefused, buf, buflen);
+  return describe_fused(swiglu ? "residual swiglu" : "residual", d, w, 1, M, buf, buflen);
 }
 
 // y = weight * round(x * rstd) per row: the standalone RMSNorm kernel (rmsnorm.hip)

@@ -134,6 +134,9 @@ struct Strip1Params {
   const void *norm_w;
   float norm_eps;
   float *rstd_out;
+  // y = residual + linear(..) in the launch (the RESID forms, strip1_resid.hip / strip1_swiglu_resid.hip): one row [N] in the activation
+  // type; may be prob[0].y itself.  Read by those forms only
+  const void *residual;
 };
 
 // ---- bitgemv.hip (round 6): fused decode matvec for the widths the MFMA strips do not take (2, 5, 6, 7, 8 bits; row-stream layouts) -----
@@ -267,6 +270,8 @@ int launch_strip1(const Strip1Params &p, int nw, int maxs, int n_prob, int max_s
 int launch_strip1_allreduce(const Strip1Params &p, int nw, int maxs, int n_strips, hipStream_t stream);  // (p.ar_* set; one layer)
 int launch_strip1_swiglu(const Strip1Params &p, int nw, int maxs, int n_strips, hipStream_t stream);     // strip1_swiglu.hip (p.x2 set; one layer)
 int launch_strip1_norm(const Strip1Params &p, int nw, int maxs, int n_prob, int max_strips, hipStream_t stream);  // strip1_norm.hip (p.norm_* set; M = 1)
+int launch_strip1_resid(const Strip1Params &p, int nw, int maxs, int n_strips, hipStream_t stream);         // strip1_resid.hip (p.residual set; one layer, M = 1)
+int launch_strip1_swiglu_resid(const Strip1Params &p, int nw, int maxs, int n_strips, hipStream_t stream);  // strip1_swiglu_resid.hip (p.x2, p.residual set)
 
 // ---- rmsnorm.hip: y = weight * round(x * rstd), one block per row (the standalone counterpart of the NORM forms) ------------------------
 constexpr int kRmsNormMaxK = 65536;

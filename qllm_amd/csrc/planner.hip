@@ -585,6 +585,19 @@ int decide_swiglu(const qllm_weight_t *w, int M, int act, StripPlan *plan) {
   return QLLM_OK;
 }
 
+// The fused residual add behind o_proj / down_proj (strip1_resid.hip, strip1_swiglu_resid.hip): one row, and there exactly what
+// decide_swiglu serves -- the calls the plain entry runs on the batch-1 kernel for native-layout layers -- with the same waves x round.
+// Everything else keeps today's path (the launch, then the elementwise add).
+int decide_residual(const qllm_weight_t *w, int M, StripPlan *plan) {
+  static const char kInstead[] = "run the launch and add the residual";
+  *plan = StripPlan{};
+  if (M != 1) return set_error(QLLM_ERR_UNSUPPORTED, "fused residual: one row only (M=%d; the four-row forms are not built); %s", M, kInstead);
+  if (decide_swiglu(w, 1, QLLM_ACT_SILU, plan))
+    return set_error(QLLM_ERR_UNSUPPORTED, "fused residual: calls of the batch-1 kernel on native-layout layers only -- 4 bits with 128- / 64-wide groups and 3 bits, "
+                     "K within its shape table, QLLM_STRIP1 on (bits=%d g=%d K=%d layout=%d); %s", w->bits, w->group_size, w->K, w->layout, kInstead);
+  return QLLM_OK;
+}
+
 // The fused RMSNorm in front of a sibling group (strip1_norm.hip): exactly the M = 1 calls decide_single / decide_group put on the batch-1
 // kernel for native-layout layers, with the same waves x round, so that the fused launch is the plain grouped launch's arithmetic on
 // RMSNorm(x).  Everything else keeps qllm_rmsnorm and today's launch.

@@ -99,6 +99,7 @@ Decision decide_group(const qllm_weight_t *w, int n, int M, int act_dtype);    /
 // qllm_linear_forward_swiglu (no route: an own entry): QLLM_OK and the batch-1 kernel's plan of the plain call -- what strip_plan(w, 1, M)
 // serves with one_nw != 0 -- or QLLM_ERR_UNSUPPORTED with the refusal text set.  `act`: QLLM_ACT_SILU only.
 int decide_swiglu(const qllm_weight_t *w, int M, int act, StripPlan *plan);
+int decide_residual(const qllm_weight_t *w, int M, StripPlan *plan);   // (one row of what decide_swiglu serves)
 // qllm_linear_forward_rmsnorm (an own entry too): QLLM_OK and the plain call's Decision where decide_single / decide_group put n validated
 // native-layout layers at M = 1 on the batch-1 kernel (d->strip.one_nw != 0), or QLLM_ERR_UNSUPPORTED with the refusal text set.
 int decide_rmsnorm(const qllm_weight_t *w, int n, int M, Decision *d);

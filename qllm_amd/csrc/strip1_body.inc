@@ -1,11 +1,13 @@
-// The body of strip1_kernel, strip1_swiglu_kernel and strip1_norm_kernel (strip1_kernel.hpp, which documents it): included inside all
-// three, with NW, MAXS, EXACT, NCH, LVL, DBG, AR, G64, MR, B3, SWIGLU, NORM and NORM_PARK constants of the enclosing function and `p` its Strip1Params.
+// The body of strip1_kernel, strip1_swiglu_kernel, strip1_norm_kernel and the two RESID kernels (strip1_kernel.hpp, which documents it):
+// included inside all five, with NW, MAXS, EXACT, NCH, LVL, DBG, AR, G64, MR, B3, SWIGLU, NORM, NORM_PARK and RESID constants of the
+// enclosing function and `p` its Strip1Params.
   static_assert(MAXS % 4 == 0 && MAXS >= 8 && MAXS <= 64, "rounds are whole 128-wide groups, at most 16 of them (round 6: 40 .. 64 k-steps for K up to 32768)");
   static_assert(!(G64 && AR), "the fused all-reduce form is built for 128-wide groups");
   static_assert(MR == 1 || (MR == 4 && !G64 && !AR && !DBG && LVL == 4), "four batch rows: 128-wide groups, the plain form");
   static_assert(!B3 || (MR == 1 && !AR && !DBG && LVL == 4), "3 bits: the plain batch-1 form");
   static_assert(!SWIGLU || (!AR && !DBG && LVL == 4), "act(gate) * up: the plain forms");
   static_assert(!NORM || (!SWIGLU && MR == 1 && !AR && !DBG && LVL == 4), "RMSNorm(x): the plain batch-1 forms");
+  static_assert(!RESID || (!NORM && MR == 1 && !AR && !DBG && LVL == 4), "residual + y: the plain and the SWIGLU batch-1 forms");
   constexpr int KPG = G64 ? 2 : 4;        // k-steps per group
   constexpr int NG = MAXS / KPG;          // groups per wave
   constexpr int NPASS = (MAXS + 15) / 16; // accumulator sets: one per 16 k-steps (four 128-wide groups / eight 64-wide ones)
@@ -25,6 +27,7 @@
                "s"(p.T), "s"(p.n_groups), "s"(p.add_zero_bias), "s"(p.act_bf16));
   if constexpr (SWIGLU) asm volatile("" ::"s"(p.x2));  // (the up vector's base: the same batch)
   if constexpr (NORM) asm volatile("" ::"s"(p.norm_w), "s"(p.norm_eps), "s"(p.rstd_out));  // (the norm's weight, epsilon, report slot)
+  if constexpr (RESID) asm volatile("" ::"s"(p.residual));  // (the residual row's base: the same batch)
   // the two flags the uniform branches and the tail read: taken from the first batch of scalar loads (as outputs of an asm they cannot
   // be re-loaded next to their use -- hipcc otherwise sinks a second s_load of each into the decode branch and in front of the y store)
   int add_zero_bias = p.add_zero_bias, act_bf16 = p.act_bf16;
@@ -44,6 +47,15 @@
   const int t0 = wave * MAXS;                              // the wave owns k-steps [t0, min(t0 + MAXS, T))
   const int tb = EXACT ? t0 : min(t0, T - MAXS);           // its window [tb, tb + MAXS): shifted back into the strip at the end of K
   // ---- every load of the wave, back to back: x chunk(s), one scale + one zero word per pass, MAXS weight words -----------------
+  // RESID: the residual of output column 16 b + i, first of the batch (loads return in order: it has arrived before the activations).
+  // Every lane issues it -- no branch in the prologue, N = 16 n_strips keeps it inside the row -- and holds it in ONE register until the
+  // epilogue, where lanes 0..15 of wave 0 use theirs: no round trip behind the cross-wave sum.
+  // RESID_LATE (the SWIGLU forms that sit AT their register bound with the up chunks live across the load batch -- rounds of 24 at 64
+  // registers, rounds of 56 / 64 at 128: one more register there is scratch): the load is issued behind the last MFMA instead, where the
+  // weight words are dead, and returns under the per-group corrections, the LDS pass and the barrier -- still not behind the sum
+  constexpr bool RESID_LATE = RESID && SWIGLU && (MAXS >= 56 || (MAXS == 24 && !G64 && !B3));
+  uint32_t resid = 0;
+  if constexpr (RESID && !RESID_LATE) resid = ((const uint16_t *)p.residual)[b * 16 + i];
   uint4_t xa[MR][XL];
   uint4_t xb[SWIGLU ? MR : 1][(SWIGLU || NORM) ? XL : 1];   // (SWIGLU: the up vector's chunks; NORM: the norm weight's)
   bool xkeep[XL];
@@ -389,6 +401,7 @@
     if (dbg_slot && lane == 0) dbg_slot[3] = __builtin_amdgcn_s_memrealtime();
   }
 
+  if constexpr (RESID_LATE) resid = ((const uint16_t *)p.residual)[b * 16 + i];
   // ---- the lane's value: its group's partial of column i; then one pass over [column][wave][g] -------------------------------------
   float val[MR];
   if constexpr (LVL >= 3) {
@@ -420,6 +433,8 @@
   } else {
     val[0] = __builtin_bit_cast(float, fold);
   }
+  // (the early load stays up there, not behind the barrier; every weight word is long consumed: no wait.  The late one is waited for where it is used)
+  if constexpr (RESID && !RESID_LATE) asm volatile("" : "+v"(resid));
 #pragma unroll
   for (int m = 0; m < MR; ++m) lds[(m * 16 + i) * RS + wave * 4 + g] = val[m];
   __syncthreads();
@@ -448,7 +463,18 @@
     const int n = b * 16 + (threadIdx.x & 15), mrow = threadIdx.x >> 4;
     if (pr.bias) v += (float)pr.bias[n];
     vfin = v;
-    if constexpr (!AR) {
+    if constexpr (RESID) {
+      // y = residual + linear(..) as the eager add of two tensors rounds it: the launch's own output rounded to the activation type (the
+      // value the plain form stores), the sum in fp32, rounded again.  y may BE the residual row: this thread alone reads element n, and
+      // it read it in the prologue
+      if (act_bf16) {
+        const float h = __builtin_bit_cast(float, (uint32_t)f32_to_bf16(v) << 16);
+        ((uint16_t *)pr.y)[n] = f32_to_bf16(h + __builtin_bit_cast(float, resid << 16));
+      } else {
+        const half_t h = (half_t)v;
+        ((half_t *)pr.y)[n] = (half_t)((float)h + (float)__builtin_bit_cast(half_t, (uint16_t)resid));
+      }
+    } else if constexpr (!AR) {
       if (MR == 1 || mrow < p.M) {
         const size_t at = (size_t)mrow * pr.n_strips * 16 + n;   // (y is [M][N], N = 16 n_strips)
         if (act_bf16) ((uint16_t *)pr.y)[at] = f32_to_bf16(v);

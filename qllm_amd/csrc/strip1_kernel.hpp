@@ -161,10 +161,19 @@ constexpr int kStrip1NormLdsBytes = 64;
 //     weight * round(x * rstd) (norm_pair: the two roundings of the eager expression, in the activation type, before the bf16 -> fp16
 //     conversion), and from there on the kernel is the plain form's code: a NORM launch returns bit for bit what the plain grouped launch
 //     returns on xn = weight * (x.float() * rstd).to(dtype).  Kernels of their own (strip1_norm_kernel below, strip1_norm.hip), as for SWIGLU.
+// RESID: y = residual + linear(..) in the launch (p.residual: one row [N] in the activation type): the 16 threads that store the block's
+//     outputs round their value to the activation type as the plain form does, add their element of the residual in fp32 and round
+//     again -- the eager `residual + linear(x)`, rounding for rounding, so a RESID launch returns bit for bit what the plain (SWIGLU)
+//     launch followed by torch's add returns.  The element is loaded with the prologue's loads and waits in one register -- except in
+//     the ten SWIGLU forms at their register bound (RESID_LATE, strip1_body.inc: plain rounds of 24, rounds of 56 and 64), which load it
+//     behind their last MFMA.  Batch 1 only,
+//     no AR; kernels of their own around the same body (strip1_resid_kernel, strip1_swiglu_resid_kernel below; strip1_resid.hip,
+//     strip1_swiglu_resid.hip), as for SWIGLU.  y may be the residual row itself: element n is read and written by the same thread.
 template <int NW, int MAXS, bool EXACT, int NCH = 2, int LVL = 4, bool DBG = false, bool AR = false, bool G64 = false, int MR = 1, bool B3 = false>
 // (second launch bound = minimum waves per SIMD: 64 registers up to rounds of 24 k-steps -- a CU full of waves -- 128 above)
 __global__ __launch_bounds__(NW * 64, (MAXS <= 24 && !G64 && MR == 1 && !B3) ? 8 : 4) void strip1_kernel(const Strip1Params p) {
   constexpr bool SWIGLU = false, NORM = false, NORM_PARK = false;
+  constexpr bool RESID = false;
 #include "strip1_body.inc"
 }
 
@@ -172,6 +181,7 @@ __global__ __launch_bounds__(NW * 64, (MAXS <= 24 && !G64 && MR == 1 && !B3) ? 8
 template <int NW, int MAXS, bool EXACT, bool G64, int MR, bool B3, int WAVES>
 __global__ __launch_bounds__(NW * 64, WAVES) void strip1_swiglu_kernel(const Strip1Params p) {
   constexpr bool SWIGLU = true, NORM = false, NORM_PARK = false, DBG = false, AR = false;
+  constexpr bool RESID = false;
   constexpr int NCH = 2, LVL = 4;
 #include "strip1_body.inc"
 }
@@ -180,8 +190,26 @@ __global__ __launch_bounds__(NW * 64, WAVES) void strip1_swiglu_kernel(const Str
 template <int NW, int MAXS, bool EXACT, bool G64, int MR, bool B3, int WAVES>
 __global__ __launch_bounds__(NW * 64, WAVES) void strip1_norm_kernel(const Strip1Params p) {
   constexpr bool SWIGLU = false, NORM = true, DBG = false, AR = false;
+  constexpr bool RESID = false;
   constexpr bool NORM_PARK = MAXS >= 64 || (MAXS == 24 && !G64 && !B3);   // (the forms whose twins sit next to their register bound)
   constexpr int NCH = 2, LVL = 4;
+#include "strip1_body.inc"
+}
+
+// the RESID forms: the plain input (strip1_resid.hip) and act(gate) * up (strip1_swiglu_resid.hip); WAVES as above, the twin form's
+template <int NW, int MAXS, bool EXACT, bool G64, bool B3, int WAVES>
+__global__ __launch_bounds__(NW * 64, WAVES) void strip1_resid_kernel(const Strip1Params p) {
+  constexpr bool SWIGLU = false, NORM = false, NORM_PARK = false, DBG = false, AR = false;
+  constexpr bool RESID = true;
+  constexpr int NCH = 2, LVL = 4, MR = 1;
+#include "strip1_body.inc"
+}
+
+template <int NW, int MAXS, bool EXACT, bool G64, bool B3, int WAVES>
+__global__ __launch_bounds__(NW * 64, WAVES) void strip1_swiglu_resid_kernel(const Strip1Params p) {
+  constexpr bool SWIGLU = true, NORM = false, NORM_PARK = false, DBG = false, AR = false;
+  constexpr bool RESID = true;
+  constexpr int NCH = 2, LVL = 4, MR = 1;
 #include "strip1_body.inc"
 }
 

@@ -6,3 +6,4 @@ from .quant_linear_onnxruntime import QuantLinearORT  # noqa: F401
 from .fused import SiblingGroup, fuse_siblings, install_sibling_groups  # noqa: F401
 from .fused_mlp import install_fused_mlp, uninstall_fused_mlp  # noqa: F401
 from .fused_norm import install_fused_norm, make_quant_norm, uninstall_fused_norm  # noqa: F401
+from .fused_residual import install_fused_residual, uninstall_fused_residual  # noqa: F401

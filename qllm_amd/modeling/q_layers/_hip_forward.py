@@ -43,8 +43,15 @@ def bitgroup_serves(bits: int, n_layers: int, act_order: bool, rows: int) -> boo
     return bits in (2, 5, 6, 7, 8) and n_layers <= 4 and not act_order and 1 <= rows <= ops.bitgroup_max_m()
 
 
+def _fused_tensors_ok(*tensors) -> bool:
+    """What the fused residual entries ask of the tensors of one call: device tensors of one activation type, nothing to differentiate."""
+    t0 = tensors[0]
+    return (t0.dtype in (torch.float16, torch.bfloat16) and all(t.is_cuda and t.dtype == t0.dtype and t.device == t0.device for t in tensors)
+            and not (torch.is_grad_enabled() and any(t.requires_grad for t in tensors)))
+
+
 # derived, pointer-holding state (ctypes descriptors, shadows, sibling groups): rebuilt on demand, never copied or pickled
-_DERIVED = ("_desc", "_desc_key", "_desc_keep", "_native", "_native_key", "_ao", "_ao_key", "_ao_panel_refused", "_ao_gemm_refused", "_perm", "_swiglu_refused_from", "_siblings")
+_DERIVED = ("_desc", "_desc_key", "_desc_keep", "_native", "_native_key", "_ao", "_ao_key", "_ao_panel_refused", "_ao_gemm_refused", "_perm", "_swiglu_refused_from", "_residual_refused", "_swiglu_residual_refused", "_siblings")
 # (a released module is materialised before it is pickled / deep-copied: see __getstate__)
 
 
@@ -262,6 +269,54 @@ class HipForwardMixin:
                 except ops.QllmUnsupported:
                     self._swiglu_refused_from = m
         return self(torch.nn.functional.silu(gate) * up)
+
+    # the fused residual entries refused this layer once (they serve one row of it or nothing): not asked again until `_invalidate()`
+    _residual_refused = False
+    _swiglu_residual_refused = False
+    # the most rows forward_residual / forward_swiglu_residual send to the fused entry (it serves one); 0: never.  Measured:
+    # profiles/residual.md; QLLM_FUSE_RESIDUAL_MAX_M moves it
+    residual_max_m = int(os.environ.get("QLLM_FUSE_RESIDUAL_MAX_M", "1"))
+
+    def _residual_descriptor(self, inputs, residual: torch.Tensor, refused: bool):
+        """The native descriptor for a fused residual call on `inputs` ([..., K] each) and `residual` ([..., N]), or None: the call is not
+        one the modules send to the entry -- more rows than `residual_max_m`, a remembered refusal, shapes / dtypes that disagree,
+        non-contiguous tensors, CPU tensors, grad mode, an act-order layer, no native copy."""
+        x = inputs[0]
+        m = x.numel() // x.shape[-1] if x.shape[-1] else 0
+        resolve = getattr(self, "_resolve_act_order", None)   # (GPTQ detects act-order lazily: do it before branching on it)
+        if resolve is not None:
+            resolve()
+        if (refused or not 1 <= m <= self.residual_max_m or any(t.shape != x.shape for t in inputs)
+                or residual.shape != x.shape[:-1] + (self.outfeatures,) or not _fused_tensors_ok(*inputs, residual)
+                or not all(t.reshape(-1, t.shape[-1]).is_contiguous() for t in (*inputs, residual)) or getattr(self, "act_order", None)):
+            return None
+        return self.native_descriptor(autogptq_compat() if self._layout_name() == "GPTQ" else 0)
+
+    def forward_residual(self, x: torch.Tensor, residual: torch.Tensor) -> torch.Tensor:
+        """residual + forward(x) -- the o_proj (or down_proj) of a decoder layer with its residual add.  Where the batch-1 kernel serves
+        the call on the layer's native copy, ONE launch adds the residual as it stores its output (ops.linear_forward_residual,
+        csrc/strip1_resid.hip), bit for bit the eager add; everything else (`_residual_descriptor`; a refusal is remembered) is the
+        layer's own forward and the elementwise add.  Never writes into `residual`."""
+        w = self._residual_descriptor((x,), residual, self._residual_refused)
+        if w is not None:
+            try:
+                return ops.linear_forward_residual(w, x.reshape(-1, x.shape[-1]), residual.reshape(-1, self.outfeatures)).reshape(residual.shape)
+            except ops.QllmUnsupported:
+                self._residual_refused = True
+        return residual + self(x)
+
+    def forward_swiglu_residual(self, gate: torch.Tensor, up: torch.Tensor, residual: torch.Tensor) -> torch.Tensor:
+        """residual + forward_swiglu(gate, up) -- the down_proj of a SwiGLU MLP with neither elementwise kernel around it
+        (ops.linear_forward_swiglu_residual, csrc/strip1_swiglu_resid.hip), under the rules of `forward_residual`; everything else is
+        `forward_swiglu` and the elementwise add."""
+        w = self._residual_descriptor((gate, up), residual, self._swiglu_residual_refused) if gate.shape == up.shape else None
+        if w is not None:
+            try:
+                return ops.linear_forward_swiglu_residual(w, gate.reshape(-1, gate.shape[-1]), up.reshape(-1, up.shape[-1]),
+                                                          residual.reshape(-1, self.outfeatures)).reshape(residual.shape)
+            except ops.QllmUnsupported:
+                self._swiglu_residual_refused = True
+        return residual + self.forward_swiglu(gate, up)
 
     def _hip_linear(self, x: torch.Tensor, act_order_g_idx=None, add_zero_bias: int = 0) -> torch.Tensor:
         if not x.is_cuda or not self.qweight.is_cuda:

@@ -385,6 +385,49 @@ def swiglu_describe(w: QllmWeight, m: int) -> str:
     return _describe("qllm_swiglu_describe", 640, C.byref(w), int(m))
 
 
+def _check_residual(residual2d: torch.Tensor, w: QllmWeight, x2d: torch.Tensor):
+    _check_input(residual2d, "residual")
+    if tuple(residual2d.shape) != (x2d.shape[0], w.N) or residual2d.dtype != x2d.dtype or residual2d.device != x2d.device:
+        raise RuntimeError(f"residual must be a [{x2d.shape[0]}, {w.N}] {x2d.dtype} tensor on {x2d.device}, got {tuple(residual2d.shape)} "
+                           f"{residual2d.dtype} on {residual2d.device}")
+
+
+def linear_forward_residual(w: QllmWeight, x2d: torch.Tensor, residual2d: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y[1,N] = residual2d + x2d[1,K] . dequant(w) (+bias) in ONE launch (qllm_linear_forward_residual, csrc/strip1_resid.hip): the o_proj
+    of a decoder layer with the residual add formed by the threads that store the output.  Bit-identical to
+    `residual2d + linear_forward(w, x2d)`.  `out` may be residual2d itself.  One row; raises QllmUnsupported for every call the batch-1
+    kernel does not serve (callers then run `linear_forward` and add)."""
+    _check_x(x2d, (w,))
+    _check_residual(residual2d, w, x2d)
+    lib = _lib.load()
+    return _forward((w,), x2d, out, None,
+                    lambda wr, y, x, m, dt, ws: lib.qllm_linear_forward_residual(wr, x.data_ptr(), None, residual2d.data_ptr(), y, m, dt, _lib.ACT_SILU,
+                                                                                 _stream_ptr()))
+
+
+def linear_forward_swiglu_residual(w: QllmWeight, gate2d: torch.Tensor, up2d: torch.Tensor, residual2d: torch.Tensor,
+                                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y[1,N] = residual2d + (silu(gate2d) * up2d)[1,K] . dequant(w) (+bias) in ONE launch (qllm_linear_forward_residual with `up`,
+    csrc/strip1_swiglu_resid.hip): the down_proj of a SwiGLU MLP with neither elementwise kernel around it.  Bit-identical to
+    `residual2d + linear_forward_swiglu(w, gate2d, up2d)`.  `out` may be residual2d itself.  One row; raises QllmUnsupported for every
+    call the batch-1 kernel does not serve."""
+    _check_x(gate2d, (w,))
+    _check_input(up2d, "up")
+    if up2d.shape != gate2d.shape or up2d.dtype != gate2d.dtype or up2d.device != gate2d.device:
+        raise RuntimeError(f"up must match gate: {tuple(gate2d.shape)} {gate2d.dtype} on {gate2d.device}, got {tuple(up2d.shape)} {up2d.dtype} on {up2d.device}")
+    _check_residual(residual2d, w, gate2d)
+    lib = _lib.load()
+    return _forward((w,), gate2d, out, None,
+                    lambda wr, y, gate, m, dt, ws: lib.qllm_linear_forward_residual(wr, gate.data_ptr(), up2d.data_ptr(), residual2d.data_ptr(), y, m, dt,
+                                                                                    _lib.ACT_SILU, _stream_ptr()))
+
+
+def residual_describe(w: QllmWeight, m: int, swiglu: bool = False) -> str:
+    """What `linear_forward_residual` (swiglu: `linear_forward_swiglu_residual`) would launch for m rows: "residual " / "residual swiglu "
+    + the plan line of the plain call, or "refused: ..." with the entry's refusal text.  Pure host code."""
+    return _describe("qllm_residual_describe", 640, C.byref(w), int(m), 1 if swiglu else 0)
+
+
 def _rstd_buffer(return_rstd, m: int, x2d: torch.Tensor):
     """return_rstd of the two RMSNorm wrappers: False (None), True (a new fp32 [m] tensor) or the caller's contiguous fp32 [m] tensor."""
     if return_rstd is False or return_rstd is None:
@@ -776,6 +819,6 @@ def unpack_native(w: QllmWeight, keep, layout: str):
     return qweight, scales, qzeros
 
 
-__all__ = ["make_weight", "linear_forward", "linear_forward_grouped", "linear_forward_permuted", "linear_forward_bitpanel", "bitpanel_describe", "linear_forward_bitgemm", "bitgemm_describe", "bitgemm_min_m", "linear_forward_bitgroup", "bitgroup_describe", "linear_forward_swiglu", "swiglu_describe", "rmsnorm", "linear_forward_rmsnorm", "rmsnorm_describe", "linear_forward_shared", "dequant", "gather_columns", "unpack_qweight", "pack_qweight",
+__all__ = ["make_weight", "linear_forward", "linear_forward_grouped", "linear_forward_permuted", "linear_forward_bitpanel", "bitpanel_describe", "linear_forward_bitgemm", "bitgemm_describe", "bitgemm_min_m", "linear_forward_bitgroup", "bitgroup_describe", "linear_forward_swiglu", "swiglu_describe", "linear_forward_residual", "linear_forward_swiglu_residual", "residual_describe", "rmsnorm", "linear_forward_rmsnorm", "rmsnorm_describe", "linear_forward_shared", "dequant", "gather_columns", "unpack_qweight", "pack_qweight",
            "workspace", "QllmUnsupported", "LAYOUTS", "plan_describe", "repack_native", "unpack_native", "hqq_quantize", "gptq_quantize",
            "gptq_quantize_static", "awq_quantize", "awq_clip_search"]
