@@ -6,6 +6,9 @@
 // does not know them) each keep ONE *_check / decide_* that their forward, *_workspace_bytes and *_describe entries all ask.  What those
 // entries do around it is written once: check_layer_count + check_layers (an array of layers), check_describe_args, describe_refusal
 // (a refusal as text), counters_and_slabs (a workspace size) and fill_bit_params (the bit family's parameter blocks).
+// The six launches of the batch-1 kernel (launch_strip1 / _allreduce / _swiglu / _norm / _resid / _swiglu_resid) fill one Strip1Params
+// here and share ONE form table and launch site, strip1_forms.hpp: a further fused family is the struct that header describes plus its
+// entry here -- no pair table and no launch of its own.
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>

@@ -8,6 +8,7 @@
 #include <algorithm>
 
 #include "planner.hpp"
+#include "strip1_forms.hpp"
 
 namespace qllm {
 
@@ -241,12 +242,12 @@ static bool take(StripPlan *plan, int cpl, int nw, int spw, int ra, int sm) {
   return true;
 }
 
-// Round 6: batches 2..4 on the batch-1 kernel's four-row forms (128-wide groups, K <= 16384): the A rows that carry four copies of x
+// Round 6: batches 2..4 on the batch-1 kernel's four-row forms (128-wide groups, as far as their rounds go): the A rows that carry four copies of x
 // at batch 1 carry four batch rows -- the weight stream and the MFMAs of a batch-1 launch.  QLLM_STRIP1_MAX_M = 1 keeps them on strip_dma.
 static bool plan_strip1_rows4(const qllm_weight_t *w, int M, int strips, StripPlan *plan) {
-  if (!(M >= 2 && M <= 4 && M <= knob("QLLM_STRIP1_MAX_M", 4) && w[0].bits == 4 && w[0].group_size == 128 && w[0].K <= 16384 && knob("QLLM_STRIP1", 1))) return false;
+  if (!(M >= 2 && M <= 4 && M <= knob("QLLM_STRIP1_MAX_M", 4) && w[0].bits == 4 && w[0].group_size == 128 && knob("QLLM_STRIP1", 1))) return false;
   int nw1 = 0, maxs1 = 0;
-  if (!strip1_shape(w[0].K, strips, compute_units(), &nw1, &maxs1) || maxs1 > 32) return false;
+  if (!strip1_shape(w[0].K, strips, compute_units(), &nw1, &maxs1) || maxs1 > strip1_max_round(false, 4, false)) return false;
   plan->one_nw = nw1;
   plan->one_maxs = maxs1;
   return take(plan, 1, nw1, maxs1, 0, 1);
@@ -312,11 +313,13 @@ static void upgrade_to_strip1(const qllm_weight_t &w, int M, int strips, StripPl
   int nw1 = 0, maxs1 = 0;
   // (round 6: 64-wide groups too -- HQQ's default; QLLM_STRIP1 = 2 keeps them on the general kernel)
   const int s1 = knob("QLLM_STRIP1", 1);
-  // (round 6: 3-bit layers too -- batch 1, K <= 16384; QLLM_STRIP1_3BIT = 0 keeps them on the general kernel)
-  const bool w4 = w.bits == 4 && (w.group_size == 128 || (w.group_size == 64 && s1 != 2 && w.K <= 24576));
-  const bool w3 = w.bits == 3 && (w.group_size == 128 || w.group_size == 64) && w.K <= 16384 && knob("QLLM_STRIP1_3BIT", 1);
+  // (round 6: 3-bit layers too -- batch 1; QLLM_STRIP1_3BIT = 0 keeps them on the general kernel)
+  const bool w4 = w.bits == 4 && (w.group_size == 128 || (w.group_size == 64 && s1 != 2));
+  const bool w3 = w.bits == 3 && (w.group_size == 128 || w.group_size == 64) && knob("QLLM_STRIP1_3BIT", 1);
   // (round 7: K % 128 == 64 -- Falcon-7B's 4544 -- on the 4-bit 64-wide-group forms: strip1_shape)
-  if (M == 1 && (w4 || w3) && s1 && strip1_shape(w.K, strips, compute_units(), &nw1, &maxs1, w4 && w.group_size == 64)) {
+  // (as far as the form's rounds go, strip1_forms.hpp: 3 bits K <= 16384, 64-wide groups K <= 24576)
+  if (M == 1 && (w4 || w3) && s1 && strip1_shape(w.K, strips, compute_units(), &nw1, &maxs1, w4 && w.group_size == 64) &&
+      maxs1 <= strip1_max_round(w.group_size == 64, 1, w.bits == 3)) {
     plan->one_nw = nw1;
     plan->one_maxs = maxs1;
   }

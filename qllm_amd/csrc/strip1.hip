@@ -1,4 +1,6 @@
-// Host side of the batch-1 native-layout decode kernel (strip1_kernel.hpp): the shape table and the instantiations.
+// Host side of the batch-1 native-layout decode kernel (strip1_kernel.hpp): the shape table, and the plain, the fused all-reduce and the
+// diagnostics families of strip1_forms.hpp's form table -- which says what a family is and picks and launches the instantiation.
+#include "strip1_forms.hpp"
 #include "strip1_kernel.hpp"
 
 namespace qllm {
@@ -41,92 +43,28 @@ bool strip1_shape(int K, int blocks, int cus, int *nw, int *maxs, bool odd64) {
   return true;
 }
 
-template <int NW, int MAXS, bool EXACT, bool DBG, bool G64 = false, int MR = 1, bool B3 = false>
-static int launch_t(const Strip1Params &p, dim3 grid, hipStream_t stream) {
-  constexpr int lds_bytes = strip1_lds_bytes<NW, MAXS, MR>();
-  static_assert(lds_bytes <= 160 * 1024, "LDS of one CU");
-  if constexpr (lds_bytes > 64 * 1024) {  // (rounds of 56 / 64 k-steps x 16 waves, or four batch rows: the staged activations)
-    static DeviceLatch attr_done;
-    if (int rc = lds_optin(attr_done, (const void *)strip1_kernel<NW, MAXS, EXACT, 2, 4, DBG, false, G64, MR, B3>)) return rc;
-  }
-  hipLaunchKernelGGL((strip1_kernel<NW, MAXS, EXACT, 2, 4, DBG, false, G64, MR, B3>), grid, dim3(NW * 64), lds_bytes, stream, p);
-  QLLM_HIP_CHECK(hipGetLastError());
-  return QLLM_OK;
-}
+// <NCH = 2, LVL = 4, DBG, AR>: the plain forms; the diagnostics forms (timeline stamps); the row-parallel layer fused with its one-shot
+// all-reduce -- the forms of the Llama-class row-parallel shards (K / world per rank up to 16384: Llama-2-70B's down_proj at TP = 2)
+template <bool DBG, bool AR>
+struct Strip1Family {
+  static constexpr const char *kWhat = AR ? "fused all-reduce" : "internal";
+  static constexpr int kLdsExtra = 0, kMaxRound = AR ? 32 : 64;
+  static constexpr bool kRows4 = !AR, kG64B3 = !AR;
+  template <int NW, int MAXS, bool EXACT, bool G64, int MR, bool B3>
+  static Strip1Kernel kernel() { return strip1_kernel<NW, MAXS, EXACT, 2, 4, DBG, AR, G64, MR, B3>; }
+};
 
-template <int NW, int MAXS>
-static int launch_e(const Strip1Params &p, dim3 grid, hipStream_t stream) {
-  if (p.bits3) {  // 3-bit layers (round 6): batch 1, 64- and 128-wide groups, rounds of up to 32 k-steps (two word loads per k-step)
-    if constexpr (MAXS <= 32) {
-      if (p.group64)
-        return (NW * MAXS == p.T) ? launch_t<NW, MAXS, true, false, true, 1, true>(p, grid, stream) : launch_t<NW, MAXS, false, false, true, 1, true>(p, grid, stream);
-      return (NW * MAXS == p.T) ? launch_t<NW, MAXS, true, false, false, 1, true>(p, grid, stream) : launch_t<NW, MAXS, false, false, false, 1, true>(p, grid, stream);
-    } else {
-      return set_error(QLLM_ERR_UNSUPPORTED, "internal: 3-bit layers on the batch-1 kernel stop at K = 16384");
-    }
-  }
-  if (p.M > 1) {  // batches 2..4 (round 6): the four-row forms, 128-wide groups, rounds of up to 32 k-steps (LDS: four staged rows per wave)
-    if constexpr (MAXS <= 32)
-      return (NW * MAXS == p.T) ? launch_t<NW, MAXS, true, false, false, 4>(p, grid, stream) : launch_t<NW, MAXS, false, false, false, 4>(p, grid, stream);
-    else
-      return set_error(QLLM_ERR_UNSUPPORTED, "internal: four batch rows on the batch-1 kernel stop at K = 16384");
-  }
-  if (p.group64) {  // 64-wide groups (round 6); rounds of up to 48 k-steps (56 spills a register with sixteen group addresses more)
-    if constexpr (MAXS <= 48)
-      return (NW * MAXS == p.T) ? launch_t<NW, MAXS, true, false, true>(p, grid, stream) : launch_t<NW, MAXS, false, false, true>(p, grid, stream);
-    else
-      return set_error(QLLM_ERR_UNSUPPORTED, "internal: 64-wide groups on the batch-1 kernel stop at K = 24576");
-  }
-  return (NW * MAXS == p.T) ? launch_t<NW, MAXS, true, false>(p, grid, stream) : launch_t<NW, MAXS, false, false>(p, grid, stream);
-}
-
-template <int NW, int MAXS>
-static int launch_ar(const Strip1Params &p, int n_strips, hipStream_t stream) {
-  constexpr int lds_bytes = strip1_lds_bytes<NW, MAXS>();
-  if (NW * MAXS == p.T) hipLaunchKernelGGL((strip1_kernel<NW, MAXS, true, 2, 4, false, true>), dim3(n_strips, 1), dim3(NW * 64), lds_bytes, stream, p);
-  else hipLaunchKernelGGL((strip1_kernel<NW, MAXS, false, 2, 4, false, true>), dim3(n_strips, 1), dim3(NW * 64), lds_bytes, stream, p);
-  QLLM_HIP_CHECK(hipGetLastError());
-  return QLLM_OK;
-}
-
-// the row-parallel layer fused with its one-shot all-reduce: the forms of the Llama-class row-parallel shards (K / world per rank)
 int launch_strip1_allreduce(const Strip1Params &p, int nw, int maxs, int n_strips, hipStream_t stream) {
-  if (nw == 4 && maxs == 8) return launch_ar<4, 8>(p, n_strips, stream);
-  if (nw == 4 && maxs == 16) return launch_ar<4, 16>(p, n_strips, stream);
-  if (nw == 4 && maxs == 32) return launch_ar<4, 32>(p, n_strips, stream);
-  if (nw == 8 && maxs == 16) return launch_ar<8, 16>(p, n_strips, stream);
-  if (nw == 7 && maxs == 16) return launch_ar<7, 16>(p, n_strips, stream);
-  if (nw == 8 && maxs == 24) return launch_ar<8, 24>(p, n_strips, stream);
-  if (nw == 8 && maxs == 32) return launch_ar<8, 32>(p, n_strips, stream);
-  if (nw == 16 && maxs == 16) return launch_ar<16, 16>(p, n_strips, stream);
-  if (nw == 16 && maxs == 24) return launch_ar<16, 24>(p, n_strips, stream);
-  if (nw == 15 && maxs == 24) return launch_ar<15, 24>(p, n_strips, stream);
-  if (nw == 16 && maxs == 32) return launch_ar<16, 32>(p, n_strips, stream);   // K per rank up to 16384 (Llama-2-70B down_proj at TP = 2)
-  return set_error(QLLM_ERR_UNSUPPORTED, "fused all-reduce: no batch-1 instantiation for nw=%d round=%d", nw, maxs);
+  return strip1_launch<Strip1Family<false, true>>(p, nw, maxs, dim3(n_strips, 1), stream);
 }
 
 int launch_strip1(const Strip1Params &p, int nw, int maxs, int n_prob, int max_strips, hipStream_t stream) {
   const dim3 grid(max_strips, n_prob);
-  if (p.dbg && !p.group64 && p.M == 1 && !p.bits3) {  // diagnostics instantiations (timeline stamps): the two Llama-2-7B forms
-    if (nw == 8 && maxs == 16 && p.T == 128) return launch_t<8, 16, true, true>(p, grid, stream);
-    if (nw == 15 && maxs == 24 && p.T < 360) return launch_t<15, 24, false, true>(p, grid, stream);
+  if (p.dbg && !p.group64 && p.M == 1 && !p.bits3) {  // the two diagnostics instantiations: Llama-2-7B's forms
+    if (nw == 8 && maxs == 16 && p.T == 128) return strip1_enqueue(strip1_form<Strip1Family<true, false>, 8, 16, true, false, 1, false>(), p, grid, nw, stream);
+    if (nw == 15 && maxs == 24 && p.T < 360) return strip1_enqueue(strip1_form<Strip1Family<true, false>, 15, 24, false, false, 1, false>(), p, grid, nw, stream);
   }
-  if (nw == 4 && maxs == 8) return launch_e<4, 8>(p, grid, stream);
-  if (nw == 4 && maxs == 16) return launch_e<4, 16>(p, grid, stream);
-  if (nw == 4 && maxs == 32) return launch_e<4, 32>(p, grid, stream);
-  if (nw == 8 && maxs == 16) return launch_e<8, 16>(p, grid, stream);
-  if (nw == 7 && maxs == 16) return launch_e<7, 16>(p, grid, stream);
-  if (nw == 8 && maxs == 24) return launch_e<8, 24>(p, grid, stream);
-  if (nw == 8 && maxs == 32) return launch_e<8, 32>(p, grid, stream);
-  if (nw == 16 && maxs == 16) return launch_e<16, 16>(p, grid, stream);
-  if (nw == 16 && maxs == 24) return launch_e<16, 24>(p, grid, stream);
-  if (nw == 15 && maxs == 24) return launch_e<15, 24>(p, grid, stream);
-  if (nw == 16 && maxs == 32) return launch_e<16, 32>(p, grid, stream);
-  if (nw == 16 && maxs == 40) return launch_e<16, 40>(p, grid, stream);
-  if (nw == 16 && maxs == 48) return launch_e<16, 48>(p, grid, stream);
-  if (nw == 16 && maxs == 56) return launch_e<16, 56>(p, grid, stream);
-  if (nw == 16 && maxs == 64) return launch_e<16, 64>(p, grid, stream);
-  return set_error(QLLM_ERR_UNSUPPORTED, "internal: no batch-1 instantiation for nw=%d round=%d", nw, maxs);
+  return strip1_launch<Strip1Family<false, false>>(p, nw, maxs, grid, stream);
 }
 
 }  // namespace qllm

@@ -33,7 +33,7 @@
 //
 // Replaces gemv<half> (/root/reference/csrc/ort_cuda/dq_gemv.cu:41-150).
 #pragma once
-#include "kernels.hpp"
+#include "strip1_forms.hpp"
 
 namespace qllm {
 
@@ -171,13 +171,13 @@ constexpr int kStrip1NormLdsBytes = 64;
 //     strip1_swiglu_resid.hip), as for SWIGLU.  y may be the residual row itself: element n is read and written by the same thread.
 template <int NW, int MAXS, bool EXACT, int NCH = 2, int LVL = 4, bool DBG = false, bool AR = false, bool G64 = false, int MR = 1, bool B3 = false>
 // (second launch bound = minimum waves per SIMD: 64 registers up to rounds of 24 k-steps -- a CU full of waves -- 128 above)
-__global__ __launch_bounds__(NW * 64, (MAXS <= 24 && !G64 && MR == 1 && !B3) ? 8 : 4) void strip1_kernel(const Strip1Params p) {
+__global__ __launch_bounds__(NW * 64, strip1_min_waves(MAXS, G64, MR, B3)) void strip1_kernel(const Strip1Params p) {
   constexpr bool SWIGLU = false, NORM = false, NORM_PARK = false;
   constexpr bool RESID = false;
 #include "strip1_body.inc"
 }
 
-// the SWIGLU forms (WAVES: the second launch bound, chosen per form from the compiler's report -- strip1_swiglu.hip)
+// the SWIGLU forms (strip1_swiglu.hip; WAVES: the second launch bound -- strip1_min_waves, the plain twin's)
 template <int NW, int MAXS, bool EXACT, bool G64, int MR, bool B3, int WAVES>
 __global__ __launch_bounds__(NW * 64, WAVES) void strip1_swiglu_kernel(const Strip1Params p) {
   constexpr bool SWIGLU = true, NORM = false, NORM_PARK = false, DBG = false, AR = false;

@@ -1,9 +1,24 @@
 // The RESID forms of the batch-1 native-layout decode kernel (strip1_kernel.hpp) around act(gate) * up: y = residual +
 // linear(w, silu(gate) * up) -- the down_proj launch of a SwiGLU MLP with neither the elementwise kernel in front of it nor the one behind.
-// One instantiation per batch-1 (MR = 1) form strip1.hip's launch_e builds without AR / DBG, with the same caps on the round length per
-// form (strip1_resid_forms.inc); strip1.hip, strip1_swiglu.hip and what they build are untouched.  qllm_linear_forward_residual (capi.hip) is the only caller.
+// One instantiation per batch-1 (MR = 1) form of the plain family (strip1.hip): the family below is all this unit adds to
+// strip1_forms.hpp's table.  The residual element is ONE more live register from the load batch to the epilogue.
+// qllm_linear_forward_residual (capi.hip) is the only caller.
+#include "strip1_forms.hpp"
 #include "strip1_kernel.hpp"
 
-#define QLLM_RESID_KERNEL strip1_swiglu_resid_kernel
-#define QLLM_RESID_LAUNCH launch_strip1_swiglu_resid
-#include "strip1_resid_forms.inc"
+namespace qllm {
+
+struct Strip1SwigluResid {
+  static constexpr const char *kWhat = "fused residual";
+  static constexpr int kLdsExtra = 0, kMaxRound = 64;
+  static constexpr bool kRows4 = false, kG64B3 = true;
+  template <int NW, int MAXS, bool EXACT, bool G64, int MR, bool B3>
+  static Strip1Kernel kernel() { return strip1_swiglu_resid_kernel<NW, MAXS, EXACT, G64, B3, strip1_min_waves(MAXS, G64, MR, B3)>; }
+};
+
+int launch_strip1_swiglu_resid(const Strip1Params &p, int nw, int maxs, int n_strips, hipStream_t stream) {
+  if (p.M != 1) return set_error(QLLM_ERR_UNSUPPORTED, "internal: the fused residual forms take one row");
+  return strip1_launch<Strip1SwigluResid>(p, nw, maxs, dim3(n_strips, 1), stream);
+}
+
+}  // namespace qllm

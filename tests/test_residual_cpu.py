@@ -16,6 +16,7 @@ import torch
 from kernel_resources import resources
 from qllm_amd import _lib, ops
 from qllm_amd.modeling.q_layers import _hip_forward, fused, fused_mlp, fused_norm, fused_residual
+from strip1_families import check_family
 from test_swiglu_cpu import TABLE_K
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -527,53 +528,10 @@ def test_the_installed_transformers_decoder_layers_meet_the_contract():
 
 
 # ---- resources ---------------------------------------------------------------------------------------------------------------------------
-FAMILIES = {"strip1_resid.hip": ("strip1_resid_kernel", "19"), "strip1_swiglu_resid.hip": ("strip1_swiglu_resid_kernel", "26")}
-# <NW, MAXS, EXACT, G64, B3, WAVES>
-FIELDS = r"_ZN4qllm%s%sILi(\d+)ELi(\d+)ELb([01])ELb([01])ELb([01])ELi(\d)EEEvNS_12Strip1ParamsE$"
-
-
-def _pairs(src, pattern):
-    text = open(os.path.join(ROOT, "qllm_amd", "csrc", src)).read()
-    return sorted((int(a), int(b)) for a, b in re.findall(pattern, text))
-
-
-@pytest.mark.parametrize("src", sorted(FAMILIES))
+@pytest.mark.parametrize("src", ["strip1_resid.hip", "strip1_swiglu_resid.hip"])
 def test_every_resid_instantiation_is_scratch_free_and_the_table_is_whole(src):
-    kernel, length = FAMILIES[src]
-    res = resources(src)
-    assert all(kernel in n for n in res), sorted(res)[:3]             # nothing else is built there
-    twins = resources("strip1.hip")
-    shared = "strip1_resid_forms.inc"                                 # (the launch, the forms and the pair table: one text for both files)
-    pairs = _pairs(shared, r"X\((\d+), (\d+)\)")
-    assert pairs == _pairs("strip1.hip", r"nw == (\d+) && maxs == (\d+)\) return launch_e<") and len(pairs) == 15
-    want = set()
-    for nw, maxs in pairs:
-        for exact in (0, 1):
-            want.add((nw, maxs, exact, 0, 0))                                     # plain
-            if maxs <= 48:
-                want.add((nw, maxs, exact, 1, 0))                                 # 64-wide groups
-            if maxs <= 32:
-                want.update({(nw, maxs, exact, 0, 1), (nw, maxs, exact, 1, 1)})   # 3 bits
-    got = {}
-    for n, r in res.items():
-        m = re.search(FIELDS % (length, kernel), n)
-        assert m, n
-        nw, maxs, exact, g64, b3, waves = map(int, m.groups())
-        got[(nw, maxs, exact, g64, b3)] = (waves, r)
-    assert len(res) == len(got) == len(want) == 100 and set(got) == want
-    for key, (waves, r) in sorted(got.items()):
-        nw, maxs, exact, g64, b3 = key
-        assert r["private_segment_fixed_size"] == 0 and r["vgpr_spill_count"] == 0 and r["sgpr_spill_count"] == 0, (key, r)
-        assert waves == (8 if maxs <= 24 and not g64 and not b3 else 4), key      # the twin's launch bound
-        assert r["vgpr_count"] <= 512 // waves, (key, waves, r)
-        assert waves * 4 >= nw, (key, waves)
-        twin = f"_ZN4qllm13strip1_kernelILi{nw}ELi{maxs}ELb{exact}ELi2ELi4ELb0ELb0ELb{g64}ELi1ELb{b3}EEEvNS_12Strip1ParamsE"
-        assert twin in twins, twin
-        assert r["group_segment_fixed_size"] == twins[twin]["group_segment_fixed_size"] == 0, key   # all LDS is dynamic
-    text = open(os.path.join(ROOT, "qllm_amd", "csrc", shared)).read()
-    assert text.count("strip1_lds_bytes<NW, MAXS, 1>()") == 1 and "lds_bytes, stream, p)" in text
-    unit = open(os.path.join(ROOT, "qllm_amd", "csrc", src)).read()
-    assert unit.count('#include "%s"' % shared) == 1 and "#define QLLM_RESID_KERNEL %s\n" % kernel in unit
+    """Every (NW, MAXS) pair of csrc/strip1_forms.hpp's table, in every one-row form of the plain family (strip1_families.py)."""
+    check_family(src)
 
 
 @pytest.mark.parametrize("src", ["strip1.hip", "strip1_swiglu.hip", "strip1_norm.hip"])

@@ -10,7 +10,7 @@ import torch
 
 from oracle import ref_cpu as O
 from gpu_util import Ref, guarded, randx, synth, to_layer
-from test_swiglu_gpu import CASES, SENTINEL, VARIANTS, _layer, _Tok
+from test_swiglu_gpu import CASES, FORM_OF, SENTINEL, VARIANTS, _layer, _Tok, nw16_cases  # noqa: F401  (nw16_cases: the autouse fixture)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -57,7 +57,7 @@ def test_bit_identity_with_the_eager_add(kind, K, N):
     stage through the same code)."""
     from qllm_amd import ops
     d, layer, w, keep = _layer(kind, K, N)
-    _check_plan(w)
+    assert FORM_OF.get((kind, K, N), "") in _check_plan(w)
     ref = Ref(d) if N == 256 else None
     for dtype in DTYPES:
         x, g, u = _inputs(K, N, dtype, K + N)

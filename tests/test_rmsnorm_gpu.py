@@ -14,8 +14,10 @@ overlap, the double-count case), 1024 (exact), 3584 (seven waves), 11008 (15 x 2
 that blocks of the narrower members leave before the barrier, and once N = 8192 at K = 4096 (more strips than CUs).
 
 Measured on an MI355X: rstd within 1.2e-7 relative of float64 in every cell (bounds 8e-6 .. 2e-3); the printed differ-shares are 0 in
-nineteen of the twenty cells, and in one (3 bits g64, K = 3584, fp16) 0.112 % of the xn elements of both kernels and 14 % of the 512
-outputs differ from the eager path in their last bits -- DESIGN 3.11."""
+188 of the 200 cells; in the eight fp16 cells at K = 3584 0.112 % of the xn elements of both kernels and 12-15 % of the outputs differ
+from the eager path in their last bits, in the four fp16 cells at K = 6144 0.065 % of the standalone kernel's xn only -- DESIGN 3.11.
+
+CASES holds one case for every NORM form of csrc/strip1_forms.hpp's table (MORE, below)."""
 import functools
 
 import numpy as np
@@ -24,7 +26,7 @@ import torch
 
 from oracle import ref_cpu as O
 from gpu_util import Ref, guarded, randx, synth, to_layer
-from test_swiglu_gpu import KINDS, SENTINEL, VARIANTS, _native
+from test_swiglu_gpu import KINDS, SENTINEL, VARIANTS, _native, nw16_cases  # noqa: F401  (nw16_cases: the autouse fixture of the "+nw16" kinds)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -37,6 +39,40 @@ CASES = [("w4", 256, (256,), "nw=4 round=8 grid"), ("w4", 1024, (256, 256), "nw=
          ("g64", 5120, (256, 256), " g64 "), ("g64", 4544, (256,), " g64 "), ("b3", 5120, (512, 256, 256), " bits=3 "), ("b3g64", 3584, (256, 256), " g64 bits=3 "),
          ("w4", 4096, (8192, 4096, 256), "nw=8 round=16 exact")]
 IDS = [f"{k}-K{K}-x{len(ns)}" for k, K, ns, _ in CASES]
+# One single-layer case for every NORM form of csrc/strip1_forms.hpp's table that the list above does not plan to (tests/test_swiglu_gpu.py,
+# MORE: the same rule for N and K), in front of the last case.
+MORE = [("b3", 256, (256,), "nw=4 round=8 bits=3 grid"), ("g64", 256, (256,), "nw=4 round=8 g64 grid"), ("b3g64", 256, (256,), "nw=4 round=8 g64 bits=3 grid"),
+        ("b3", 1024, (256,), "nw=4 round=8 exact bits=3 grid"), ("g64", 1024, (256,), "nw=4 round=8 exact g64 grid"), ("b3g64", 1024, (256,), "nw=4 round=8 exact g64 bits=3 grid"),
+        ("w4", 1152, (256,), "nw=4 round=16 grid"), ("b3", 1152, (256,), "nw=4 round=16 bits=3 grid"), ("g64", 1152, (256,), "nw=4 round=16 g64 grid"),
+        ("b3g64", 1152, (256,), "nw=4 round=16 g64 bits=3 grid"), ("w4", 2048, (256,), "nw=4 round=16 exact grid"), ("b3", 2048, (256,), "nw=4 round=16 exact bits=3 grid"),
+        ("g64", 2048, (256,), "nw=4 round=16 exact g64 grid"), ("b3g64", 2048, (256,), "nw=4 round=16 exact g64 bits=3 grid"), ("w4", 3584, (256,), "nw=4 round=32 grid"),
+        ("b3", 3584, (256,), "nw=4 round=32 bits=3 grid"), ("g64", 3584, (256,), "nw=4 round=32 g64 grid"), ("w4", 4096, (256,), "nw=4 round=32 exact grid"),
+        ("b3", 4096, (256,), "nw=4 round=32 exact bits=3 grid"), ("g64", 4096, (256,), "nw=4 round=32 exact g64 grid"), ("b3g64", 4096, (256,), "nw=4 round=32 exact g64 bits=3 grid"),
+        ("w4", 3200, (8192,), "nw=7 round=16 grid"), ("b3", 3200, (8192,), "nw=7 round=16 bits=3 grid"), ("g64", 3200, (8192,), "nw=7 round=16 g64 grid"),
+        ("b3g64", 3200, (8192,), "nw=7 round=16 g64 bits=3 grid"), ("b3", 3584, (8192,), "nw=7 round=16 exact bits=3 grid"), ("g64", 3584, (8192,), "nw=7 round=16 exact g64 grid"),
+        ("b3g64", 3584, (8192,), "nw=7 round=16 exact g64 bits=3 grid"), ("w4", 3840, (8192,), "nw=8 round=16 grid"), ("b3", 3840, (8192,), "nw=8 round=16 bits=3 grid"),
+        ("g64", 3840, (8192,), "nw=8 round=16 g64 grid"), ("b3g64", 3840, (8192,), "nw=8 round=16 g64 bits=3 grid"), ("b3", 4096, (8192,), "nw=8 round=16 exact bits=3 grid"),
+        ("g64", 4096, (8192,), "nw=8 round=16 exact g64 grid"), ("b3g64", 4096, (8192,), "nw=8 round=16 exact g64 bits=3 grid"), ("w4", 5120, (256,), "nw=8 round=24 grid"),
+        ("b3g64", 5120, (256,), "nw=8 round=24 g64 bits=3 grid"), ("w4", 6144, (256,), "nw=8 round=24 exact grid"), ("b3", 6144, (256,), "nw=8 round=24 exact bits=3 grid"),
+        ("g64", 6144, (256,), "nw=8 round=24 exact g64 grid"), ("b3g64", 6144, (256,), "nw=8 round=24 exact g64 bits=3 grid"), ("w4", 6656, (256,), "nw=8 round=32 grid"),
+        ("b3", 6656, (256,), "nw=8 round=32 bits=3 grid"), ("g64", 6656, (256,), "nw=8 round=32 g64 grid"), ("b3g64", 6656, (256,), "nw=8 round=32 g64 bits=3 grid"),
+        ("w4", 8192, (256,), "nw=8 round=32 exact grid"), ("b3", 8192, (256,), "nw=8 round=32 exact bits=3 grid"), ("g64", 8192, (256,), "nw=8 round=32 exact g64 grid"),
+        ("b3g64", 8192, (256,), "nw=8 round=32 exact g64 bits=3 grid"), ("b3", 11008, (256,), "nw=15 round=24 bits=3 grid"), ("g64", 11008, (256,), "nw=15 round=24 g64 grid"),
+        ("b3g64", 11008, (256,), "nw=15 round=24 g64 bits=3 grid"), ("w4", 11520, (256,), "nw=15 round=24 exact grid"), ("b3", 11520, (256,), "nw=15 round=24 exact bits=3 grid"),
+        ("g64", 11520, (256,), "nw=15 round=24 exact g64 grid"), ("b3g64", 11520, (256,), "nw=15 round=24 exact g64 bits=3 grid"), ("w4+nw16", 6656, (256,), "nw=16 round=16 grid"),
+        ("b3+nw16", 6656, (256,), "nw=16 round=16 bits=3 grid"), ("g64+nw16", 6656, (256,), "nw=16 round=16 g64 grid"), ("b3g64+nw16", 6656, (256,), "nw=16 round=16 g64 bits=3 grid"),
+        ("w4+nw16", 8192, (256,), "nw=16 round=16 exact grid"), ("b3+nw16", 8192, (256,), "nw=16 round=16 exact bits=3 grid"), ("g64+nw16", 8192, (256,), "nw=16 round=16 exact g64 grid"),
+        ("b3g64+nw16", 8192, (256,), "nw=16 round=16 exact g64 bits=3 grid"), ("w4", 11776, (256,), "nw=16 round=24 grid"), ("b3", 11776, (256,), "nw=16 round=24 bits=3 grid"),
+        ("g64", 11776, (256,), "nw=16 round=24 g64 grid"), ("b3g64", 11776, (256,), "nw=16 round=24 g64 bits=3 grid"), ("w4", 12288, (256,), "nw=16 round=24 exact grid"),
+        ("b3", 12288, (256,), "nw=16 round=24 exact bits=3 grid"), ("g64", 12288, (256,), "nw=16 round=24 exact g64 grid"), ("b3g64", 12288, (256,), "nw=16 round=24 exact g64 bits=3 grid"),
+        ("w4", 14336, (256,), "nw=16 round=32 grid"), ("b3", 14336, (256,), "nw=16 round=32 bits=3 grid"), ("g64", 14336, (256,), "nw=16 round=32 g64 grid"),
+        ("b3g64", 14336, (256,), "nw=16 round=32 g64 bits=3 grid"), ("w4", 16384, (256,), "nw=16 round=32 exact grid"), ("b3", 16384, (256,), "nw=16 round=32 exact bits=3 grid"),
+        ("g64", 16384, (256,), "nw=16 round=32 exact g64 grid"), ("b3g64", 16384, (256,), "nw=16 round=32 exact g64 bits=3 grid"), ("g64", 18944, (256,), "nw=16 round=40 g64 grid"),
+        ("w4", 20480, (256,), "nw=16 round=40 exact grid"), ("g64", 20480, (256,), "nw=16 round=40 exact g64 grid"), ("w4", 22016, (256,), "nw=16 round=48 grid"),
+        ("g64", 22016, (256,), "nw=16 round=48 g64 grid"), ("w4", 24576, (256,), "nw=16 round=48 exact grid"), ("g64", 24576, (256,), "nw=16 round=48 exact g64 grid"),
+        ("w4", 26624, (256,), "nw=16 round=56 grid"), ("w4", 28672, (256,), "nw=16 round=56 exact grid"), ("w4", 28800, (256,), "nw=16 round=64 grid")]
+CASES[-1:-1] = MORE
+IDS[-1:-1] = [f"{k}-K{K}-N{ns[0]}" for k, K, ns, _ in MORE]
 BIG = CASES[-1]
 
 

@@ -9,9 +9,9 @@ import re
 import pytest
 import torch
 
-from kernel_resources import resources
 from qllm_amd import _lib, ops
 from qllm_amd.modeling.q_layers import _hip_forward, fused_mlp
+from strip1_families import check_family
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GPTQ, NATIVE, NATIVE_F16Z = _lib.LAYOUT_GPTQ, _lib.LAYOUT_NATIVE, _lib.LAYOUT_NATIVE_F16Z
@@ -261,45 +261,6 @@ def test_load_quantized_keeps_the_fusion_opt_in():
 
 
 # ---- resources ---------------------------------------------------------------------------------------------------------------------------
-FIELDS = r"strip1_swiglu_kernelILi(\d+)ELi(\d+)ELb([01])ELb([01])ELi(\d)ELb([01])ELi(\d)EEEvNS_12Strip1ParamsE$"   # <NW, MAXS, EXACT, G64, MR, B3, WAVES>
-
-
-def _pairs(src, pattern):
-    text = open(os.path.join(ROOT, "qllm_amd", "csrc", src)).read()
-    return sorted((int(a), int(b)) for a, b in re.findall(pattern, text))
-
-
 def test_every_swiglu_instantiation_is_scratch_free_and_the_table_is_whole():
-    res = {n: r for n, r in resources("strip1_swiglu.hip").items() if "strip1_swiglu_kernel" in n}
-    twins = resources("strip1.hip")
-    # the launcher's table: every (NW, MAXS) pair of launch_strip1's, in the forms launch_e builds with the same caps on the round length
-    pairs = _pairs("strip1_swiglu.hip", r"X\((\d+), (\d+)\)")
-    assert pairs == _pairs("strip1.hip", r"nw == (\d+) && maxs == (\d+)\) return launch_e<") and len(pairs) == 15
-    want = set()
-    for nw, maxs in pairs:
-        for exact in (0, 1):
-            want.add((nw, maxs, exact, 0, 1, 0))                                  # plain
-            if maxs <= 48:
-                want.add((nw, maxs, exact, 1, 1, 0))                              # 64-wide groups
-            if maxs <= 32:
-                want.update({(nw, maxs, exact, 0, 1, 1), (nw, maxs, exact, 1, 1, 1), (nw, maxs, exact, 0, 4, 0)})   # 3 bits; four rows
-    got = {}
-    for n, r in res.items():
-        m = re.search(FIELDS, n)
-        assert m, n
-        nw, maxs, exact, g64, mr, b3, waves = map(int, m.groups())
-        got[(nw, maxs, exact, g64, mr, b3)] = (waves, r)
-    assert len(res) == len(got) == len(want) == 122 and set(got) == want
-    for (nw, maxs, exact, g64, mr, b3), (waves, r) in sorted(got.items()):
-        key = (nw, maxs, exact, g64, mr, b3)
-        assert r["private_segment_fixed_size"] == 0 and r["vgpr_spill_count"] == 0 and r["sgpr_spill_count"] == 0, (key, r)
-        # the registers its launch bound allows (512 per SIMD lane over `waves` waves; a 16-wave block needs 4 per SIMD)
-        assert waves in (4, 8) and r["vgpr_count"] <= 512 // waves, (key, waves, r)
-        assert waves * 4 >= nw, (key, waves)
-        twin = f"_ZN4qllm13strip1_kernelILi{nw}ELi{maxs}ELb{exact}ELi2ELi4ELb0ELb0ELb{g64}ELi{mr}ELb{b3}EEEvNS_12Strip1ParamsE"
-        assert twin in twins, twin
-        # LDS: all of it is dynamic -- strip1_lds_bytes<NW, MAXS, MR>() at the launch, the twin's own expression -- and none static
-        assert r["group_segment_fixed_size"] == twins[twin]["group_segment_fixed_size"] == 0, key
-        assert twins[twin]["vgpr_spill_count"] == 0
-    src = open(os.path.join(ROOT, "qllm_amd", "csrc", "strip1_swiglu.hip")).read()
-    assert src.count("strip1_lds_bytes<NW, MAXS, MR>()") == 1 and "lds_bytes, stream, p)" in src
+    """Every (NW, MAXS) pair of csrc/strip1_forms.hpp's table, in every form of the plain family, four-row forms included (strip1_families.py)."""
+    check_family("strip1_swiglu.hip")

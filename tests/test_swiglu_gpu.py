@@ -6,7 +6,7 @@ in {0} u {20..40}, silu(g) == g exactly (1 + exp(-g) rounds to 1 in fp32), so `l
 `linear_forward(w, F.silu(g) * u)` bit for bit whatever the device's expf does.  Random gates are held to the project's tolerances against
 the oracle (tests/test_strip1_gpu.py) and the share of outputs that differ from the unfused launch is printed, not asserted.
 
-Measured on an MI355X (the printed shares, random gates of both signs, all 190 cells): 0.00000 everywhere -- DESIGN 3.10."""
+Measured on an MI355X (the printed shares, random gates of both signs, all 278 cells): 0.00000 everywhere -- DESIGN 3.10."""
 import functools
 
 import numpy as np
@@ -26,6 +26,8 @@ SENTINEL = 0x7E5A   # an fp16 / bf16 NaN nobody computes (tests/test_bitgemv_gro
 # (kind, K, N): every K of the three form lists at N = 256 (16 strips: one block per CU at most) and, for K <= 4096, at N = 8192 too (more
 # strips than CUs: the wide-launch forms of those K)
 KINDS = {"w4": (4, 128), "g64": (4, 64), "b3": (3, 128), "b3g64": (3, 64)}
+NW16 = "+nw16"   # a kind with this suffix: the case runs with QLLM_S1_T256_NW16 = 1, which the (16, 16) pair of the shape table needs
+KINDS.update({kind + NW16: v for kind, v in list(KINDS.items())})
 
 
 def _cases():
@@ -38,7 +40,25 @@ def _cases():
     return out
 
 
-CASES = _cases()
+# (kind, K, N, the plan line's form): one case for every form of csrc/strip1_forms.hpp's table that the three lists do not plan to -- N = 256,
+# or 8192 for the pairs taken on wide launches only; K = 32 NW MAXS for an exact form, a K of the lists (or the smallest) for a shifted one.
+# With these every SWIGLU and every RESID form is launched here and in tests/test_residual_gpu.py, and its plain twin next to it.
+MORE = [("b3", 256, 256, "nw=4 round=8 bits=3 grid"), ("b3g64", 256, 256, "nw=4 round=8 g64 bits=3 grid"), ("b3", 1152, 256, "nw=4 round=16 bits=3 grid"),
+        ("g64", 1152, 256, "nw=4 round=16 g64 grid"), ("b3g64", 1152, 256, "nw=4 round=16 g64 bits=3 grid"), ("w4", 3200, 8192, "nw=7 round=16 grid"),
+        ("b3", 3200, 8192, "nw=7 round=16 bits=3 grid"), ("g64", 3200, 8192, "nw=7 round=16 g64 grid"), ("b3g64", 3200, 8192, "nw=7 round=16 g64 bits=3 grid"),
+        ("b3", 3840, 8192, "nw=8 round=16 bits=3 grid"), ("g64", 3840, 8192, "nw=8 round=16 g64 grid"), ("b3g64", 3840, 8192, "nw=8 round=16 g64 bits=3 grid"),
+        ("b3", 6144, 256, "nw=8 round=24 exact bits=3 grid"), ("g64", 6144, 256, "nw=8 round=24 exact g64 grid"), ("b3g64", 6144, 256, "nw=8 round=24 exact g64 bits=3 grid"),
+        ("b3", 6656, 256, "nw=8 round=32 bits=3 grid"), ("g64", 6656, 256, "nw=8 round=32 g64 grid"), ("b3g64", 6656, 256, "nw=8 round=32 g64 bits=3 grid"),
+        ("w4", 11520, 256, "nw=15 round=24 exact grid"), ("b3", 11520, 256, "nw=15 round=24 exact bits=3 grid"), ("g64", 11520, 256, "nw=15 round=24 exact g64 grid"),
+        ("b3g64", 11520, 256, "nw=15 round=24 exact g64 bits=3 grid"), ("w4+nw16", 6656, 256, "nw=16 round=16 grid"), ("b3+nw16", 6656, 256, "nw=16 round=16 bits=3 grid"),
+        ("g64+nw16", 6656, 256, "nw=16 round=16 g64 grid"), ("b3g64+nw16", 6656, 256, "nw=16 round=16 g64 bits=3 grid"), ("w4+nw16", 8192, 256, "nw=16 round=16 exact grid"),
+        ("b3+nw16", 8192, 256, "nw=16 round=16 exact bits=3 grid"), ("g64+nw16", 8192, 256, "nw=16 round=16 exact g64 grid"), ("b3g64+nw16", 8192, 256, "nw=16 round=16 exact g64 bits=3 grid"),
+        ("b3", 11776, 256, "nw=16 round=24 bits=3 grid"), ("g64", 11776, 256, "nw=16 round=24 g64 grid"), ("b3g64", 11776, 256, "nw=16 round=24 g64 bits=3 grid"),
+        ("b3", 12288, 256, "nw=16 round=24 exact bits=3 grid"), ("g64", 12288, 256, "nw=16 round=24 exact g64 grid"), ("b3g64", 12288, 256, "nw=16 round=24 exact g64 bits=3 grid"),
+        ("g64", 16384, 256, "nw=16 round=32 exact g64 grid"), ("g64", 20480, 256, "nw=16 round=40 exact g64 grid"), ("g64", 22016, 256, "nw=16 round=48 g64 grid"),
+        ("w4", 28800, 256, "nw=16 round=64 grid")]
+CASES = _cases() + [c[:3] for c in MORE]
+FORM_OF = {c[:3]: c[3] for c in MORE}
 # zero points / bias / layout rotate over the cases (the staging under test does not depend on them); test_zero_kinds_and_bias crosses them
 VARIANTS = (("GPTQ", "asym", False), ("HQQ", "asym", True), ("GPTQ", "sym", True), ("HQQ", "asym", False), ("GPTQ", "asym", True), ("GPTQ", "sym", False))
 
@@ -66,7 +86,22 @@ def _layer(kind, K, N, variant=None, compat=0):
 
 
 def _rows(kind, K):
-    return (1, 2, 3, 4) if kind == "w4" and K <= 16384 else (1,)
+    return (1, 2, 3, 4) if KINDS[kind] == (4, 128) and K <= 16384 else (1,)
+
+
+@pytest.fixture(autouse=True)
+def nw16_cases(request):
+    """QLLM_S1_T256_NW16 = 1 for the length of a test whose `kind` carries the suffix."""
+    from qllm_amd import ops
+    kind = request.node.callspec.params.get("kind", "") if hasattr(request.node, "callspec") else ""
+    if not str(kind).endswith(NW16):
+        yield
+        return
+    ops.set_knob("QLLM_S1_T256_NW16", 1)
+    try:
+        yield
+    finally:
+        ops.reset_knobs()
 
 
 def _exact_gates(m, K, dtype, seed):
@@ -101,7 +136,7 @@ def test_bit_identity_with_the_unfused_launch(kind, K, N):
     from qllm_amd import ops
     d, layer, w, keep = _layer(kind, K, N)
     for m in _rows(kind, K):
-        _check_plan(w, m)
+        assert FORM_OF.get((kind, K, N), "").replace(" grid", " rows=4 grid" if m > 1 else " grid") in _check_plan(w, m)
         for dtype in DTYPES:
             g = _exact_gates(m, K, dtype, seed=K + m).to(DEV)
             u = (torch.from_numpy(randx(m, K, seed=K + 7 * m)) / 16).to(dtype).to(DEV)
