@@ -33,6 +33,7 @@
 //   * epilogue through LDS: 16-byte row-contiguous stores where N % 8 == 0 and y is 16-byte aligned, else two-byte stores.
 // K % 32 == 0, group_size % 32 == 0 (any such size: the group walk is a counter, not a template parameter), any N >= 1.
 #include "kernels.hpp"
+#include "planner.hpp"
 
 namespace qllm {
 
@@ -431,7 +432,7 @@ BitPanelGeom bitpanel_geometry(const qllm_weight_t &w, int M, size_t ws_bytes) {
   g.chunk = chunk_for(S);
   g.split_k = (T + g.chunk - 1) / g.chunk;
   g.slab_bytes = g.split_k > 1 ? (size_t)blocks * g.split_k * g.mt * 4096 : 0;  // [panel x row block][split][4 waves x MT x 4 x 64] fp32
-  if (g.split_k > 1 && (ws_bytes < 16384 + g.slab_bytes || blocks > 4096)) {     // (16384: the counter page every route shares)
+  if (g.split_k > 1 && (ws_bytes < kCounterBytes + g.slab_bytes || blocks > (int)(kCounterBytes / sizeof(int)))) {  // (the counter page every route shares)
     g.split_k = 1;
     g.chunk = even_T;
     g.slab_bytes = 0;

@@ -33,20 +33,17 @@
 //   * epilogue: + bias, one rounding, transposed through wave-private LDS into 16-byte row-contiguous stores.
 // Serves what gemm2's 256x128 form serves when no split-K is wanted (M >= 1024 on the Llama shapes); gemm2 keeps the rest.
 // Replaces gemm_forward_4bit_cuda_m16n128k32 (/root/reference/csrc/awq_cuda/quantization/gemm_cuda_gen.cu:31-353).
+//
+// Shared with bitgemm.hip (the same tile, MW = 8, for the widths and the N this unit does not take): tile256.hpp holds the tile
+// constants, tile_off and xcd_run; tile256_body.inc holds the staging waves' schedule, the matrix waves, the split-K hand-off and the
+// epilogue, and is included into gemm3_kernel below.  What is this unit's own: the block-to-tile map (tail split, grouped launches,
+// raster) and the staging waves' load_b / store_b for the three 4- / 3-bit layouts.
 #include <stdlib.h>
 
 #include "kernels.hpp"
+#include "tile256.hpp"
 
 namespace qllm {
-
-namespace g3 {
-constexpr int BM = 256, BN = 128, BK = 64;
-constexpr int kATile = BM * BK, kBTile = BN * BK;  // halves per stage
-typedef float float16_t __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) void lds_void_t;
-
-__device__ __forceinline__ int tile_off(int row, int slot) { return row * BK + ((slot ^ lds_row_swizzle(row)) & 7) * 8; }  // in halves
-}  // namespace g3
 
 // LAYOUT 0 = GPTQ/HQQ row stream (4 bits), 1 = AWQ GEMM, 2 = GPTQ/HQQ row stream with 3-bit weights (bit stream: the 32 k of
 // a half k-tile are 3 consecutive word rows of the column).  p.sm (LAYOUT 0 / 2): the same words stored strip-major (the native
@@ -62,17 +59,17 @@ __device__ __forceinline__ int tile_off(int row, int slot) { return row * BK + (
 // staging waves dequantise to bf16 (q as fp32 via v_cvt_f32_ubyte, one v_pk_fma_f32 per pair: W = bf16(s q - s z), ONE rounding;
 // v_cvt_pk_bf16_f32), the matrix waves run v_mfma_f32_32x32x16_bf16 and the epilogue rounds the fp32 sums to bf16 once.  No conversion
 // pre-pass, no fp16 overflow for |x| > 65504 (the reference's shim casts x to fp16: quant_linear_awq.py:29-36).
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef float float2_t __attribute__((ext_vector_type(2)));
 
 template <int LAYOUT, int MW, bool PRIO = true, bool BF = false>
 __global__ __launch_bounds__((MW + 4) * 64) void gemm3_kernel(const GemmParams p) {
   static_assert(!BF || LAYOUT == 0, "native bf16: row-stream / strip-major 4-bit layers");
-  using namespace g3;
+  using namespace tile256;
   constexpr int AM = 8 / MW * 2;       // 32-row MFMA tiles per matrix wave along M: 4 or 2
   constexpr int WROWS = AM * 32;       // rows per matrix wave: 128 or 64
   constexpr int NP = 32 / MW;          // activation DMA pieces (8 rows x 128 B) per matrix wave and k-tile: 8 or 4
+  constexpr bool N_ENDS_IN_TILE = false;  // a column tile ends at 128 columns, or at 64 (the half-wide last tile): whole matrix waves
   extern __shared__ __attribute__((aligned(16))) half_t smem[];
   half_t *As = smem;               // [3][256][64]  (LDS-DMA ring)
   half_t *Bs = smem + 3 * kATile;  // [2][128 n][64 k]
@@ -89,10 +86,6 @@ __global__ __launch_bounds__((MW + 4) * 64) void gemm3_kernel(const GemmParams p
   // each publishes its fp32 partial tile to a slab, the last to arrive sums them in fixed order (the protocol of gemm2.hip)
   // Round 6, tail split (p.tail_split > 1, tiles > CUs): the tiles of the whole rounds run unsplit; the tiles of the ragged last round
   // are shared by tail_split blocks each -- two segments of block ids, each walked XCD-contiguously.
-  auto xcd_run = [](int b, int n) {  // each XCD (block id % 8) walks a contiguous run of the n blocks
-    const int q = n / 8, r = n % 8, xcd = b % 8, idx = b / 8;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  };
   int S, ksplit, tile_id, slab_tile;
   if (p.tail_split > 1) {
     const int F = p.tail_from, bid = blockIdx.x;
@@ -275,226 +268,11 @@ __global__ __launch_bounds__((MW + 4) * 64) void gemm3_kernel(const GemmParams p
       }
     };
 
-    // Order of one iteration: [write B tile kt+1 from its register set] barrier [request tile kt+3 into that set].  A set is
-    // requested right after the barrier that frees it and consumed two barriers later (~1.5 k-tiles of flight), and the only
-    // vmcnt wait in the loop is the counted one in front of the stores (the younger set's loads stay in flight).  Nothing is
-    // conditional around a load (a branch there makes hipcc's counted vmcnt collapse to vmcnt(0)): past the last tile the
-    // loads re-read it and the stores fill a stage nobody reads again.
-    load_b(0, bset[0]);
-    load_b(1, bset[1]);
-    __builtin_amdgcn_sched_barrier(0);
-    store_b(0, bset[0]);
-    __builtin_amdgcn_sched_barrier(0);
-    load_b(2, bset[0]);
-    __syncthreads();  // prologue barrier: B stage 0 holds tile 0
-    for (int kt = 0; kt + 1 < KT; kt += 2) {  // two k-tiles per trip: the register sets alternate by name, no branch between them
-      store_b(1, bset[1]);
-      __syncthreads();  // barrier #kt
-      load_b(kt + 3, bset[1]);
-      __builtin_amdgcn_sched_barrier(0);
-      store_b(0, bset[0]);
-      __syncthreads();  // barrier #kt+1
-      load_b(kt + 4, bset[0]);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (KT & 1) __syncthreads();  // odd number of k-tiles: barrier #KT-1 (the tile it would publish does not exist)
-    __syncthreads();  // matches the matrix waves' barrier in front of their epilogue
-    if (S > 1) {          // ... and the two around the split-K ticket
-      __syncthreads();
-      __syncthreads();
-    }
-    return;
+#define TILE256_STAGING  // the schedule of load_b / store_b / barriers
+#include "tile256_body.inc"
   }
 
-  // =================================================== matrix waves ===================================================
-  const int wm = wave >> 1, wn = wave & 1;  // (MW/2) (M) x 2 (N): rows wm*WROWS.., columns wn*64..
-  const int fr = lane & 31, fs = lane >> 5;  // fragment row (A: m, B: n) and k half of the 16-wide sub-step
-  float16_t acc[AM][2];
-#pragma unroll
-  for (int a = 0; a < AM; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-
-  half8_t fa0[AM], fb0[2], fa1[AM], fb1[2];
-  auto read_frags = [&](int sa, int sb, int ks, half8_t (&fa)[AM], half8_t (&fb)[2]) {
-    const half_t *Ab = As + sa * kATile, *Bb = Bs + sb * kBTile;
-#pragma unroll
-    for (int b = 0; b < 2; ++b) fb[b] = *(const half8_t *)(Bb + tile_off(wn * 64 + b * 32 + fr, ks * 2 + fs));
-#pragma unroll
-    for (int a = 0; a < AM; ++a) fa[a] = *(const half8_t *)(Ab + tile_off(wm * WROWS + a * 32 + fr, ks * 2 + fs));
-  };
-  // ---- activation tile by LDS-DMA: this wave owns rows wave*64 .. +63 of the 256-row tile = 8 pieces of 8 rows x 128 B.
-  // Piece q: lane l -> LDS row r = wave*64 + 8q + l/8, physical slot l%8, which holds logical 16-byte chunk (l%8) ^ ((r>>1)&7).
-  // Per-lane byte offsets into x are loop constants; the k-tile advance (128 B) is the scalar offset.
-  const auto rs_x = __builtin_amdgcn_make_buffer_rsrc((void *)p.x, 0, (int)min((size_t)p.M * p.K * 2, (size_t)0x7fffffff), 0x00020000);
-  int voff_x[NP];
-#pragma unroll
-  for (int q = 0; q < NP; ++q) {
-    const int r = wave * (8 * NP) + 8 * q + (lane >> 3);
-    const int grow = min(m0 + r, p.M - 1);  // rows past M re-read the last row; their outputs are never stored
-    voff_x[q] = grow * p.K * 2 + (((lane & 7) ^ lds_row_swizzle(r)) << 4);
-  }
-  // one DMA piece (8 rows x 128 B of this wave's 64 rows) of k-tile kt into ring slot `slot`
-  // (the builtin's operands are first copied into plain locals: called with template-dependent expressions, the HOST pass of
-  //  hipcc silently fails to instantiate the whole kernel -- no diagnostic, just an undefined __device_stub__ at load time)
-  const int rows_per_wave = 8 * NP;
-  auto dma_piece = [&](int kt, int slot, int q) {
-    const int so = (KT0 + min(kt, KT - 1)) * (BK * 2);
-    const int vo = voff_x[q];
-    lds_void_t *dst = (lds_void_t *)(As + slot * kATile + (wave * rows_per_wave + q * 8) * BK);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, dst, 16, vo, so, 0, 0);
-  };
-  // half of a sub-step's MFMAs: row tiles [h * AM/2, (h+1) * AM/2)
-  auto mfma_half = [&](const half8_t (&fa)[AM], const half8_t (&fb)[2], int h) {
-#pragma unroll
-    for (int a = h * (AM / 2); a < (h + 1) * (AM / 2); ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {
-        if constexpr (BF) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, fa[a]), __builtin_bit_cast(bf16x8_t, fb[b]), acc[a][b], 0, 0, 0);
-        else acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[a], fb[b], acc[a][b], 0, 0, 0);
-      }
-  };
-
-  if constexpr (PRIO) __builtin_amdgcn_s_setprio(2);  // the matrix wave outranks its SIMD's dequant wave for issue slots
-#pragma unroll
-  for (int q = 0; q < NP; ++q) dma_piece(0, 0, q);
-#pragma unroll
-  for (int q = 0; q < NP; ++q) dma_piece(1, 1, q);
-  if constexpr (NP == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");  // tile 0's pieces have landed (tile 1's still in flight)
-  else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  __builtin_amdgcn_s_barrier();                      // prologue barrier (the dequant waves' __syncthreads)
-#pragma unroll
-  for (int q = 0; q < NP / 4; ++q) dma_piece(2, 2, q);
-  read_frags(0, 0, 0, fa0, fb0);
-  // The issue order is pinned (sched_barrier): left alone, hipcc sinks every fragment read to just above its first use
-  // (fewest live registers) and the lone matrix wave of the SIMD then sits out each LDS round trip with an idle matrix pipe.
-  // A DMA piece costs 60-180 issue cycles (MI355X_MICROARCH.md): one goes behind every four MFMAs (128 cycles of matrix-pipe
-  // work), never eight in a row (first version: all eight right after the barrier -- the pipe ran dry behind them).
-  // Between barrier #kt-1 and barrier #kt the wave requests the 8 pieces of tile kt+2 (slot (kt+2)%3, freed by barrier
-  // #kt-1): pieces 0,1 beside sub-step 3 of tile kt-1, pieces 2..7 beside sub-steps 0..2 of tile kt.  At barrier #kt the
-  // pieces of tile kt+1 are older than those 8: vmcnt(8) retires exactly them.
-#define G3_SB() __builtin_amdgcn_sched_barrier(0)
-  // NP == 4 (one piece per sub-step): the piece goes BETWEEN the two halves of the sub-step's MFMAs, not behind them (round 4,
-  // profiles/logs/r04p_time_native.log: +1-2 % on all three shapes; alternating the position between the two matrix waves of a SIMD: none)
-#define G3_PIECE_MID(kt_, slot_, q8, q4) { dma_piece(kt_, slot_, NP == 8 ? q8 : q4); G3_SB(); }
-#define G3_PIECE_END(kt_, slot_, q8, q4) if constexpr (NP == 8) { dma_piece(kt_, slot_, q8); } G3_SB();
-  int sa = 0;  // A ring slot of tile kt (kt % 3)
-  for (int kt = 0; kt < KT; ++kt) {
-    const int sb = kt & 1;
-    const int sa1 = (sa == 2) ? 0 : sa + 1, sa2 = (sa == 0) ? 2 : sa - 1;  // slots of tiles kt+1, kt+2
-    // pieces per sub-step: NP / 4 (2 or 1), one behind each half (NP = 8) or behind the first half (NP = 4) of its MFMAs;
-    // piece indices: sub-step 3 of the previous tile took [0, NP/4), sub-steps 0..2 take the rest
-    read_frags(sa, sb, 1, fa1, fb1);
-    G3_SB();
-    mfma_half(fa0, fb0, 0); G3_SB();
-    G3_PIECE_MID(kt + 2, sa2, 2, 1)
-    mfma_half(fa0, fb0, 1); G3_SB();
-    G3_PIECE_END(kt + 2, sa2, 3, 1)  // sub-step 0
-    read_frags(sa, sb, 2, fa0, fb0);
-    G3_SB();
-    mfma_half(fa1, fb1, 0); G3_SB();
-    G3_PIECE_MID(kt + 2, sa2, 4, 2)
-    mfma_half(fa1, fb1, 1); G3_SB();
-    G3_PIECE_END(kt + 2, sa2, 5, 2)  // sub-step 1
-    read_frags(sa, sb, 3, fa1, fb1);
-    G3_SB();
-    mfma_half(fa0, fb0, 0); G3_SB();
-    G3_PIECE_MID(kt + 2, sa2, 6, 3)
-    mfma_half(fa0, fb0, 1); G3_SB();
-    G3_PIECE_END(kt + 2, sa2, 7, 3)  // sub-step 2
-    // barrier #kt: my fragment reads of tile kt are complete (lgkmcnt(0)) and my DMA pieces of tile kt+1 have landed
-    // (vmcnt(NP): only tile kt+2's are still in flight).  After it: B stage sb and A slot sa are free, tile kt+1 is complete.
-    if constexpr (NP == 8) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    G3_SB();
-    read_frags(sa1, sb ^ 1, 0, fa0, fb0);  // past the last tile: stages nobody uses
-    G3_SB();
-    mfma_half(fa1, fb1, 0); G3_SB();
-    G3_PIECE_MID(kt + 3, sa, 0, 0)
-    mfma_half(fa1, fb1, 1); G3_SB();
-    G3_PIECE_END(kt + 3, sa, 1, 0)  // sub-step 3
-    sa = sa1;
-  }
-  // (half-wide last tile: the matrix waves with wn = 1 run this loop too -- their MFMAs on B columns nobody stores cost no time,
-  //  the tile's length is set by the live waves' SIMDs -- and leave before the epilogue)
-  const bool live = n0 + wn * 64 < PN;
-#undef G3_PIECE_MID
-#undef G3_PIECE_END
-#undef G3_SB
-  __builtin_amdgcn_s_setprio(0);
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // stray DMA pieces past the last tile: land before the LDS is reused
-  __builtin_amdgcn_s_barrier();                                // (matched by the dequant waves' final barrier)
-
-  // ---- split-K: publish the fp32 partial tile; the last block to arrive sums the S partials in fixed order (deterministic).
-  // Write-through (sc1) stores, every storing wave drains them, one relaxed agent-scope ticket per block, the last arriver reads
-  // with sc1 loads and re-arms the counter.  Slab element (tile, split, wave, register, lane): 256 contiguous bytes per instruction.
-  if (S > 1) {
-    int &s_ticket = *(int *)(smem + 24 * 1024);  // past the epilogue's wave-private regions (8 x 4.5 KB)
-    constexpr int WREGS = AM * 2 * 16;
-    float *slab = p.slabs + ((size_t)slab_tile * S + ksplit) * (size_t)(BM * BN) + (size_t)wave * (WREGS * 64) + lane;
-#pragma unroll
-    for (int a = 0; a < AM; ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) st_sc1(slab + ((a * 2 + b) * 16 + r) * 64, acc[a][b][r]);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) s_ticket = __hip_atomic_fetch_add(p.counters + slab_tile, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    if (s_ticket != S - 1) return;
-#pragma unroll
-    for (int a = 0; a < AM; ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-    for (int sp = 0; sp < S; ++sp) {
-      const float *src = p.slabs + ((size_t)slab_tile * S + sp) * (size_t)(BM * BN) + (size_t)wave * (WREGS * 64) + lane;
-#pragma unroll
-      for (int a = 0; a < AM; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[a][b][r] += ld_sc1(src + ((a * 2 + b) * 16 + r) * 64);
-    }
-    if (tid == 0) __hip_atomic_store(p.counters + slab_tile, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  if (!live) return;  // (columns past N: no bias, no store; the block's last barrier is behind it)
-
-  // ---- epilogue: + bias, round once, transpose through wave-private LDS, 16-byte row-contiguous stores ---------------------
-  // C/D layout of 32x32 tiles: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).  (All fragment reads that
-  // matter completed before the last barrier; the stray ones above only fill registers.)
-  half_t *ep = smem + wave * (32 * 72);  // 32 rows x 64 cols, row stride 72 halves (144 B)
-  float bv[2];
-#pragma unroll
-  for (int b = 0; b < 2; ++b) bv[b] = Pbias ? (float)Pbias[n0 + wn * 64 + b * 32 + fr] : 0.f;
-#pragma unroll
-  for (int a = 0; a < AM; ++a) {
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = (r & 3) + 8 * (r >> 2) + 4 * fs;
-        const float v = acc[a][b][r] + bv[b];
-        // bf16 activations (x converted to fp16 by the pre-pass): the result is rounded to fp16 and then to bf16, as the
-        // reference's shim does (fp16 kernel output .to(bfloat16), quant_linear_awq.py:29-36, 144-146)
-        if constexpr (BF) ((uint16_t *)ep)[row * 72 + b * 32 + fr] = f32_to_bf16(v);  // (native bf16: one rounding of the fp32 sum)
-        else if (p.out_bf16) ((uint16_t *)ep)[row * 72 + b * 32 + fr] = f32_to_bf16((float)(half_t)v);
-        else ep[row * 72 + b * 32 + fr] = (half_t)v;
-      }
-    // 32 rows x 128 B = 256 chunks of 16 B: 4 per lane (wave-private region: no barrier, the wave's own LDS ops are ordered)
-#pragma unroll
-    for (int h = 0; h < 4; ++h) {
-      const int c = lane + 64 * h, row = c >> 3, ch = c & 7;
-      const uint4_t v = *(const uint4_t *)(ep + row * 72 + ch * 8);
-      const int m = m0 + wm * WROWS + a * 32 + row;
-      if (m < p.M) *(uint4_t *)((half_t *)Py + (size_t)m * PN + n0 + wn * 64 + ch * 8) = v;
-    }
-  }
+#include "tile256_body.inc"  // matrix waves, split-K hand-off, epilogue
 }
 
 // round 7: single strip-major 4-bit layers whose last 128-column tile is half wide (N % 128 == 64: Falcon-7B); the 4-bit row-stream
@@ -537,13 +315,12 @@ int launch_bf16_to_f16(const void *src, void *dst, size_t n, hipStream_t stream)
 
 template <int LAYOUT, int MW, bool PRIO = true, bool BF = false>
 static int launch_gemm3_b(const GemmParams &p, hipStream_t stream) {
-  using namespace g3;
+  using namespace tile256;
   static DeviceLatch attr_done;
   if (int rc = lds_optin(attr_done, (const void *)gemm3_kernel<LAYOUT, MW, PRIO, BF>)) return rc;
   const int tiles_all = p.n_prob > 1 ? p.total_tiles : ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
   const int tiles = p.tail_split > 1 ? p.tail_from + (tiles_all - p.tail_from) * p.tail_split : tiles_all * p.split_k;
-  const size_t lds = (size_t)(3 * kATile + 2 * kBTile) * sizeof(half_t);  // 128 KB
-  hipLaunchKernelGGL((gemm3_kernel<LAYOUT, MW, PRIO, BF>), dim3(tiles), dim3((MW + 4) * 64), lds, stream, p);
+  hipLaunchKernelGGL((gemm3_kernel<LAYOUT, MW, PRIO, BF>), dim3(tiles), dim3((MW + 4) * 64), kLdsBytes, stream, p);
   QLLM_HIP_CHECK(hipGetLastError());
   return QLLM_OK;
 }

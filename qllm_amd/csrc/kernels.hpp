@@ -223,7 +223,7 @@ BitPanelGeom bitpanel_geometry(const qllm_weight_t &w, int M, size_t ws_bytes);
 int launch_bitpanel(const BitPanelParams &p, const BitPanelGeom &g, hipStream_t stream);
 
 // ---- bitgemm.hip: fused prefill GEMM (129 rows and up) for every width 2..8 on the row-stream layouts in place -- gemm3's 256 x 128 x 64
-// tile with unit-owning dequant waves; reached through qllm_linear_forward_bitgemm only (no planner route) ------------------------------
+// tile (tile256.hpp, tile256_body.inc: shared text) with unit-owning dequant waves; reached through qllm_linear_forward_bitgemm only ----
 constexpr int kBitGemmMinM = 129;
 struct BitGemmParams {
   const void *x;  // fp16
@@ -359,7 +359,7 @@ int panel_split_k(int M, int n_panels, int K);
 size_t panel_slab_bytes(int M, int n_panels, int S);
 int launch_panel(const PanelParams &p, hipStream_t stream);
 
-// ---- gemm3.hip (256x128 tile, 4 matrix waves + 4 staging waves; no split-K) ---------------------------------------------
+// ---- gemm3.hip (256x128 tile, 8 or 4 matrix waves + 4 staging waves; tile256.hpp, tile256_body.inc: shared with bitgemm.hip) ----------
 constexpr int kGemm3Rows3Bit = 100;  // `layout` value for launch_gemm3 / gemm3_ok: GPTQ / HQQ row stream with 3-bit weights
 bool gemm3_ok(const GemmParams &p, int layout);
 bool gemm3_n_tail(const GemmParams &p, int layout);  // round 7: a strip-major 4-bit layer with N % 128 == 64 (half-wide last column tile)

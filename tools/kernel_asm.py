@@ -32,6 +32,25 @@ def asm_text(src):
         return f.read()
 
 
+_SCALAR_KEPT = re.compile(r"s_(waitcnt|barrier|setprio|sleep|endpgm|branch|cbranch)")
+
+
+def vector_lines(text):
+    """The lines of an assembly text that a change of scalar bookkeeping cannot move: scalar-ALU / scalar-memory lines are dropped
+    (waits, barriers, priority, sleep, end and branches stay), scalar register numbers are masked (s12 -> sR, s[4:5] -> s[R]) and so
+    is the per-build __hip_cuid_ symbol; lines that are only an assembler comment go too (code sizes, register totals, and the
+    `; sched_barrier` marks, which stand for no instruction).  Vector, LDS, MFMA, memory, wait, barrier, priority and branch lines
+    stay as they are, vector register numbers included: two builds of a kernel whose lists are equal differ in the scalar unit's
+    work only."""
+    out = []
+    for line in text.splitlines():
+        op = line.split()[0] if line.strip() else ""
+        if "__hip_cuid_" in line or op.startswith(";") or (op.startswith("s_") and not _SCALAR_KEPT.match(op)):
+            continue
+        out.append(re.sub(r"\bs\[\d+:\d+\]", "s[R]", re.sub(r"\bs\d+\b", "sR", line)))
+    return out
+
+
 def parse(text, fields=FIELDS):
     """{kernel name: {field: int}} from the amdhsa.kernels metadata of an assembly text."""
     res = {}
