@@ -472,6 +472,28 @@ int qllm_linear_forward_residual(const qllm_weight_t *w, const void *x, const vo
  * ("residual strip1 nw=8 round=16 exact grid=strips x 1 layout=strip-major"), or "refused: " and the refusal text.  Pure host code. */
 int qllm_residual_describe(const qllm_weight_t *w, int32_t M, int32_t swiglu, char *buf, size_t buflen);
 
+/* ---- rotary position embedding of q and k ------------------------------------------------------------------------------------------------ */
+/* q_out = q * cos + rotate_half(q) * sin and k_out = k * cos + rotate_half(k) * sin, rotate_half(x) = cat(-x2, x1) of the two halves of
+ * a head (the Llama / Mistral / Qwen2 convention: column d pairs with d + head_dim / 2), for both tensors in ONE launch (csrc/rope.hip;
+ * the eager expression is ten elementwise kernels).  The arithmetic is the eager expression's, rounding for rounding, in act_dtype
+ * (QLLM_F16 / QLLM_BF16): a = round(x * c), b = round(r * s), out = round(float(a) + float(b)) with r = -x2 for the first half and x1
+ * for the second -- bit for bit what transformers' apply_rotary_pos_emb returns.
+ * rows = batch * sequence tokens.  q: element (row, head, d) at q + row * q_row_stride + head * q_head_stride + d (strides in elements:
+ * a view into a wider buffer is served); k likewise with k_heads heads (k_heads != q_heads: grouped-query attention).  q_out / k_out:
+ * contiguous [rows, heads, head_dim].  cos / sin: contiguous [cos_rows, head_dim]; row r reads row r % cos_rows, so one [S, D] table
+ * broadcast over a batch and a [B * S, D] table are both served.  An output may be its input when the strides agree (q_row_stride ==
+ * q_heads * head_dim, q_head_stride == head_dim): each thread reads everything it needs before it writes.  k == NULL, k_out == NULL and
+ * k_heads == 0 serve q alone.
+ * QLLM_ERR_INVALID: a NULL q / cos / sin / q_out, k / k_out not matching k_heads, rows / q_heads / head_dim < 1, a bad act_dtype, a
+ * cos_rows that does not divide rows, a pointer that is not 16-byte aligned, a stride that is negative or no multiple of 8.
+ * QLLM_ERR_UNSUPPORTED: head_dim % 16 != 0, head_dim < 16 or head_dim > 256.  Every error is raised before any device work.  No
+ * workspace, no LDS, no host synchronisation; hipGraph-capturable.  Not built: the interleaved (GPT-J) convention, partial rotary,
+ * cos / sin from positions.
+ * ABI: the symbol is ADDITIVE within ABI 7 (QLLM_ABI_VERSION is unchanged): probe for it by symbol. */
+int qllm_rope(const void *q, const void *k, const void *cos, const void *sin, void *q_out, void *k_out, int32_t rows, int32_t q_heads,
+              int32_t k_heads, int32_t head_dim, int64_t q_row_stride, int64_t q_head_stride, int64_t k_row_stride, int64_t k_head_stride,
+              int32_t cos_rows, int32_t act_dtype, void *stream);
+
 /* ---- HQQ quantizer (ABI 7) ---------------------------------------------------------------------------------------------------------- */
 /* W[N,K] (fp16 / bf16 / fp32 by w_dtype, row-major, 16-byte aligned) -> the HQQ layer buffers: qweight i32 [K*bits/32][N], scales f16
  * [K/g][N] = fp16(1/s), zeros f16 [K/g][N] = fp16(z).  The algorithm is HQQQuant.do_quantize's (qllm/quantization/hqq/quant_hqq.py:34-36,

@@ -43,7 +43,7 @@ class QllmDeviceInfo(C.Structure):
 # The C ABI as ctypes sees it: name -> (restype, argtypes).  The ONE list of symbols: EXPORTS (what
 # tests/test_capi_symbols.py holds against include/qllm_mi355x.h) is its keys and _declare() walks it, so no symbol can be exported
 # without argtypes -- ctypes would pass its 64-bit pointers as C int.
-vp, i32, sz = C.c_void_p, C.c_int32, C.c_size_t
+vp, i32, i64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t
 wp = C.POINTER(QllmWeight)
 SIGNATURES = {
     "qllm_abi_version": (C.c_int, []),
@@ -105,6 +105,7 @@ SIGNATURES = {
     "qllm_rmsnorm_describe": (C.c_int, [wp, i32, i32, C.c_char_p, sz]),
     "qllm_linear_forward_residual": (C.c_int, [wp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "qllm_residual_describe": (C.c_int, [wp, i32, i32, C.c_char_p, sz]),
+    "qllm_rope": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i64, i64, i64, i64, i32, i32, vp]),
 }
 EXPORTS = tuple(SIGNATURES)
 

@@ -989,6 +989,34 @@ int qllm_rmsnorm_describe(const qllm_weight_t *w, int32_t n_weights, int32_t M, 
   return describe_fused("rmsnorm", d, w, n_weights, M, buf, buflen);
 }
 
+// q_out = q * cos + rotate_half(q) * sin, k_out likewise: the rotary embedding of q and k in one launch (rope.hip)
+int qllm_rope(const void *q, const void *k, const void *cos, const void *sin, void *q_out, void *k_out, int32_t rows, int32_t q_heads, int32_t k_heads,
+              int32_t head_dim, int64_t q_row_stride, int64_t q_head_stride, int64_t k_row_stride, int64_t k_head_stride, int32_t cos_rows,
+              int32_t act_dtype, void *stream) {
+  clear_error();
+  if (!q || !cos || !sin || !q_out) return set_error(QLLM_ERR_INVALID, "q / cos / sin / q_out must not be NULL");
+  if (k_heads < 0 || (k_heads == 0) != (k == nullptr) || (k_heads == 0) != (k_out == nullptr))
+    return set_error(QLLM_ERR_INVALID, "k and k_out must not be NULL with k_heads >= 1, and both NULL with k_heads == 0 (got k_heads=%d)", k_heads);
+  if (rows <= 0 || q_heads <= 0 || head_dim <= 0)
+    return set_error(QLLM_ERR_INVALID, "rows, q_heads and head_dim must be >= 1 (got rows=%d q_heads=%d head_dim=%d)", rows, q_heads, head_dim);
+  if (act_dtype != QLLM_F16 && act_dtype != QLLM_BF16) return set_error(QLLM_ERR_INVALID, "act_dtype must be QLLM_F16 or QLLM_BF16");
+  if (cos_rows <= 0 || rows % cos_rows != 0) return set_error(QLLM_ERR_INVALID, "cos_rows must be >= 1 and divide rows (got cos_rows=%d rows=%d)", cos_rows, rows);
+  if ((uintptr_t)q % 16 || (uintptr_t)k % 16 || (uintptr_t)cos % 16 || (uintptr_t)sin % 16 || (uintptr_t)q_out % 16 || (uintptr_t)k_out % 16)
+    return set_error(QLLM_ERR_INVALID, "q / k / cos / sin / q_out / k_out must be 16-byte aligned");
+  const int64_t strides[4] = {q_row_stride, q_head_stride, k_row_stride, k_head_stride};
+  for (int i = 0; i < (k ? 4 : 2); ++i)
+    if (strides[i] < 0 || strides[i] % 8 != 0)
+      return set_error(QLLM_ERR_INVALID, "row and head strides must be non-negative multiples of 8 elements (got %lld)", (long long)strides[i]);
+  // an output may BE its input only where both have one layout (a thread then writes what it alone has read)
+  if ((q_out == q && (q_head_stride != head_dim || q_row_stride != (int64_t)q_heads * head_dim)) ||
+      (k && k_out == k && (k_head_stride != head_dim || k_row_stride != (int64_t)k_heads * head_dim)))
+    return set_error(QLLM_ERR_INVALID, "an output may be its input only with contiguous strides (head_stride == head_dim, row_stride == heads * head_dim)");
+  if (head_dim % 16 != 0 || head_dim < 16 || head_dim > kRopeMaxHeadDim)
+    return set_error(QLLM_ERR_UNSUPPORTED, "rope serves head_dim %% 16 == 0, 16 <= head_dim <= %d (got %d)", kRopeMaxHeadDim, head_dim);
+  return launch_rope(q, k, cos, sin, q_out, k_out, rows, q_heads, k_heads, head_dim, q_row_stride, q_head_stride, k_row_stride, k_head_stride, cos_rows,
+                     act_dtype == QLLM_BF16, (hipStream_t)stream);
+}
+
 int qllm_dequant(const qllm_weight_t *w, void *out, int32_t out_dtype, int32_t out_transposed, void *stream) {
   clear_error();
   int rc = validate_weight(w);

@@ -277,6 +277,11 @@ int launch_strip1_swiglu_resid(const Strip1Params &p, int nw, int maxs, int n_st
 constexpr int kRmsNormMaxK = 65536;
 int launch_rmsnorm(const void *x, const void *weight, void *y, int M, int K, float eps, int act_bf16, float *rstd_out, hipStream_t stream);
 
+// ---- rope.hip: q * cos + rotate_half(q) * sin for q and k in one launch (the Llama convention: column d pairs with d + head_dim / 2) -----
+constexpr int kRopeMaxHeadDim = 256;
+int launch_rope(const void *q, const void *k, const void *cos, const void *sin, void *q_out, void *k_out, int rows, int q_heads, int k_heads, int head_dim,
+                int64_t q_row_stride, int64_t q_head_stride, int64_t k_row_stride, int64_t k_head_stride, int cos_rows, int act_bf16, hipStream_t stream);
+
 // ---- native.hip (reference layouts <-> the strip-major native layout) -------------------------------------------------------
 int launch_repack_native(const qllm_weight_t &src, int zero_kind, void *qweight_out, void *scales_out, void *qzeros_out, hipStream_t stream);
 int launch_unpack_native(const qllm_weight_t &src, int dst_layout, void *qweight_out, void *scales_out, void *qzeros_out, hipStream_t stream);

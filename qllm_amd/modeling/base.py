@@ -141,13 +141,16 @@ def release_reference_layouts(model: torch.nn.Module, on: bool = True) -> int:
 
 
 def load_quantized(model_dir: str, device: Optional[str] = "cuda", torch_dtype: Optional[torch.dtype] = None,
-                   release_reference: bool = True, fuse_mlp: bool = False, fuse_norm: bool = False, fuse_residual: bool = False):
+                   release_reference: bool = True, fuse_mlp: bool = False, fuse_norm: bool = False, fuse_residual: bool = False,
+                   fuse_rope: bool = False):
     """Local equivalent of AutoQuantizedModelForCausalLM.from_quantized (base.py:226-322).  `release_reference`: see
     release_reference_layouts (QLLM_RELEASE_REFERENCE=0 in the environment keeps both copies).  `fuse_mlp` (opt-in): fold
     act_fn(gate) * up of the SwiGLU MLPs into the down_proj launch (q_layers/fused_mlp.py); model.fused_mlps counts the modules.
     `fuse_norm` (opt-in): fold the decoder layers' RMSNorms into the q/k/v and gate/up launches and run the remaining ones as one
     kernel (q_layers/fused_norm.py); model.fused_norms / model.quant_norms count them.  `fuse_residual` (opt-in): fold the two residual
-    adds of every decoder layer into the o_proj and down_proj launches (q_layers/fused_residual.py); model.fused_residuals counts the layers."""
+    adds of every decoder layer into the o_proj and down_proj launches (q_layers/fused_residual.py); model.fused_residuals counts the layers.
+    `fuse_rope` (opt-in): the rotary embedding of q and k of every attention module as one kernel (q_layers/fused_rope.py);
+    model.fused_ropes counts the modules."""
     import transformers
 
     hf_cfg = transformers.AutoConfig.from_pretrained(model_dir)
@@ -198,6 +201,9 @@ def load_quantized(model_dir: str, device: Optional[str] = "cuda", torch_dtype: 
     if fuse_residual:
         from .q_layers import install_fused_residual
         model.fused_residuals = install_fused_residual(model, [target])
+    if fuse_rope:
+        from .q_layers import install_fused_rope
+        model.fused_ropes = install_fused_rope(model)
     return model.eval()
 
 

@@ -496,6 +496,94 @@ def rmsnorm_describe(ws_desc: Sequence[QllmWeight], m: int) -> str:
     return _describe("qllm_rmsnorm_describe", 768, _array(ws_desc), len(ws_desc), int(m))
 
 
+ROPE_MAX_HEAD_DIM = 256   # kRopeMaxHeadDim of csrc/kernels.hpp
+
+
+def _rope_tokens(t: torch.Tensor, unsqueeze_dim: int) -> torch.Tensor:
+    """The [B, S, H, D] view of a 4-D q / k: `unsqueeze_dim` 1 says [B, H, S, D], 2 says [B, S, H, D]."""
+    return t.transpose(1, 2) if unsqueeze_dim == 1 else t
+
+
+def _rope_strides(t: torch.Tensor, unsqueeze_dim: int, name: str):
+    """(row stride, head stride) in elements of q / k as qllm_rope reads it -- token (b, s) is row b * S + s -- or QllmUnsupported."""
+    b, s, h, d = _rope_tokens(t, unsqueeze_dim).shape
+    sb, ss, sh, sd = _rope_tokens(t, unsqueeze_dim).stride()
+    if sd != 1:
+        raise QllmUnsupported(_lib.QLLM_ERR_UNSUPPORTED, f"rope: the last dimension of {name} must have stride 1 (got {sd})")
+    if s > 1 and b > 1 and sb != s * ss:
+        raise QllmUnsupported(_lib.QLLM_ERR_UNSUPPORTED, f"rope: the tokens of {name} must be rows of one stride (batch stride {sb}, sequence stride {ss} x {s})")
+    row = ss if s > 1 else sb if b > 1 else h * d
+    head = sh if h > 1 else d
+    if row % 8 or head % 8 or row < 0 or head < 0 or t.data_ptr() % 16:
+        raise QllmUnsupported(_lib.QLLM_ERR_UNSUPPORTED, f"rope: {name} must be 16-byte aligned with strides that are multiples of 8 (row {row}, head {head})")
+    # the eager output keeps its input's dimension order (as torch.empty_like does); the kernel writes [tokens, heads, head_dim]
+    order = [st for n, st in zip((b, s, h, d), (sb, ss, sh, sd)) if n > 1]
+    if any(x <= y for x, y in zip(order, order[1:])):
+        raise QllmUnsupported(_lib.QLLM_ERR_UNSUPPORTED, f"rope: {name} is not token-major in memory (strides {tuple(t.stride())}): the eager result would not be either")
+    return row, head
+
+
+def rope_plan(q: torch.Tensor, k: Optional[torch.Tensor], cos: torch.Tensor, sin: torch.Tensor, unsqueeze_dim: int = 1):
+    """What `rope` hands to qllm_rope for these tensors -- (rows, q_heads, k_heads, head_dim, q row / head stride, k row / head stride,
+    cos_rows) -- or QllmUnsupported with the reason: q / k 4-D of one fp16 / bf16 type with cos / sin, [B, H, S, D] (unsqueeze_dim 1) or
+    [B, S, H, D] (2), inner stride 1, tokens at one row stride, 16-byte aligned, strides multiples of 8; D % 16 == 0, 16 <= D <= 256;
+    cos / sin contiguous [B or 1, S, D] (the whole head: no partial rotary); and the eager call's output, which keeps its input's
+    dimension order, token-major -- a head-major [B, H, S, D] input with H, S > 1 is not served.  Pure host code, any device."""
+    def no(why):
+        return QllmUnsupported(_lib.QLLM_ERR_UNSUPPORTED, "rope: " + why)
+    if unsqueeze_dim not in (1, 2):
+        raise no(f"unsqueeze_dim must be 1 ([B, H, S, D]) or 2 ([B, S, H, D]), got {unsqueeze_dim}")
+    ts = [("q", q), ("cos", cos), ("sin", sin)] + ([("k", k)] if k is not None else [])
+    if q.dtype not in (torch.float16, torch.bfloat16) or any(t.dtype != q.dtype for _, t in ts):
+        raise no("q, k, cos and sin must share one type, float16 or bfloat16 (got " + ", ".join(str(t.dtype)[6:] for _, t in ts) + ")")
+    if any(t.device != q.device for _, t in ts):
+        raise no("q, k, cos and sin must be on one device")
+    if q.dim() != 4 or (k is not None and (k.dim() != 4 or _rope_tokens(k, unsqueeze_dim).shape[:2] != _rope_tokens(q, unsqueeze_dim).shape[:2] or k.shape[3] != q.shape[3])):
+        raise no("q and k must be 4-D with the same batch, sequence and head sizes")
+    b, s, hq, d = _rope_tokens(q, unsqueeze_dim).shape
+    hk = _rope_tokens(k, unsqueeze_dim).shape[2] if k is not None else 0
+    if d % 16 or d < 16 or d > ROPE_MAX_HEAD_DIM:
+        raise no(f"head_dim % 16 == 0, 16 <= head_dim <= {ROPE_MAX_HEAD_DIM} (got {d})")
+    if b * s == 0 or hq == 0 or (k is not None and hk == 0):
+        raise no("empty q / k")
+    if cos.shape != sin.shape or cos.dim() != 3 or cos.shape[0] not in (1, b) or tuple(cos.shape[1:]) != (s, d):
+        raise no(f"cos and sin must be [{b} or 1, {s}, {d}] (got {tuple(cos.shape)}, {tuple(sin.shape)})")
+    if not cos.is_contiguous() or not sin.is_contiguous() or cos.data_ptr() % 16 or sin.data_ptr() % 16:
+        raise no("cos and sin must be contiguous and 16-byte aligned")
+    strides = _rope_strides(q, unsqueeze_dim, "q") + (_rope_strides(k, unsqueeze_dim, "k") if k is not None else (0, 0))
+    return (b * s, hq, hk, d) + strides + (cos.shape[0] * s,)
+
+
+def rope(q: torch.Tensor, k: Optional[torch.Tensor], cos: torch.Tensor, sin: torch.Tensor, unsqueeze_dim: int = 1, *, out=None, plan=None):
+    """(q * cos + rotate_half(q) * sin, k * cos + rotate_half(k) * sin) with cos / sin unsqueezed at `unsqueeze_dim`: transformers'
+    apply_rotary_pos_emb (Llama, Mistral, Qwen2) for both tensors in ONE kernel (qllm_rope, csrc/rope.hip), bit for bit, returning tensors
+    of the shape and strides the eager call returns -- for the usual view(B, S, H, D).transpose(1, 2) inputs logical [B, H, S, D] over
+    [B, S, H, D] memory.  `rope_plan` says what is served; everything else raises QllmUnsupported before anything is launched.  k may be
+    None (q alone: returns (q_out, None)).  out: (q_out, k_out) to write into, each of its input's shape, type and device, laid out as
+    the result would be (token-major, dense); an output may be its input when that one is laid out so.  plan: what `rope_plan` returned
+    for these very arguments, for a caller that has asked already."""
+    rows, hq, hk, d, q_row, q_head, k_row, k_head, cos_rows = plan if plan is not None else rope_plan(q, k, cos, sin, unsqueeze_dim)
+    for t in (q, cos, sin) + ((k,) if k is not None else ()):
+        if not t.is_cuda:
+            raise RuntimeError("rope: q, k, cos and sin must be HIP/CUDA tensors (qllm_amd has no CPU forward path)")
+    if out is None:
+        q_out, k_out = torch.empty_like(q), torch.empty_like(k) if k is not None else None
+        if not all(o is None or _rope_tokens(o, unsqueeze_dim).is_contiguous() for o in (q_out, k_out)):
+            raise QllmUnsupported(_lib.QLLM_ERR_UNSUPPORTED, "rope: the eager result of these inputs is not token-major in memory")
+    else:
+        q_out, k_out = out
+        for name, o, t in (("q_out", q_out, q), ("k_out", k_out, k)):
+            if (o is None) != (t is None):
+                raise RuntimeError(f"rope: {name} must be given exactly when its input is")
+            if t is not None and (o.shape != t.shape or o.dtype != t.dtype or o.device != t.device or not _rope_tokens(o, unsqueeze_dim).is_contiguous()):
+                raise RuntimeError(f"rope: {name} must be a {tuple(t.shape)} {t.dtype} tensor on {t.device} that is dense and token-major in memory")
+    with torch.cuda.device(q.device):
+        rc = _lib.load().qllm_rope(q.data_ptr(), _ptr(k), cos.data_ptr(), sin.data_ptr(), q_out.data_ptr(), _ptr(k_out), rows, hq, hk, d,
+                                   q_row, q_head, k_row, k_head, cos_rows, _act_dtype(q), _stream_ptr())
+    _lib.check(rc)
+    return q_out, k_out
+
+
 def dequant(w: QllmWeight, device: torch.device, dtype=torch.float16, transposed: bool = False) -> torch.Tensor:
     """W[K,N] (or [N,K]) bit-identical to the reference's DequantizeLinearBlockWise / unpack()."""
     lib = _lib.load()
