@@ -494,6 +494,52 @@ int qllm_rope(const void *q, const void *k, const void *cos, const void *sin, vo
               int32_t k_heads, int32_t head_dim, int64_t q_row_stride, int64_t q_head_stride, int64_t k_row_stride, int64_t k_head_stride,
               int32_t cos_rows, int32_t act_dtype, void *stream);
 
+/* ---- single-token attention over the KV cache -------------------------------------------------------------------------------------------- */
+/* out = softmax(scaling * q K^T + mask) V for ONE query token per sequence against caches [batch, kv_heads, max_len, head_dim] of which
+ * the first kv_len positions count, in ONE launch (csrc/attn_decode.hip, flash-decoding): a block owns one (batch entry, kv head, split of
+ * the positions) and all q_heads / kv_heads query heads of that kv head, so a K / V row is read once for the whole group; fp32 scores, an
+ * fp32 online softmax, fp32 P.V on the vector ALU, one rounding to act_dtype (QLLM_F16 / QLLM_BF16) at the store.  The splits' (m, l, acc)
+ * go through the workspace; the last block to arrive for a (batch entry, kv head) combines them in split order, so the result is the same
+ * bits on every call.  Splits and grid are functions of (batch, kv_heads, head_dim, max_len) and the device's CU count only -- never of
+ * kv_len: a captured launch serves every length.
+ * q: element (b, head, d) at q + b * q_row_stride + head * q_head_stride + d (strides in elements; a view into a wider buffer is served).
+ * out: contiguous [batch, q_heads, head_dim] -- the row o_proj takes.  Caches: element (b, h, pos, d) at cache + b * cache_batch_stride +
+ * h * cache_head_stride + pos * cache_pos_stride + d, the same three strides for k_cache and v_cache.
+ * Length: kv_len, or with kv_len_dev != NULL the int64 the kernel reads there (clamped to 0..max_len).  Positions >= kv_len are never
+ * loaded.
+ * Append: with k_new / v_new ([batch, kv_heads, head_dim], row and head strides each, as qllm_rope takes them) position kv_len is the new
+ * token: the kernel stores the two rows into the caches and attends over kv_len + 1 positions.  With the length on the device kv_len + 1 >
+ * max_len cannot be refused here: the kernel then stores nothing and attends over the first max_len positions of the cache.
+ * Mask: one row per batch entry, element (b, pos) at mask + b * mask_batch_stride + pos, pos < mask_len; QLLM_ATTN_MASK_BOOL: bytes, non-zero
+ * = visible; QLLM_ATTN_MASK_ADDITIVE: act_dtype values added to the scaled score, a value <= the type's lowest finite number hides the key as
+ * a zero byte does (in bf16 a finite bias below about -7e29 that is not that low gets weight 0 against the floor -1e30 the running maximum
+ * starts from: a row whose visible keys all carry such a bias stores zeros, not a softmax among them).  It must cover kv_len (+ 1 with an
+ * append) positions, max_len with the length on the device.  A row with no visible key stores zeros.
+ * Workspace: qllm_attn_decode_workspace_bytes, 16-byte aligned, its counter page zero-filled once (qllm_workspace_init); every call leaves
+ * it zero.  QLLM_ERR_INVALID: a NULL q / cache / out, sizes < 1, kv_heads not dividing q_heads, a bad act_dtype or mask_kind, a mask
+ * pointer not matching mask_kind, only one of k_new / v_new, a data pointer off 16 bytes, a stride that is negative or no multiple of 8,
+ * a host kv_len outside 0..max_len (kv_len + 1 > max_len with an append), a mask too short.  QLLM_ERR_UNSUPPORTED: head_dim other than
+ * 64 / 128, more than 8 query heads per kv head, batch * kv_heads > 4096.  QLLM_ERR_WORKSPACE: a missing, misaligned or small
+ * workspace.  Every error is raised before any device work.  No host synchronisation; hipGraph-capturable.
+ * Not built: prefill (more than one query token), sliding-window, quantized and paged caches, per-sequence lengths other than through the
+ * mask, rotary inside the kernel, an fp8 cache.
+ * ABI: the symbols are ADDITIVE within ABI 7 (QLLM_ABI_VERSION is unchanged): probe for them by symbol. */
+#define QLLM_ATTN_MASK_NONE 0
+#define QLLM_ATTN_MASK_BOOL 1
+#define QLLM_ATTN_MASK_ADDITIVE 2
+int qllm_attn_decode(const void *q, const void *k_new, const void *v_new, void *k_cache, void *v_cache, const void *mask, void *out, int32_t batch,
+                     int32_t q_heads, int32_t kv_heads, int32_t head_dim, int64_t kv_len, const int64_t *kv_len_dev, int64_t max_len, int64_t q_row_stride,
+                     int64_t q_head_stride, int64_t k_new_row_stride, int64_t k_new_head_stride, int64_t v_new_row_stride, int64_t v_new_head_stride,
+                     int64_t cache_batch_stride, int64_t cache_head_stride, int64_t cache_pos_stride, int32_t mask_kind, int64_t mask_len,
+                     int64_t mask_batch_stride, float scaling, int32_t act_dtype, void *workspace, size_t workspace_bytes, void *stream);
+/* The workspace qllm_attn_decode needs: the counter page and the splits' partial results.  Pure host code; shapes the entry refuses need
+ * the page alone. */
+size_t qllm_attn_decode_workspace_bytes(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int64_t max_len);
+/* What a call would launch, as text: "attn_decode tile=64 splits=16 chunk=256 grid=16x32x1 group=1 combine=last-block" (tile: positions per
+ * block step; chunk: positions per split, a multiple of the tile; split s owns positions s * chunk .. (s + 1) * chunk - 1), or "refused: "
+ * and the refusal text.  Pure host code. */
+int qllm_attn_decode_describe(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int64_t max_len, char *buf, size_t buflen);
+
 /* ---- HQQ quantizer (ABI 7) ---------------------------------------------------------------------------------------------------------- */
 /* W[N,K] (fp16 / bf16 / fp32 by w_dtype, row-major, 16-byte aligned) -> the HQQ layer buffers: qweight i32 [K*bits/32][N], scales f16
  * [K/g][N] = fp16(1/s), zeros f16 [K/g][N] = fp16(z).  The algorithm is HQQQuant.do_quantize's (qllm/quantization/hqq/quant_hqq.py:34-36,

@@ -19,6 +19,7 @@ DT_F16, DT_BF16, DT_F16_IN_BF16_OUT, DT_F32 = 0, 1, 2, 3
 ABI_VERSION = 7
 BITPANEL_MAX_M_DEFAULT = 256   # QLLM_BITPANEL_MAX_M_DEFAULT of include/qllm_mi355x.h: the measured line of profiles/bitpanel.md (0: modules do not route)
 BITGEMM_MIN_M_DEFAULT = 0      # QLLM_BITGEMM_MIN_M_DEFAULT of include/qllm_mi355x.h: the measured line of profiles/bitgemm.md (0: modules do not route)
+ATTN_MASK_NONE, ATTN_MASK_BOOL, ATTN_MASK_ADDITIVE = 0, 1, 2   # QLLM_ATTN_MASK_* of include/qllm_mi355x.h (qllm_attn_decode)
 ACT_SILU = 0                   # QLLM_ACT_SILU of include/qllm_mi355x.h (qllm_linear_forward_swiglu)
 BITGROUP_MAX_M_DEFAULT = 16    # QLLM_BITGROUP_MAX_M_DEFAULT of include/qllm_mi355x.h: the measured line of profiles/bitgemv_group.md (0: sibling groups do not route)
 
@@ -106,6 +107,10 @@ SIGNATURES = {
     "qllm_linear_forward_residual": (C.c_int, [wp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "qllm_residual_describe": (C.c_int, [wp, i32, i32, C.c_char_p, sz]),
     "qllm_rope": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i64, i64, i64, i64, i32, i32, vp]),
+    "qllm_attn_decode": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i64, vp, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, i32, i64, i64,
+                                   C.c_float, i32, vp, sz, vp]),
+    "qllm_attn_decode_workspace_bytes": (sz, [i32, i32, i32, i32, i64]),
+    "qllm_attn_decode_describe": (C.c_int, [i32, i32, i32, i32, i64, C.c_char_p, sz]),
 }
 EXPORTS = tuple(SIGNATURES)
 

@@ -1017,6 +1017,88 @@ int qllm_rope(const void *q, const void *k, const void *cos, const void *sin, vo
                      act_dtype == QLLM_BF16, (hipStream_t)stream);
 }
 
+// ---- single-token attention over the KV cache (attn_decode.hip) ------------------------------------------------------------------------
+// the shape checks the three entries share: sizes, the head ratio, then what the kernel is built for
+static int check_attn_decode_shape(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int64_t max_len) {
+  if (batch <= 0 || q_heads <= 0 || kv_heads <= 0 || head_dim <= 0 || max_len <= 0)
+    return set_error(QLLM_ERR_INVALID, "batch, q_heads, kv_heads, head_dim and max_len must be >= 1 (got %d, %d, %d, %d, %lld)", batch, q_heads, kv_heads,
+                     head_dim, (long long)max_len);
+  if (q_heads % kv_heads != 0) return set_error(QLLM_ERR_INVALID, "kv_heads must divide q_heads (got q_heads=%d kv_heads=%d)", q_heads, kv_heads);
+  return QLLM_OK;
+}
+static int check_attn_decode_served(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim) {
+  if (head_dim != 64 && head_dim != 128) return set_error(QLLM_ERR_UNSUPPORTED, "attn_decode serves head_dim 64 and 128 (got %d)", head_dim);
+  if (q_heads / kv_heads > kAttnDecodeMaxGroup)
+    return set_error(QLLM_ERR_UNSUPPORTED, "attn_decode serves 1..%d query heads per kv head (got %d)", kAttnDecodeMaxGroup, q_heads / kv_heads);
+  if (batch > 65535 || kv_heads > 65535 || (int64_t)batch * kv_heads > (int64_t)(kCounterBytes / sizeof(int)))
+    return set_error(QLLM_ERR_UNSUPPORTED, "attn_decode serves batch * kv_heads <= %d (got %lld)", (int)(kCounterBytes / sizeof(int)), (long long)batch * kv_heads);
+  return QLLM_OK;
+}
+
+size_t qllm_attn_decode_workspace_bytes(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int64_t max_len) {
+  const bool refused = check_attn_decode_shape(batch, q_heads, kv_heads, head_dim, max_len) != QLLM_OK ||
+                       check_attn_decode_served(batch, q_heads, kv_heads, head_dim) != QLLM_OK;
+  clear_error();
+  return refused ? kCounterBytes : kCounterBytes + attn_decode_geom(batch, q_heads, kv_heads, head_dim, max_len).partial_bytes;
+}
+
+int qllm_attn_decode_describe(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int64_t max_len, char *buf, size_t buflen) {
+  clear_error();
+  if (!buf || buflen == 0) return set_error(QLLM_ERR_INVALID, "buf must not be NULL or empty");
+  int rc = check_attn_decode_shape(batch, q_heads, kv_heads, head_dim, max_len);
+  if (rc == QLLM_OK) rc = check_attn_decode_served(batch, q_heads, kv_heads, head_dim);
+  if (rc != QLLM_OK) return describe_refusal(rc, kRefused, buf, buflen);
+  const AttnDecodeGeom g = attn_decode_geom(batch, q_heads, kv_heads, head_dim, max_len);
+  snprintf(buf, buflen, "attn_decode tile=%d splits=%d chunk=%lld grid=%dx%dx%d group=%d combine=last-block", g.tile, g.splits, (long long)g.chunk, g.splits,
+           kv_heads, batch, q_heads / kv_heads);
+  return QLLM_OK;
+}
+
+int qllm_attn_decode(const void *q, const void *k_new, const void *v_new, void *k_cache, void *v_cache, const void *mask, void *out, int32_t batch,
+                     int32_t q_heads, int32_t kv_heads, int32_t head_dim, int64_t kv_len, const int64_t *kv_len_dev, int64_t max_len, int64_t q_row_stride,
+                     int64_t q_head_stride, int64_t k_new_row_stride, int64_t k_new_head_stride, int64_t v_new_row_stride, int64_t v_new_head_stride,
+                     int64_t cache_batch_stride, int64_t cache_head_stride, int64_t cache_pos_stride, int32_t mask_kind, int64_t mask_len,
+                     int64_t mask_batch_stride, float scaling, int32_t act_dtype, void *workspace, size_t workspace_bytes, void *stream) {
+  clear_error();
+  if (!q || !k_cache || !v_cache || !out) return set_error(QLLM_ERR_INVALID, "q / k_cache / v_cache / out must not be NULL");
+  int rc = check_attn_decode_shape(batch, q_heads, kv_heads, head_dim, max_len);
+  if (rc != QLLM_OK) return rc;
+  if (act_dtype != QLLM_F16 && act_dtype != QLLM_BF16) return set_error(QLLM_ERR_INVALID, "act_dtype must be QLLM_F16 or QLLM_BF16");
+  if (mask_kind != QLLM_ATTN_MASK_NONE && mask_kind != QLLM_ATTN_MASK_BOOL && mask_kind != QLLM_ATTN_MASK_ADDITIVE)
+    return set_error(QLLM_ERR_INVALID, "mask_kind must be QLLM_ATTN_MASK_NONE, _BOOL or _ADDITIVE (got %d)", mask_kind);
+  if ((mask_kind == QLLM_ATTN_MASK_NONE) != (mask == nullptr)) return set_error(QLLM_ERR_INVALID, "mask must be NULL exactly with QLLM_ATTN_MASK_NONE");
+  if ((k_new == nullptr) != (v_new == nullptr)) return set_error(QLLM_ERR_INVALID, "k_new and v_new must be given together or not at all");
+  if ((uintptr_t)q % 16 || (uintptr_t)k_new % 16 || (uintptr_t)v_new % 16 || (uintptr_t)k_cache % 16 || (uintptr_t)v_cache % 16 || (uintptr_t)out % 16)
+    return set_error(QLLM_ERR_INVALID, "q / k_new / v_new / k_cache / v_cache / out must be 16-byte aligned");
+  if ((uintptr_t)kv_len_dev % 8 || (mask_kind == QLLM_ATTN_MASK_ADDITIVE && (uintptr_t)mask % 2))
+    return set_error(QLLM_ERR_INVALID, "kv_len_dev must be 8-byte aligned and an additive mask 2-byte aligned");
+  const int64_t strides[9] = {q_row_stride, q_head_stride, cache_batch_stride, cache_head_stride, cache_pos_stride,
+                              k_new_row_stride, k_new_head_stride, v_new_row_stride, v_new_head_stride};
+  for (int i = 0; i < (k_new ? 9 : 5); ++i)
+    if (strides[i] < 0 || strides[i] % 8 != 0)
+      return set_error(QLLM_ERR_INVALID, "row, head, batch and position strides must be non-negative multiples of 8 elements (got %lld)", (long long)strides[i]);
+  const int64_t need_len = kv_len_dev ? max_len : kv_len + (k_new ? 1 : 0);  // the positions a call may reach
+  if (!kv_len_dev && (kv_len < 0 || need_len > max_len))
+    return set_error(QLLM_ERR_INVALID, "kv_len%s must lie in 0..max_len (got kv_len=%lld max_len=%lld)", k_new ? " + 1 (append)" : "", (long long)kv_len, (long long)max_len);
+  if (mask && (mask_len < need_len || mask_batch_stride < 0))
+    return set_error(QLLM_ERR_INVALID, "the mask must cover %lld positions (%s) with a non-negative batch stride (got mask_len=%lld stride=%lld)", (long long)need_len,
+                     kv_len_dev ? "max_len: the length is on the device" : "kv_len, + 1 with an append", (long long)mask_len, (long long)mask_batch_stride);
+  rc = check_attn_decode_served(batch, q_heads, kv_heads, head_dim);
+  if (rc != QLLM_OK) return rc;
+  const AttnDecodeGeom g = attn_decode_geom(batch, q_heads, kv_heads, head_dim, max_len);
+  rc = check_workspace("qllm_attn_decode", workspace, workspace_bytes, kCounterBytes + g.partial_bytes);
+  if (rc != QLLM_OK) return rc;
+
+  AttnDecodeParams p;
+  p.q = q, p.k_new = k_new, p.v_new = v_new, p.k_cache = k_cache, p.v_cache = v_cache, p.mask = mask, p.out = out;
+  p.kv_len_dev = kv_len_dev, p.kv_len = kv_len, p.max_len = max_len;
+  p.q_row = q_row_stride, p.q_head = q_head_stride, p.kn_row = k_new_row_stride, p.kn_head = k_new_head_stride, p.vn_row = v_new_row_stride,
+  p.vn_head = v_new_head_stride, p.c_batch = cache_batch_stride, p.c_head = cache_head_stride, p.c_pos = cache_pos_stride, p.mask_batch = mask_batch_stride;
+  p.chunk = g.chunk, p.batch = batch, p.q_heads = q_heads, p.kv_heads = kv_heads, p.mask_kind = mask_kind, p.splits = g.splits, p.scaling = scaling;
+  carve(workspace, &p.counters, &p.partials);
+  return launch_attn_decode(p, head_dim, act_dtype == QLLM_BF16, (hipStream_t)stream);
+}
+
 int qllm_dequant(const qllm_weight_t *w, void *out, int32_t out_dtype, int32_t out_transposed, void *stream) {
   clear_error();
   int rc = validate_weight(w);

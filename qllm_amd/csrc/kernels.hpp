@@ -282,6 +282,31 @@ constexpr int kRopeMaxHeadDim = 256;
 int launch_rope(const void *q, const void *k, const void *cos, const void *sin, void *q_out, void *k_out, int rows, int q_heads, int k_heads, int head_dim,
                 int64_t q_row_stride, int64_t q_head_stride, int64_t k_row_stride, int64_t k_head_stride, int cos_rows, int act_bf16, hipStream_t stream);
 
+// ---- attn_decode.hip: one query token per sequence against the first kv_len positions of a KV cache (flash-decoding) ---------------------
+constexpr int kAttnDecodeMaxGroup = 8;    // query heads per kv head
+constexpr int kAttnDecodeMaxSplits = 32;  // blocks per (batch entry, kv head)
+struct AttnDecodeParams {
+  const void *q, *k_new, *v_new;  // k_new / v_new: both or neither (append)
+  void *k_cache, *v_cache;
+  const void *mask;               // mask_kind 0: none; 1: bool bytes; 2: additive, activation type
+  void *out;
+  const int64_t *kv_len_dev;      // NULL: kv_len
+  int64_t kv_len, max_len;
+  int64_t q_row, q_head, kn_row, kn_head, vn_row, vn_head, c_batch, c_head, c_pos, mask_batch;  // strides in elements
+  int64_t chunk;                  // positions per split
+  int batch, q_heads, kv_heads, mask_kind, splits;
+  float scaling;
+  float *partials;                // [batch * kv_heads][splits][G][4 + head_dim] fp32: m, l, two pads, acc
+  int *counters;                  // one arrival counter per (batch entry, kv head) (zero before and after the launch)
+};
+struct AttnDecodeGeom {
+  int tile, splits;
+  int64_t chunk;
+  size_t partial_bytes;
+};
+AttnDecodeGeom attn_decode_geom(int batch, int q_heads, int kv_heads, int head_dim, int64_t max_len);
+int launch_attn_decode(const AttnDecodeParams &p, int head_dim, int act_bf16, hipStream_t stream);
+
 // ---- native.hip (reference layouts <-> the strip-major native layout) -------------------------------------------------------
 int launch_repack_native(const qllm_weight_t &src, int zero_kind, void *qweight_out, void *scales_out, void *qzeros_out, hipStream_t stream);
 int launch_unpack_native(const qllm_weight_t &src, int dst_layout, void *qweight_out, void *scales_out, void *qzeros_out, hipStream_t stream);

@@ -142,7 +142,7 @@ def release_reference_layouts(model: torch.nn.Module, on: bool = True) -> int:
 
 def load_quantized(model_dir: str, device: Optional[str] = "cuda", torch_dtype: Optional[torch.dtype] = None,
                    release_reference: bool = True, fuse_mlp: bool = False, fuse_norm: bool = False, fuse_residual: bool = False,
-                   fuse_rope: bool = False):
+                   fuse_rope: bool = False, fuse_attention: bool = False):
     """Local equivalent of AutoQuantizedModelForCausalLM.from_quantized (base.py:226-322).  `release_reference`: see
     release_reference_layouts (QLLM_RELEASE_REFERENCE=0 in the environment keeps both copies).  `fuse_mlp` (opt-in): fold
     act_fn(gate) * up of the SwiGLU MLPs into the down_proj launch (q_layers/fused_mlp.py); model.fused_mlps counts the modules.
@@ -150,7 +150,8 @@ def load_quantized(model_dir: str, device: Optional[str] = "cuda", torch_dtype: 
     kernel (q_layers/fused_norm.py); model.fused_norms / model.quant_norms count them.  `fuse_residual` (opt-in): fold the two residual
     adds of every decoder layer into the o_proj and down_proj launches (q_layers/fused_residual.py); model.fused_residuals counts the layers.
     `fuse_rope` (opt-in): the rotary embedding of q and k of every attention module as one kernel (q_layers/fused_rope.py);
-    model.fused_ropes counts the modules."""
+    model.fused_ropes counts the modules.  `fuse_attention` (opt-in): the attention core of a decode step -- one query token against the KV
+    cache -- as one kernel that reads only the valid keys (q_layers/fused_attention.py); model.fused_attentions counts the modules."""
     import transformers
 
     hf_cfg = transformers.AutoConfig.from_pretrained(model_dir)
@@ -204,6 +205,9 @@ def load_quantized(model_dir: str, device: Optional[str] = "cuda", torch_dtype: 
     if fuse_rope:
         from .q_layers import install_fused_rope
         model.fused_ropes = install_fused_rope(model)
+    if fuse_attention:
+        from .q_layers import install_fused_attention
+        model.fused_attentions = install_fused_attention(model)
     return model.eval()
 
 

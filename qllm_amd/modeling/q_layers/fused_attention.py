@@ -1,0 +1,120 @@
+"""The attention core of a decode step -- one query token against the KV cache -- as one kernel.
+
+Per layer and token transformers runs `past_key_values.update` (torch.cat of the whole K and V on a DynamicCache; arange, add, add_ and two
+index_copy_ on a StaticCache) and sdpa or the eager matmul / softmax / matmul over what `update` returned: with a StaticCache all
+max_cache_len positions behind a mask.  `ops.attn_decode` (qllm_attn_decode, csrc/attn_decode.hip) reads only the valid keys, each K / V
+row once for all query heads of its group, and takes the length from device memory when the cache is static.
+
+`install_fused_attention` gives each whitelisted attention INSTANCE the restated forward of fused_rope.py (one text for both installs: the
+class's data flow, no transformers global touched) with `_fused_core` behind the rotary embedding.  The core serves a call when q_len == 1,
+q / k / v are device tensors of one fp16 / bf16 type, nothing is being differentiated, the module is not training, the attention
+implementation is sdpa or eager, no sliding window reaches the call, no kwarg changes the mathematics, the mask is None or one of the two
+forms transformers builds at q_len == 1 ([B, 1, 1, L] bool or additive), the cache layer is EXACTLY a DynamicLayer or an initialised
+StaticLayer of a cache that does not offload, and `ops.attn_decode_plan` serves the shapes:
+
+  DynamicLayer  `update` as before, then the kernel over what it returned with the host length.
+  StaticLayer   `update` as before, then the kernel over the layer's buffers with the length read from `layer.cumulative_length` on the
+                device: the valid positions, not max_cache_len.  (The append form of the kernel -- two launches instead of update's five
+                -- needs a host-side bound on the length that holds across `reset`, `crop` and foreign updates of the layer; it is not
+                used here.)
+
+Everything else -- prefill, sliding layers, quantized and offloaded caches, no cache, CPU and fp32 tensors, training, output_attentions --
+runs the family's own route unchanged.  Composes with install_fused_rope and the other installs in any order.
+Opt-in: `load_quantized(..., fuse_attention=True)`."""
+from __future__ import annotations
+
+import os
+from typing import Iterable, Optional
+
+import torch
+
+from ... import ops
+from .fused_norm import ATTENTION_TYPES
+from .fused_rope import _ACT_DTYPES, _CORE, _known, _patch, _unpatch
+
+# kwargs the decoder layers pass on that do not change what the attention computes; any other one must be None or False
+_BENIGN = ("position_ids", "cache_position", "use_cache", "output_hidden_states", "return_dict", "is_causal")
+
+
+def _on_device(*ts) -> bool:
+    return all(t.is_cuda for t in ts)
+
+
+def _layer_of(past_key_values, layer_idx):
+    """The cache layer the core may serve -- exactly a DynamicLayer or an initialised StaticLayer of a cache that does not offload --
+    else None."""
+    from transformers.cache_utils import DynamicLayer, StaticLayer
+    layers = getattr(past_key_values, "layers", None)
+    if not isinstance(layers, list) or not isinstance(layer_idx, int) or not 0 <= layer_idx < len(layers) or getattr(past_key_values, "offloading", False):
+        return None
+    layer = layers[layer_idx]
+    if type(layer) is DynamicLayer:
+        return layer
+    if type(layer) is StaticLayer and layer.is_initialized:
+        return layer
+    return None
+
+
+def _fused_core(self, q, k, v, attention_mask, past_key_values, kwargs, window):
+    """(the attention output [B, Hq, D] or None, key states, value states, whether the cache has been updated) of one forward: the kernel
+    where the conditions of this file's docstring hold, else None and the states for the family's route."""
+    no = (None, k, v, False)
+    if q.shape[2] != 1 or past_key_values is None or self.training or self.config._attn_implementation not in ("sdpa", "eager"):
+        return no
+    if q.dtype not in _ACT_DTYPES or k.dtype != q.dtype or v.dtype != q.dtype or not _on_device(q, k, v):
+        return no
+    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+        return no
+    sliding = getattr(self.config, "sliding_window", None) if window == "config" else getattr(self, "sliding_window", None) if window == "self" else None
+    if sliding is not None or any(val is not None and val is not False for name, val in kwargs.items() if name not in _BENIGN):
+        return no
+    if attention_mask is not None and not (isinstance(attention_mask, torch.Tensor) and attention_mask.dim() == 4 and attention_mask.shape[1] == 1
+                                           and attention_mask.shape[2] == 1 and (attention_mask.dtype == torch.bool or attention_mask.dtype == q.dtype)):
+        return no
+    layer = _layer_of(past_key_values, self.layer_idx)
+    if layer is None:
+        return no
+    static = hasattr(layer, "cumulative_length")
+    if static and (layer.keys.dtype != q.dtype or layer.keys.shape[0] != q.shape[0] or layer.keys.shape[3] != q.shape[3]):
+        return no
+    keys, values = past_key_values.update(k, v, self.layer_idx)
+    length = layer.cumulative_length if static else keys.shape[2]
+    try:
+        plan = ops.attn_decode_plan(q, keys, values, length, mask=attention_mask)
+    except ops.QllmUnsupported:
+        return None, keys, values, True
+    with torch.no_grad():
+        return ops.attn_decode(q, keys, values, length, mask=attention_mask, scaling=self.scaling, plan=plan), keys, values, True
+
+
+def install_fused_attention(model: torch.nn.Module, attention_types: Optional[Iterable] = None) -> int:
+    """Give every attention module of `model` whose class name is in fused_norm.ATTENTION_TYPES (and in `attention_types`, classes or
+    names, when given) and whose forward is the one fused_rope.py restates (`_known`) that restated forward with `_fused_core` in it.  No
+    transformers global is touched.  Anything else is left alone and not counted.  Returns the number of modules patched;
+    QLLM_FUSE_ATTENTION=0 makes it a no-op that returns 0.  `uninstall_fused_attention` restores exactly what was there, in any order with
+    `uninstall_fused_rope`."""
+    if os.environ.get("QLLM_FUSE_ATTENTION", "1") == "0":
+        return 0
+    names = set(ATTENTION_TYPES)
+    if attention_types is not None:
+        names &= {t if isinstance(t, str) else t.__name__ for t in attention_types}
+    n = 0
+    for attn in model.modules():
+        if type(attn).__name__ not in names or _CORE in attn.__dict__:
+            continue
+        known = _known(attn)
+        if known is None:
+            continue
+        _patch(attn, _CORE, known + (_fused_core,))
+        n += 1
+    return n
+
+
+def uninstall_fused_attention(model: torch.nn.Module) -> int:
+    """Undo `install_fused_attention`.  Returns how many modules were restored."""
+    n = 0
+    for mod in model.modules():
+        if _CORE in mod.__dict__:
+            _unpatch(mod, _CORE)
+            n += 1
+    return n

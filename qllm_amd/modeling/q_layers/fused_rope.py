@@ -25,6 +25,7 @@ from ... import ops
 from .fused_norm import ATTENTION_TYPES
 
 _ATTN = "_qllm_unfused_attention_forward"   # on an attention module: (the instance forward it had or None, the eager rotary function, how it finds its sliding window)
+_CORE = "_qllm_unfused_attention_core"      # fused_attention.py's record on an attention module: the same three, and its attention core
 _KNOWN = ("hidden_states", "position_embeddings", "attention_mask", "past_key_values")
 _ACT_DTYPES = (torch.float16, torch.bfloat16)
 
@@ -60,8 +61,11 @@ def apply_rotary(eager, q, k, cos, sin, unsqueeze_dim: int = 1):
 
 
 def _attention_forward(self, hidden_states, position_embeddings=None, attention_mask=None, past_key_values=None, **kwargs):
-    """LlamaAttention.forward / MistralAttention.forward / Qwen2Attention.forward of transformers 5, with `apply_rotary`."""
-    _, eager_rotary, window = self.__dict__[_ATTN]
+    """LlamaAttention.forward / MistralAttention.forward / Qwen2Attention.forward of transformers 5 -- the ONE restatement, shared with
+    fused_attention.py -- with `apply_rotary` where install_fused_rope put it (`_ATTN`) and the fused attention core where
+    install_fused_attention put it (`_CORE`); either may be there without the other."""
+    rope, core = self.__dict__.get(_ATTN), self.__dict__.get(_CORE)
+    _, eager_rotary, window = (rope or core)[:3]
     family = sys.modules[type(self).__module__]
     input_shape = hidden_states.shape[:-1]
     hidden_shape = (*input_shape, -1, self.head_dim)
@@ -69,8 +73,17 @@ def _attention_forward(self, hidden_states, position_embeddings=None, attention_
     key_states = self.k_proj(hidden_states).view(hidden_shape).transpose(1, 2)
     value_states = self.v_proj(hidden_states).view(hidden_shape).transpose(1, 2)
     cos, sin = position_embeddings
-    query_states, key_states = apply_rotary(eager_rotary, query_states, key_states, cos, sin)
-    if past_key_values is not None:
+    if rope is not None:
+        query_states, key_states = apply_rotary(eager_rotary, query_states, key_states, cos, sin)
+    else:
+        query_states, key_states = eager_rotary(query_states, key_states, cos, sin)
+    updated = False
+    if core is not None:
+        # (the core's output [B, Hq, D], or None), and the key / value states after the cache update where the core has made it
+        attn_output, key_states, value_states, updated = core[3](self, query_states, key_states, value_states, attention_mask, past_key_values, kwargs, window)
+        if attn_output is not None:
+            return self.o_proj(attn_output.reshape(*input_shape, -1)), None
+    if past_key_values is not None and not updated:
         key_states, value_states = past_key_values.update(key_states, value_states, self.layer_idx)
     attention_interface = family.ALL_ATTENTION_FUNCTIONS.get_interface(self.config._attn_implementation, family.eager_attention_forward)
     if window == "config":      # Mistral
@@ -81,6 +94,29 @@ def _attention_forward(self, hidden_states, position_embeddings=None, attention_
                                                     dropout=0.0 if not self.training else self.attention_dropout, scaling=self.scaling, **kwargs)
     attn_output = attn_output.reshape(*input_shape, -1).contiguous()
     return self.o_proj(attn_output), attn_weights
+
+
+def _patch(attn, key: str, value: tuple) -> None:
+    """Record `value` under `key` (`_ATTN` or `_CORE`) on an attention module and give it the restated forward, unless the other install
+    has done so already; the instance forward it had before either (or None) is kept with both records."""
+    other = attn.__dict__.get(_CORE if key == _ATTN else _ATTN)
+    if other is None:
+        orig = attn.__dict__.get("forward")
+        attn.forward = types.MethodType(_attention_forward, attn)
+    else:
+        orig = other[0]
+    setattr(attn, key, (orig,) + value)
+
+
+def _unpatch(mod, key: str) -> None:
+    """Undo `_patch`: drop the record; when the other install's is gone too, the module gets back the forward it had."""
+    orig = mod.__dict__.pop(key)[0]
+    if (_CORE if key == _ATTN else _ATTN) in mod.__dict__:
+        return
+    if orig is None:
+        mod.__dict__.pop("forward", None)
+    else:
+        mod.forward = orig
 
 
 def _known(attn):
@@ -127,8 +163,7 @@ def install_fused_rope(model: torch.nn.Module, attention_types: Optional[Iterabl
         known = _known(attn)
         if known is None:
             continue
-        setattr(attn, _ATTN, (attn.__dict__.get("forward"),) + known)
-        attn.forward = types.MethodType(_attention_forward, attn)
+        _patch(attn, _ATTN, known)
         n += 1
     return n
 
@@ -138,10 +173,6 @@ def uninstall_fused_rope(model: torch.nn.Module) -> int:
     n = 0
     for mod in model.modules():
         if _ATTN in mod.__dict__:
-            orig = mod.__dict__.pop(_ATTN)[0]
-            if orig is None:
-                mod.__dict__.pop("forward", None)
-            else:
-                mod.forward = orig
+            _unpatch(mod, _ATTN)
             n += 1
     return n

@@ -584,6 +584,134 @@ def rope(q: torch.Tensor, k: Optional[torch.Tensor], cos: torch.Tensor, sin: tor
     return q_out, k_out
 
 
+ATTN_DECODE_HEAD_DIMS = (64, 128)   # what csrc/attn_decode.hip is built for
+ATTN_DECODE_MAX_GROUP = 8           # kAttnDecodeMaxGroup of csrc/kernels.hpp
+
+
+def _attn_heads(t: torch.Tensor, name: str):
+    """(batch, heads, head_dim, row stride, head stride) of a one-token q / k_new / v_new given as [B, H, 1, D] or [B, 1, H, D]."""
+    if t.dim() != 4 or (t.shape[2] != 1 and t.shape[1] != 1):
+        raise QllmUnsupported(_lib.QLLM_ERR_UNSUPPORTED, f"attn_decode: {name} must be one token, [B, H, 1, D] or [B, 1, H, D] (got {tuple(t.shape)})")
+    hd = 1 if t.shape[2] == 1 else 2
+    b, h, d = t.shape[0], t.shape[hd], t.shape[3]
+    if b == 0 or h == 0 or d == 0:
+        raise QllmUnsupported(_lib.QLLM_ERR_UNSUPPORTED, f"attn_decode: empty {name}")
+    if d > 1 and t.stride(3) != 1:
+        raise QllmUnsupported(_lib.QLLM_ERR_UNSUPPORTED, f"attn_decode: the last dimension of {name} must have stride 1 (got {t.stride(3)})")
+    row = t.stride(0) if b > 1 else h * d
+    head = t.stride(hd) if h > 1 else d
+    if row % 8 or head % 8 or row < 0 or head < 0 or t.data_ptr() % 16:
+        raise QllmUnsupported(_lib.QLLM_ERR_UNSUPPORTED, f"attn_decode: {name} must be 16-byte aligned with strides that are multiples of 8 (row {row}, head {head})")
+    return b, h, d, row, head
+
+
+def attn_decode_plan(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, length, k_new: Optional[torch.Tensor] = None,
+                     v_new: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None):
+    """What `attn_decode` hands to qllm_attn_decode for these tensors -- (batch, q_heads, kv_heads, head_dim, max_len, q row / head stride,
+    k_new row / head stride, v_new row / head stride, cache batch / head / position stride, mask_kind, mask_len, mask batch stride) -- or
+    QllmUnsupported with the reason.  q (and k_new / v_new, both or neither): one token, [B, H, 1, D] or [B, 1, H, D] views of one fp16 /
+    bf16 type, inner stride 1, 16-byte aligned, strides multiples of 8; caches [B, Hkv, L, D] of that type with contiguous D and the same
+    strides; Hkv divides Hq, at most 8 query heads per kv head; D 64 or 128; mask None, [B, 1, 1, L'] or [B, L'] (B or 1 rows), bool or of
+    the activation type, inner stride 1; `length` an int (0..L, L - 1 at most with an append; the mask covers it) or a 0-d int64 tensor on
+    the device (the mask then covers L).  Pure host code, any device."""
+    def no(why):
+        return QllmUnsupported(_lib.QLLM_ERR_UNSUPPORTED, "attn_decode: " + why)
+    if (k_new is None) != (v_new is None):
+        raise no("k_new and v_new must be given together or not at all")
+    ts = [("q", q), ("k_cache", k_cache), ("v_cache", v_cache)] + ([("k_new", k_new), ("v_new", v_new)] if k_new is not None else [])
+    if q.dtype not in (torch.float16, torch.bfloat16) or any(t.dtype != q.dtype for _, t in ts):
+        raise no("q, the caches and k_new / v_new must share one type, float16 or bfloat16 (got " + ", ".join(str(t.dtype)[6:] for _, t in ts) + ")")
+    if any(t.device != q.device for _, t in ts) or (mask is not None and mask.device != q.device):
+        raise no("every tensor must be on one device")
+    b, hq, d, q_row, q_head = _attn_heads(q, "q")
+    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape or k_cache.stride() != v_cache.stride() or k_cache.shape[0] != b or k_cache.shape[3] != d:
+        raise no(f"the caches must be two [B, Hkv, L, D] tensors of one shape and layout with q's B and D (got {tuple(k_cache.shape)}, {tuple(v_cache.shape)})")
+    hkv, max_len = k_cache.shape[1], k_cache.shape[2]
+    if hkv == 0 or max_len == 0:
+        raise no("empty caches")
+    if hq % hkv:
+        raise no(f"the kv heads must divide the query heads (got {hq}, {hkv})")
+    if d not in ATTN_DECODE_HEAD_DIMS:
+        raise no(f"head_dim 64 or 128 (got {d})")
+    if hq // hkv > ATTN_DECODE_MAX_GROUP:
+        raise no(f"at most {ATTN_DECODE_MAX_GROUP} query heads per kv head (got {hq // hkv})")
+    if b * hkv > 4096 or b > 65535:
+        raise no(f"batch * kv_heads <= 4096 (got {b * hkv})")
+    cs = [k_cache.stride(i) if k_cache.shape[i] > 1 else 0 for i in range(3)]
+    if k_cache.stride(3) != 1 or any(s % 8 or s < 0 for s in cs) or k_cache.data_ptr() % 16 or v_cache.data_ptr() % 16:
+        raise no(f"the caches must have contiguous head rows, 16-byte aligned, with strides that are multiples of 8 (got {tuple(k_cache.stride())})")
+    new = (0, 0, 0, 0)
+    if k_new is not None:
+        kb, kh, kd, k_row, k_head = _attn_heads(k_new, "k_new")
+        vb, vh, vd, v_row, v_head = _attn_heads(v_new, "v_new")
+        if (kb, kh, kd) != (b, hkv, d) or (vb, vh, vd) != (b, hkv, d):
+            raise no(f"k_new and v_new must be one token of [{b}, {hkv}, {d}] (got {tuple(k_new.shape)}, {tuple(v_new.shape)})")
+        new = (k_row, k_head, v_row, v_head)
+    on_device = isinstance(length, torch.Tensor)
+    if on_device:
+        if length.dim() != 0 or length.dtype != torch.int64 or length.device != q.device:
+            raise no("a length on the device must be a 0-d int64 tensor on q's device")
+        need = max_len
+    else:
+        length = int(length)
+        need = length + (1 if k_new is not None else 0)
+        if length < 0 or need > max_len:
+            raise no(f"the length{' + 1 (append)' if k_new is not None else ''} must lie in 0..{max_len} (got {length})")
+    kind, mask_len, mask_batch = _lib.ATTN_MASK_NONE, 0, 0
+    if mask is not None:
+        m2 = mask[:, 0, 0] if mask.dim() == 4 and mask.shape[1] == 1 and mask.shape[2] == 1 else mask
+        if m2.dim() != 2 or m2.shape[0] not in (1, b) or (m2.shape[1] > 1 and m2.stride(1) != 1):
+            raise no(f"the mask must be [B, 1, 1, L] or [B, L] with B = {b} or 1 and inner stride 1 (got {tuple(mask.shape)}, strides {tuple(mask.stride())})")
+        if mask.dtype == torch.bool:
+            kind = _lib.ATTN_MASK_BOOL
+        elif mask.dtype == q.dtype and mask.data_ptr() % 2 == 0:
+            kind = _lib.ATTN_MASK_ADDITIVE
+        else:
+            raise no(f"the mask must be bool or additive in {str(q.dtype)[6:]} (got {str(mask.dtype)[6:]})")
+        mask_len, mask_batch = m2.shape[1], (m2.stride(0) if m2.shape[0] > 1 else 0)
+        if mask_len < need or mask_batch < 0:
+            raise no(f"the mask must cover {need} positions (got {mask_len})")
+    return (b, hq, hkv, d, max_len, q_row, q_head) + new + tuple(cs) + (kind, mask_len, mask_batch)
+
+
+def attn_decode_describe(batch: int, q_heads: int, kv_heads: int, head_dim: int, max_len: int) -> str:
+    """The launch `attn_decode` makes for these shapes ("attn_decode tile=64 splits=16 chunk=256 grid=16x32x1 group=1 combine=last-block"), or
+    "refused: ...".  Pure host code: a function of the shapes and the device's CU count, never of the length."""
+    return _describe("qllm_attn_decode_describe", 256, int(batch), int(q_heads), int(kv_heads), int(head_dim), int(max_len))
+
+
+def attn_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, length, k_new: Optional[torch.Tensor] = None,
+                v_new: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, scaling: Optional[float] = None, *, out=None, plan=None):
+    """softmax(scaling * q K^T + mask) V for one query token per sequence over the first `length` positions of the caches [B, Hkv, L, D], as
+    ONE kernel (qllm_attn_decode, csrc/attn_decode.hip): a K / V row is read once for all query heads of its kv head, positions >= length
+    are never loaded, fp32 scores and softmax, one rounding at the store.  Returns [B, Hq, D] (contiguous: the row o_proj takes).
+    `length`: an int, or a 0-d int64 tensor on the device that the kernel reads (a captured call then serves every length).  k_new / v_new:
+    the new token's rows; the kernel stores them at position `length` of the caches and attends over length + 1 positions (with the
+    length on the device and length + 1 > L it stores nothing and attends over the first L positions).  mask: [B, 1, 1, L'] or [B, L'],
+    bool (True = visible) or additive; a row with no visible key gives zeros.  scaling: D ** -0.5 when None.  `attn_decode_plan` says what
+    is served; everything else raises QllmUnsupported before anything is launched.  plan: what it returned for these very arguments."""
+    if plan is None:
+        plan = attn_decode_plan(q, k_cache, v_cache, length, k_new, v_new, mask)
+    b, hq, hkv, d, max_len = plan[:5]
+    for t in (q, k_cache, v_cache):
+        if not t.is_cuda:
+            raise RuntimeError("attn_decode: q and the caches must be HIP/CUDA tensors (qllm_amd has no CPU forward path)")
+    if out is None:
+        out = torch.empty((b, hq, d), dtype=q.dtype, device=q.device)
+    elif out.shape != (b, hq, d) or out.dtype != q.dtype or out.device != q.device or not out.is_contiguous():
+        raise RuntimeError(f"attn_decode: out must be a contiguous {(b, hq, d)} {q.dtype} tensor on {q.device}")
+    on_device = isinstance(length, torch.Tensor)
+    lib = _lib.load()
+    with torch.cuda.device(q.device):
+        nbytes = lib.qllm_attn_decode_workspace_bytes(b, hq, hkv, d, max_len)
+        ws = workspace(q.device, nbytes)
+        rc = lib.qllm_attn_decode(q.data_ptr(), _ptr(k_new), _ptr(v_new), k_cache.data_ptr(), v_cache.data_ptr(), _ptr(mask), out.data_ptr(),
+                                  b, hq, hkv, d, 0 if on_device else int(length), length.data_ptr() if on_device else None, max_len,
+                                  *plan[5:], float(d ** -0.5 if scaling is None else scaling), _act_dtype(q), ws.data_ptr(), ws.numel(), _stream_ptr())
+    _lib.check(rc)
+    return out
+
+
 def dequant(w: QllmWeight, device: torch.device, dtype=torch.float16, transposed: bool = False) -> torch.Tensor:
     """W[K,N] (or [N,K]) bit-identical to the reference's DequantizeLinearBlockWise / unpack()."""
     lib = _lib.load()
