@@ -156,6 +156,10 @@ def load_quantized(model_dir: str, device: Optional[str] = "cuda", torch_dtype: 
 
     hf_cfg = transformers.AutoConfig.from_pretrained(model_dir)
     dtype = torch_dtype or getattr(hf_cfg, "torch_dtype", None) or torch.float16
+    if torch_dtype is not None:
+        # from_config builds the model in the type its config names, whatever the default type is: a checkpoint saved as float16 and
+        # asked for in bfloat16 used to come back in float16
+        setattr(hf_cfg, "dtype" if hasattr(hf_cfg, "dtype") else "torch_dtype", torch_dtype)
     cfg = QuantConfig.from_dir(model_dir)
     prev = torch.get_default_dtype()
     torch.set_default_dtype(dtype)
