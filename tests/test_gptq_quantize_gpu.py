@@ -7,8 +7,10 @@ the fixtures are chosen so that the reference against itself (calibration batche
 loss and output error <= 1.01 x the reference's (its self-variation is <= 3e-4), and the output error below the midpoint between the
 reference's and round-to-nearest's.  Group 0's parameters depend on the original W only (one subtraction, one division, one rint): exact.
 
-Measured on an MI355X (kernel tier / pipeline tier, share of differing codes; inside the first 128 columns always 0):
-see profiles/gptq_quantize.md."""
+Measured on an MI355X (kernel tier / pipeline tier, share of differing codes): see profiles/gptq_quantize.md.  Inside the first 128
+processed columns the kernel tier differs in no code, which is asserted; the pipeline tier factorises H on the device, its U differs from
+the fixture's by 2e-6 of the largest entry, and w4_g128_actorder then changes 0.134 % of the first block's codes.
+The summation order itself is pinned bit for bit by tests/test_gptq_walk_gpu.py."""
 import glob
 import json
 import os
@@ -89,6 +91,8 @@ def check_quality(d, name, tier, codes_nk, loss, wq_orig_order):
     print(f"{tier} {name}: codes differ {diff.mean():.4%} (first 128 columns {first.mean():.4%}); loss {loss:.6e} vs {d['error']:.6e} "
           f"(x{loss / d['error']:.5f}); out err {e:.6e} vs gptq {d['gptq_out_err']:.6e} (x{e / d['gptq_out_err']:.5f}) rtn {d['rtn_out_err']:.6e}")
     assert diff.mean() <= 0.01
+    if tier == "kernel":      # the reference's own U: the first block has no summation order of a matmul behind it
+        assert not first.any()
     assert loss <= 1.01 * d["error"]
     assert e <= 1.01 * d["gptq_out_err"]
     assert e < 0.5 * (d["gptq_out_err"] + d["rtn_out_err"])
