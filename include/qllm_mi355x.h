@@ -521,8 +521,8 @@ int qllm_rope(const void *q, const void *k, const void *cos, const void *sin, vo
  * a host kv_len outside 0..max_len (kv_len + 1 > max_len with an append), a mask too short.  QLLM_ERR_UNSUPPORTED: head_dim other than
  * 64 / 128, more than 8 query heads per kv head, batch * kv_heads > 4096.  QLLM_ERR_WORKSPACE: a missing, misaligned or small
  * workspace.  Every error is raised before any device work.  No host synchronisation; hipGraph-capturable.
- * Not built: prefill (more than one query token), sliding-window, quantized and paged caches, per-sequence lengths other than through the
- * mask, rotary inside the kernel, an fp8 cache.
+ * Not built: sliding-window, quantized and paged caches, per-sequence lengths other than through the mask, rotary inside the kernel, an
+ * fp8 cache.  More than one query token: qllm_attn_prefill below.
  * ABI: the symbols are ADDITIVE within ABI 7 (QLLM_ABI_VERSION is unchanged): probe for them by symbol. */
 #define QLLM_ATTN_MASK_NONE 0
 #define QLLM_ATTN_MASK_BOOL 1
@@ -539,6 +539,41 @@ size_t qllm_attn_decode_workspace_bytes(int32_t batch, int32_t q_heads, int32_t 
  * block step; chunk: positions per split, a multiple of the tile; split s owns positions s * chunk .. (s + 1) * chunk - 1), or "refused: "
  * and the refusal text.  Pure host code. */
 int qllm_attn_decode_describe(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int64_t max_len, char *buf, size_t buflen);
+
+/* ---- prefill attention over the KV cache --------------------------------------------------------------------------------------------------- */
+/* out[b, i, h, :] = softmax_j(scaling * q[b, h, i, :] . K[b, h / G, j, :] + mask[b, i, j]) V[b, h / G, j, :] for q_len >= 2 query rows per
+ * sequence against caches that ALREADY hold the q_len new rows, in ONE launch (csrc/attn_prefill.hip, flash attention forward on MFMA):
+ * a block of four waves owns one (batch entry, query head, tile of 128 query rows) and walks the keys in tiles of 64; fp32 scores, an fp32
+ * online softmax in the log2 domain, P rounded once to act_dtype as the P.V operand, fp32 accumulators, one rounding at the store.  No
+ * split over the keys, no workspace: batch * q_heads * ceil(q_len / 128) blocks, a function of the shapes alone -- never of kv_len: a
+ * captured launch serves every length.
+ * kv_len counts the valid positions INCLUDING the new ones; query row i sits at absolute position kv_len - q_len + i.  causal = 1: key j is
+ * visible to row i only if j <= kv_len - q_len + i, and key tiles wholly above a block's diagonal are never read; causal = 0: every
+ * j < kv_len counts.
+ * q: element (b, head, i, d) at q + b * q_batch_stride + head * q_head_stride + i * q_row_stride + d (strides in elements: the [B, S, Hq, D]
+ * projection output viewed as [B, Hq, S, D] is served in place).  out: contiguous [batch, q_len, q_heads, head_dim] -- the rows o_proj
+ * takes.  Caches: as qllm_attn_decode takes them, the same three strides for both; they are only read.
+ * Length: kv_len, or with kv_len_dev != NULL the int64 the kernel reads there, clamped to q_len..max_len.  Positions >= kv_len are never
+ * loaded: their K and V count as zeros.  Keys hidden only by the mask or by causality ARE loaded; their rows are assumed finite.
+ * Mask: element (b, i, j) at mask + b * mask_batch_stride + i * mask_row_stride + j, j < mask_len; the two kinds and constants of
+ * qllm_attn_decode; mask_batch_stride may be 0.  It is applied in addition to causality.  A row with no visible key stores zeros.
+ * QLLM_ERR_INVALID: a NULL q / cache / out, sizes < 1, q_len < 2 or q_len > max_len, kv_heads not dividing q_heads, a bad act_dtype,
+ * mask_kind or causal, a mask pointer not matching mask_kind, a data pointer off 16 bytes, a q or cache stride that is negative or no
+ * multiple of 8, a negative mask stride, a host kv_len outside q_len..max_len, a mask shorter than kv_len (max_len with the length on the
+ * device).  QLLM_ERR_UNSUPPORTED: head_dim other than 64 / 128, more than 8 query heads per kv head, q_heads or batch above 65535.  Every
+ * error is raised before any device work.  No host synchronisation; hipGraph-capturable.
+ * Not built: a split over the keys for short q_len behind long caches, sliding-window, quantized and paged caches, rotary or the cache
+ * append inside the kernel, dropout, attention weights as an output, backward.
+ * ABI: the symbols are ADDITIVE within ABI 7 (QLLM_ABI_VERSION is unchanged): probe for them by symbol. */
+int qllm_attn_prefill(const void *q, const void *k_cache, const void *v_cache, const void *mask, void *out, int32_t batch, int32_t q_heads,
+                      int32_t kv_heads, int32_t head_dim, int32_t q_len, int64_t kv_len, const int64_t *kv_len_dev, int64_t max_len,
+                      int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride, int64_t cache_batch_stride, int64_t cache_head_stride,
+                      int64_t cache_pos_stride, int32_t mask_kind, int64_t mask_len, int64_t mask_batch_stride, int64_t mask_row_stride, int32_t causal,
+                      float scaling, int32_t act_dtype, void *stream);
+/* What a call would launch, as text: "attn_prefill q_tile=128 kv_tile=64 grid=2x32x1 group=4", or "refused: " and the refusal text.  Pure
+ * host code. */
+int qllm_attn_prefill_describe(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t q_len, int64_t max_len, char *buf,
+                               size_t buflen);
 
 /* ---- HQQ quantizer (ABI 7) ---------------------------------------------------------------------------------------------------------- */
 /* W[N,K] (fp16 / bf16 / fp32 by w_dtype, row-major, 16-byte aligned) -> the HQQ layer buffers: qweight i32 [K*bits/32][N], scales f16

@@ -29,8 +29,8 @@
 // a bf16 bias that is finite, above the lowest finite number and below about -7e29 has exp2(s - kNoMax) = 0: a row whose visible keys ALL
 // carry such a bias stores zeros instead of a softmax among them (fp16 has no such value; transformers masks with finfo.min).
 //
-// Not built: prefill (q_len > 1), sliding-window and quantized caches, paged caches, per-sequence lengths other than through the mask,
-// head_dim other than 64 / 128, rotary inside the kernel, an fp8 cache, P.V on MFMA.
+// Not built: sliding-window and quantized caches, paged caches, per-sequence lengths other than through the mask,
+// head_dim other than 64 / 128, rotary inside the kernel, an fp8 cache, P.V on MFMA.  More than one query token: attn_prefill.hip.
 #include "kernels.hpp"
 
 namespace qllm {

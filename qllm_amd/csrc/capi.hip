@@ -1099,6 +1099,79 @@ int qllm_attn_decode(const void *q, const void *k_new, const void *v_new, void *
   return launch_attn_decode(p, head_dim, act_dtype == QLLM_BF16, (hipStream_t)stream);
 }
 
+// ---- prefill attention over the KV cache (attn_prefill.hip) ------------------------------------------------------------------------------
+// the shape checks the two entries share: sizes, the head ratio, then what the kernel is built for
+static int check_attn_prefill_shape(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t q_len, int64_t max_len) {
+  if (batch <= 0 || q_heads <= 0 || kv_heads <= 0 || head_dim <= 0 || max_len <= 0)
+    return set_error(QLLM_ERR_INVALID, "batch, q_heads, kv_heads, head_dim and max_len must be >= 1 (got %d, %d, %d, %d, %lld)", batch, q_heads, kv_heads,
+                     head_dim, (long long)max_len);
+  if (q_len < 2 || q_len > max_len)
+    return set_error(QLLM_ERR_INVALID, "q_len must lie in 2..max_len (got q_len=%d max_len=%lld); one token is qllm_attn_decode's", q_len, (long long)max_len);
+  if (q_heads % kv_heads != 0) return set_error(QLLM_ERR_INVALID, "kv_heads must divide q_heads (got q_heads=%d kv_heads=%d)", q_heads, kv_heads);
+  return QLLM_OK;
+}
+static int check_attn_prefill_served(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim) {
+  if (head_dim != 64 && head_dim != 128) return set_error(QLLM_ERR_UNSUPPORTED, "attn_prefill serves head_dim 64 and 128 (got %d)", head_dim);
+  if (q_heads / kv_heads > kAttnDecodeMaxGroup)
+    return set_error(QLLM_ERR_UNSUPPORTED, "attn_prefill serves 1..%d query heads per kv head (got %d)", kAttnDecodeMaxGroup, q_heads / kv_heads);
+  if (batch > 65535 || q_heads > 65535)
+    return set_error(QLLM_ERR_UNSUPPORTED, "attn_prefill serves batch <= 65535 and q_heads <= 65535 (got %d, %d)", batch, q_heads);
+  return QLLM_OK;
+}
+
+int qllm_attn_prefill_describe(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t q_len, int64_t max_len, char *buf,
+                               size_t buflen) {
+  clear_error();
+  if (!buf || buflen == 0) return set_error(QLLM_ERR_INVALID, "buf must not be NULL or empty");
+  int rc = check_attn_prefill_shape(batch, q_heads, kv_heads, head_dim, q_len, max_len);
+  if (rc == QLLM_OK) rc = check_attn_prefill_served(batch, q_heads, kv_heads, head_dim);
+  if (rc != QLLM_OK) return describe_refusal(rc, kRefused, buf, buflen);
+  snprintf(buf, buflen, "attn_prefill q_tile=%d kv_tile=%d grid=%dx%dx%d group=%d", kAttnPrefillQTile, kAttnPrefillKvTile,
+           (q_len + kAttnPrefillQTile - 1) / kAttnPrefillQTile, q_heads, batch, q_heads / kv_heads);
+  return QLLM_OK;
+}
+
+int qllm_attn_prefill(const void *q, const void *k_cache, const void *v_cache, const void *mask, void *out, int32_t batch, int32_t q_heads,
+                      int32_t kv_heads, int32_t head_dim, int32_t q_len, int64_t kv_len, const int64_t *kv_len_dev, int64_t max_len,
+                      int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride, int64_t cache_batch_stride, int64_t cache_head_stride,
+                      int64_t cache_pos_stride, int32_t mask_kind, int64_t mask_len, int64_t mask_batch_stride, int64_t mask_row_stride, int32_t causal,
+                      float scaling, int32_t act_dtype, void *stream) {
+  clear_error();
+  if (!q || !k_cache || !v_cache || !out) return set_error(QLLM_ERR_INVALID, "q / k_cache / v_cache / out must not be NULL");
+  int rc = check_attn_prefill_shape(batch, q_heads, kv_heads, head_dim, q_len, max_len);
+  if (rc != QLLM_OK) return rc;
+  if (act_dtype != QLLM_F16 && act_dtype != QLLM_BF16) return set_error(QLLM_ERR_INVALID, "act_dtype must be QLLM_F16 or QLLM_BF16");
+  if (mask_kind != QLLM_ATTN_MASK_NONE && mask_kind != QLLM_ATTN_MASK_BOOL && mask_kind != QLLM_ATTN_MASK_ADDITIVE)
+    return set_error(QLLM_ERR_INVALID, "mask_kind must be QLLM_ATTN_MASK_NONE, _BOOL or _ADDITIVE (got %d)", mask_kind);
+  if ((mask_kind == QLLM_ATTN_MASK_NONE) != (mask == nullptr)) return set_error(QLLM_ERR_INVALID, "mask must be NULL exactly with QLLM_ATTN_MASK_NONE");
+  if (causal != 0 && causal != 1) return set_error(QLLM_ERR_INVALID, "causal must be 0 or 1 (got %d)", causal);
+  if ((uintptr_t)q % 16 || (uintptr_t)k_cache % 16 || (uintptr_t)v_cache % 16 || (uintptr_t)out % 16)
+    return set_error(QLLM_ERR_INVALID, "q / k_cache / v_cache / out must be 16-byte aligned");
+  if ((uintptr_t)kv_len_dev % 8 || (mask_kind == QLLM_ATTN_MASK_ADDITIVE && (uintptr_t)mask % 2))
+    return set_error(QLLM_ERR_INVALID, "kv_len_dev must be 8-byte aligned and an additive mask 2-byte aligned");
+  const int64_t strides[6] = {q_batch_stride, q_head_stride, q_row_stride, cache_batch_stride, cache_head_stride, cache_pos_stride};
+  for (int i = 0; i < 6; ++i)
+    if (strides[i] < 0 || strides[i] % 8 != 0)
+      return set_error(QLLM_ERR_INVALID, "batch, head, row and position strides must be non-negative multiples of 8 elements (got %lld)", (long long)strides[i]);
+  if (!kv_len_dev && (kv_len < q_len || kv_len > max_len))
+    return set_error(QLLM_ERR_INVALID, "kv_len must lie in q_len..max_len (got kv_len=%lld q_len=%d max_len=%lld)", (long long)kv_len, q_len, (long long)max_len);
+  const int64_t need_len = kv_len_dev ? max_len : kv_len;  // the positions a call may reach
+  if (mask && (mask_len < need_len || mask_batch_stride < 0 || mask_row_stride < 0))
+    return set_error(QLLM_ERR_INVALID, "the mask must cover %lld positions (%s) with non-negative batch and row strides (got mask_len=%lld strides=%lld, %lld)",
+                     (long long)need_len, kv_len_dev ? "max_len: the length is on the device" : "kv_len", (long long)mask_len, (long long)mask_batch_stride,
+                     (long long)mask_row_stride);
+  rc = check_attn_prefill_served(batch, q_heads, kv_heads, head_dim);
+  if (rc != QLLM_OK) return rc;
+
+  AttnPrefillParams p;
+  p.q = q, p.k_cache = k_cache, p.v_cache = v_cache, p.mask = mask, p.out = out;
+  p.kv_len_dev = kv_len_dev, p.kv_len = kv_len, p.max_len = max_len;
+  p.q_batch = q_batch_stride, p.q_head = q_head_stride, p.q_row = q_row_stride, p.c_batch = cache_batch_stride, p.c_head = cache_head_stride,
+  p.c_pos = cache_pos_stride, p.mask_batch = mask_batch_stride, p.mask_row = mask_row_stride;
+  p.batch = batch, p.q_heads = q_heads, p.kv_heads = kv_heads, p.q_len = q_len, p.mask_kind = mask_kind, p.causal = causal, p.scaling = scaling;
+  return launch_attn_prefill(p, head_dim, act_dtype == QLLM_BF16, (hipStream_t)stream);
+}
+
 int qllm_dequant(const qllm_weight_t *w, void *out, int32_t out_dtype, int32_t out_transposed, void *stream) {
   clear_error();
   int rc = validate_weight(w);

@@ -307,6 +307,21 @@ struct AttnDecodeGeom {
 AttnDecodeGeom attn_decode_geom(int batch, int q_heads, int kv_heads, int head_dim, int64_t max_len);
 int launch_attn_decode(const AttnDecodeParams &p, int head_dim, int act_bf16, hipStream_t stream);
 
+// ---- attn_prefill.hip: q_len >= 2 query rows per sequence against the first kv_len positions of a KV cache (flash attention forward) -----
+constexpr int kAttnPrefillQTile = 128;  // query rows per block: 32 per wave
+constexpr int kAttnPrefillKvTile = 64;  // key positions per block step
+struct AttnPrefillParams {
+  const void *q, *k_cache, *v_cache;
+  const void *mask;               // mask_kind 0: none; 1: bool bytes; 2: additive, activation type
+  void *out;                      // contiguous [batch, q_len, q_heads, head_dim]
+  const int64_t *kv_len_dev;      // NULL: kv_len
+  int64_t kv_len, max_len;
+  int64_t q_batch, q_head, q_row, c_batch, c_head, c_pos, mask_batch, mask_row;  // strides in elements
+  int batch, q_heads, kv_heads, q_len, mask_kind, causal;
+  float scaling;
+};
+int launch_attn_prefill(const AttnPrefillParams &p, int head_dim, int act_bf16, hipStream_t stream);
+
 // ---- native.hip (reference layouts <-> the strip-major native layout) -------------------------------------------------------
 int launch_repack_native(const qllm_weight_t &src, int zero_kind, void *qweight_out, void *scales_out, void *qzeros_out, hipStream_t stream);
 int launch_unpack_native(const qllm_weight_t &src, int dst_layout, void *qweight_out, void *scales_out, void *qzeros_out, hipStream_t stream);

@@ -142,7 +142,7 @@ def release_reference_layouts(model: torch.nn.Module, on: bool = True) -> int:
 
 def load_quantized(model_dir: str, device: Optional[str] = "cuda", torch_dtype: Optional[torch.dtype] = None,
                    release_reference: bool = True, fuse_mlp: bool = False, fuse_norm: bool = False, fuse_residual: bool = False,
-                   fuse_rope: bool = False, fuse_attention: bool = False):
+                   fuse_rope: bool = False, fuse_attention: bool = False, fuse_attention_prefill: bool = False):
     """Local equivalent of AutoQuantizedModelForCausalLM.from_quantized (base.py:226-322).  `release_reference`: see
     release_reference_layouts (QLLM_RELEASE_REFERENCE=0 in the environment keeps both copies).  `fuse_mlp` (opt-in): fold
     act_fn(gate) * up of the SwiGLU MLPs into the down_proj launch (q_layers/fused_mlp.py); model.fused_mlps counts the modules.
@@ -151,7 +151,10 @@ def load_quantized(model_dir: str, device: Optional[str] = "cuda", torch_dtype: 
     adds of every decoder layer into the o_proj and down_proj launches (q_layers/fused_residual.py); model.fused_residuals counts the layers.
     `fuse_rope` (opt-in): the rotary embedding of q and k of every attention module as one kernel (q_layers/fused_rope.py);
     model.fused_ropes counts the modules.  `fuse_attention` (opt-in): the attention core of a decode step -- one query token against the KV
-    cache -- as one kernel that reads only the valid keys (q_layers/fused_attention.py); model.fused_attentions counts the modules."""
+    cache -- as one kernel that reads only the valid keys (q_layers/fused_attention.py); model.fused_attentions counts the modules.
+    `fuse_attention_prefill` (opt-in; implies the attention install): also the attention core of calls with two or more query tokens --
+    prompts, continuation chunks, padded batches -- as one flash-attention kernel where q_layers/fused_attention.py routes them to it;
+    model.fused_attention_prefills counts the modules (0 with QLLM_FUSE_ATTENTION_PREFILL=0)."""
     import transformers
 
     hf_cfg = transformers.AutoConfig.from_pretrained(model_dir)
@@ -209,9 +212,12 @@ def load_quantized(model_dir: str, device: Optional[str] = "cuda", torch_dtype: 
     if fuse_rope:
         from .q_layers import install_fused_rope
         model.fused_ropes = install_fused_rope(model)
-    if fuse_attention:
+    if fuse_attention or fuse_attention_prefill:
         from .q_layers import install_fused_attention
-        model.fused_attentions = install_fused_attention(model)
+        from .q_layers.fused_attention import count_fused_attention_prefill
+        model.fused_attentions = install_fused_attention(model, prefill=fuse_attention_prefill)
+        if fuse_attention_prefill:
+            model.fused_attention_prefills = count_fused_attention_prefill(model)
     return model.eval()
 
 

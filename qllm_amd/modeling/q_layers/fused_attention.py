@@ -18,9 +18,14 @@ StaticLayer of a cache that does not offload, and `ops.attn_decode_plan` serves 
                 -- needs a host-side bound on the length that holds across `reset`, `crop` and foreign updates of the layer; it is not
                 used here.)
 
-Everything else -- prefill, sliding layers, quantized and offloaded caches, no cache, CPU and fp32 tensors, training, output_attentions --
+Everything else -- sliding layers, quantized and offloaded caches, no cache, CPU and fp32 tensors, training, output_attentions --
 runs the family's own route unchanged.  Composes with install_fused_rope and the other installs in any order.
-Opt-in: `load_quantized(..., fuse_attention=True)`."""
+Opt-in: `load_quantized(..., fuse_attention=True)`.
+
+Prefill (q_len >= 2) runs the family's route unless the install is made with `prefill=True` (`load_quantized(...,
+fuse_attention_prefill=True)`): then `_fused_core_prefill` hands prompts, continuation chunks and padded batches to `ops.attn_prefill`
+(qllm_attn_prefill, csrc/attn_prefill.hip) under the conditions in its docstring, for the (cache layer kind, mask or none, q_len)
+combinations of `PREFILL_ROUTES`.  With the flag off nothing changes."""
 from __future__ import annotations
 
 import os
@@ -40,9 +45,9 @@ def _on_device(*ts) -> bool:
     return all(t.is_cuda for t in ts)
 
 
-def _layer_of(past_key_values, layer_idx):
-    """The cache layer the core may serve -- exactly a DynamicLayer or an initialised StaticLayer of a cache that does not offload --
-    else None."""
+def _layer_of(past_key_values, layer_idx, uninitialized=False):
+    """The cache layer the core may serve -- exactly a DynamicLayer or an initialised StaticLayer (with `uninitialized`: any StaticLayer)
+    of a cache that does not offload -- else None."""
     from transformers.cache_utils import DynamicLayer, StaticLayer
     layers = getattr(past_key_values, "layers", None)
     if not isinstance(layers, list) or not isinstance(layer_idx, int) or not 0 <= layer_idx < len(layers) or getattr(past_key_values, "offloading", False):
@@ -50,7 +55,7 @@ def _layer_of(past_key_values, layer_idx):
     layer = layers[layer_idx]
     if type(layer) is DynamicLayer:
         return layer
-    if type(layer) is StaticLayer and layer.is_initialized:
+    if type(layer) is StaticLayer and (layer.is_initialized or uninitialized):
         return layer
     return None
 
@@ -87,14 +92,88 @@ def _fused_core(self, q, k, v, attention_mask, past_key_values, kwargs, window):
         return ops.attn_decode(q, keys, values, length, mask=attention_mask, scaling=self.scaling, plan=plan), keys, values, True
 
 
-def install_fused_attention(model: torch.nn.Module, attention_types: Optional[Iterable] = None) -> int:
+# What `_fused_core_prefill` hands to ops.attn_prefill, by (cache layer kind, whether the call carries a mask): the q_len range (lowest,
+# highest; None: no upper end) and whether calls behind already cached tokens are routed too.  Set from profiles/attn_prefill.md, "Module
+# routing" (tools/attn_prefill_bench.py; fp16, head_dim 128, S = 16 .. 2048, one MI355X): a combination the kernel loses at a measured
+# point stays on the family's route.  Without a mask and on a static layer every measured point wins (1.06 to 13 times).  On a dynamic
+# layer with a mask the prompt wins up to 128 rows at all three shapes, is mixed at 512 and 1024 (the 32 / 32 shape loses) and loses at
+# 2048, and a chunk of 128 rows behind 1024 cached tokens loses (0.78 to 0.96: B x Hq blocks walk the keys alone, there is no split over
+# them), so there only first prompts of at most PREFILL_DYNAMIC_MASKED_MAX_ROWS rows are routed.
+PREFILL_DYNAMIC_MASKED_MAX_ROWS = 128
+PREFILL_ROUTES = {
+    ("dynamic", False): (2, None, True),
+    ("dynamic", True): (2, PREFILL_DYNAMIC_MASKED_MAX_ROWS, False),
+    ("static", False): (2, None, True),
+    ("static", True): (2, None, True),
+}
+
+
+def _prefill_routed(static: bool, masked: bool, q_len: int, behind: bool) -> bool:
+    """`behind`: the host knows that the layer held tokens before this call (a dynamic layer's length; a static layer's is on the device)."""
+    lo, hi, chunks = PREFILL_ROUTES.get(("static" if static else "dynamic", masked), (1, 0, False))
+    return q_len >= lo and (hi is None or q_len <= hi) and (chunks or not behind)
+
+
+def _fused_core_prefill(self, q, k, v, attention_mask, past_key_values, kwargs, window):
+    """`_fused_core` for q_len == 1; for q_len >= 2 the same tuple with ops.attn_prefill's [B, S, Hq, D] output: the kernel under
+    `_fused_core`'s conditions on types, device, autograd, training, implementation, sliding window, kwargs and cache layer (a StaticLayer
+    may also be uninitialised: `update` initialises it), and in addition: the module is causal (`self.is_causal`); the mask is None or 4-D
+    [B, 1, S, L'], bool or of the activation type; with mask None the cache layer holds nothing before this call and that is known on the
+    host (sdpa's own is_causal rule: a DynamicLayer of length 0, a StaticLayer not yet initialised); `PREFILL_ROUTES` routes the
+    combination.  The kernel runs with causal = 1 plus the mask: a hand-made mask that shows a causal model keys above the diagonal is
+    not honoured there."""
+    if q.shape[2] == 1:
+        return _fused_core(self, q, k, v, attention_mask, past_key_values, kwargs, window)
+    no = (None, k, v, False)
+    if past_key_values is None or self.training or self.config._attn_implementation not in ("sdpa", "eager") or not getattr(self, "is_causal", False):
+        return no
+    if q.dtype not in _ACT_DTYPES or k.dtype != q.dtype or v.dtype != q.dtype or not _on_device(q, k, v):
+        return no
+    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+        return no
+    sliding = getattr(self.config, "sliding_window", None) if window == "config" else getattr(self, "sliding_window", None) if window == "self" else None
+    if sliding is not None or any(val is not None and val is not False for name, val in kwargs.items() if name not in _BENIGN):
+        return no
+    s = q.shape[2]
+    if attention_mask is not None and not (isinstance(attention_mask, torch.Tensor) and attention_mask.dim() == 4 and attention_mask.shape[1] == 1
+                                           and attention_mask.shape[2] == s and (attention_mask.dtype == torch.bool or attention_mask.dtype == q.dtype)):
+        return no
+    layer = _layer_of(past_key_values, self.layer_idx, uninitialized=True)
+    if layer is None:
+        return no
+    static = hasattr(layer, "cumulative_length")
+    held = layer.is_initialized if static else layer.get_seq_length() != 0   # (a static layer: may hold tokens; its length is on the device)
+    if not _prefill_routed(static, attention_mask is not None, s, held and not static):
+        return no
+    if attention_mask is None and held:
+        return no
+    if static and layer.is_initialized and (layer.keys.dtype != q.dtype or layer.keys.shape[0] != q.shape[0] or layer.keys.shape[3] != q.shape[3]):
+        return no
+    keys, values = past_key_values.update(k, v, self.layer_idx)
+    length = layer.cumulative_length if static else keys.shape[2]
+    try:
+        plan = ops.attn_prefill_plan(q, keys, values, length, mask=attention_mask)
+    except ops.QllmUnsupported:
+        return None, keys, values, True
+    with torch.no_grad():
+        return ops.attn_prefill(q, keys, values, length, mask=attention_mask, causal=True, scaling=self.scaling, plan=plan), keys, values, True
+
+
+def count_fused_attention_prefill(model: torch.nn.Module) -> int:
+    """How many attention modules of `model` carry the prefill core."""
+    return sum(1 for mod in model.modules() if _CORE in mod.__dict__ and mod.__dict__[_CORE][3] is _fused_core_prefill)
+
+
+def install_fused_attention(model: torch.nn.Module, attention_types: Optional[Iterable] = None, prefill: bool = False) -> int:
     """Give every attention module of `model` whose class name is in fused_norm.ATTENTION_TYPES (and in `attention_types`, classes or
     names, when given) and whose forward is the one fused_rope.py restates (`_known`) that restated forward with `_fused_core` in it.  No
     transformers global is touched.  Anything else is left alone and not counted.  Returns the number of modules patched;
     QLLM_FUSE_ATTENTION=0 makes it a no-op that returns 0.  `uninstall_fused_attention` restores exactly what was there, in any order with
-    `uninstall_fused_rope`."""
+    `uninstall_fused_rope`.  `prefill` (opt-in, off by default): the modules get `_fused_core_prefill`, which also serves calls with two
+    or more query tokens; QLLM_FUSE_ATTENTION_PREFILL=0 turns the flag into a no-op (the decode core alone is installed)."""
     if os.environ.get("QLLM_FUSE_ATTENTION", "1") == "0":
         return 0
+    core = _fused_core_prefill if prefill and os.environ.get("QLLM_FUSE_ATTENTION_PREFILL", "1") != "0" else _fused_core
     names = set(ATTENTION_TYPES)
     if attention_types is not None:
         names &= {t if isinstance(t, str) else t.__name__ for t in attention_types}
@@ -105,7 +184,7 @@ def install_fused_attention(model: torch.nn.Module, attention_types: Optional[It
         known = _known(attn)
         if known is None:
             continue
-        _patch(attn, _CORE, known + (_fused_core,))
+        _patch(attn, _CORE, known + (core,))
         n += 1
     return n
 

@@ -712,6 +712,109 @@ def attn_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, l
     return out
 
 
+def attn_prefill_plan(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, length, mask: Optional[torch.Tensor] = None):
+    """What `attn_prefill` hands to qllm_attn_prefill for these tensors -- (batch, q_heads, kv_heads, head_dim, q_len, max_len, q batch /
+    head / row stride, cache batch / head / position stride, mask_kind, mask_len, mask batch / row stride) -- or QllmUnsupported with the
+    reason.  q: [B, Hq, S, D] (any strides: the transposed view of the [B, S, Hq, D] projection output is served in place), S >= 2, fp16 /
+    bf16, inner stride 1, 16-byte aligned, strides multiples of 8; caches [B, Hkv, L, D] of that type with contiguous D and the same
+    strides, already holding the S new rows; Hkv divides Hq, at most 8 query heads per kv head; D 64 or 128; mask None, [B, 1, S, L'] or
+    [B, S, L'] (B or 1 batch rows, expanded views included), bool or of the activation type, inner stride 1; `length` an int (S..L; the mask
+    covers it) or a 0-d int64 tensor on the device (the mask then covers L).  Pure host code, any device."""
+    def no(why):
+        return QllmUnsupported(_lib.QLLM_ERR_UNSUPPORTED, "attn_prefill: " + why)
+    ts = [("q", q), ("k_cache", k_cache), ("v_cache", v_cache)]
+    if q.dtype not in (torch.float16, torch.bfloat16) or any(t.dtype != q.dtype for _, t in ts):
+        raise no("q and the caches must share one type, float16 or bfloat16 (got " + ", ".join(str(t.dtype)[6:] for _, t in ts) + ")")
+    if any(t.device != q.device for _, t in ts) or (mask is not None and mask.device != q.device):
+        raise no("every tensor must be on one device")
+    if q.dim() != 4 or 0 in q.shape:
+        raise no(f"q must be a non-empty [B, Hq, S, D] tensor or view (got {tuple(q.shape)})")
+    b, hq, s, d = q.shape
+    if s < 2:
+        raise no(f"q must hold at least two rows per sequence (got {s}); one token is attn_decode's")
+    if q.stride(3) != 1:
+        raise no(f"the last dimension of q must have stride 1 (got {q.stride(3)})")
+    qs = [q.stride(i) if q.shape[i] > 1 else 0 for i in range(3)]
+    if any(x % 8 or x < 0 for x in qs) or q.data_ptr() % 16:
+        raise no(f"q must be 16-byte aligned with strides that are non-negative multiples of 8 (got {tuple(q.stride())})")
+    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape or k_cache.stride() != v_cache.stride() or k_cache.shape[0] != b or k_cache.shape[3] != d:
+        raise no(f"the caches must be two [B, Hkv, L, D] tensors of one shape and layout with q's B and D (got {tuple(k_cache.shape)}, {tuple(v_cache.shape)})")
+    hkv, max_len = k_cache.shape[1], k_cache.shape[2]
+    if hkv == 0 or max_len == 0:
+        raise no("empty caches")
+    if hq % hkv:
+        raise no(f"the kv heads must divide the query heads (got {hq}, {hkv})")
+    if d not in ATTN_DECODE_HEAD_DIMS:
+        raise no(f"head_dim 64 or 128 (got {d})")
+    if hq // hkv > ATTN_DECODE_MAX_GROUP:
+        raise no(f"at most {ATTN_DECODE_MAX_GROUP} query heads per kv head (got {hq // hkv})")
+    if b > 65535 or hq > 65535:
+        raise no(f"batch <= 65535 and q_heads <= 65535 (got {b}, {hq})")
+    if s > max_len:
+        raise no(f"the caches must hold the {s} query rows (got {max_len} positions)")
+    cs = [k_cache.stride(i) if k_cache.shape[i] > 1 else 0 for i in range(3)]
+    if k_cache.stride(3) != 1 or any(x % 8 or x < 0 for x in cs) or k_cache.data_ptr() % 16 or v_cache.data_ptr() % 16:
+        raise no(f"the caches must have contiguous head rows, 16-byte aligned, with strides that are multiples of 8 (got {tuple(k_cache.stride())})")
+    if isinstance(length, torch.Tensor):
+        if length.dim() != 0 or length.dtype != torch.int64 or length.device != q.device:
+            raise no("a length on the device must be a 0-d int64 tensor on q's device")
+        need = max_len
+    else:
+        need = int(length)
+        if need < s or need > max_len:
+            raise no(f"the length must lie in {s}..{max_len} (got {need})")
+    kind, mask_len, mask_batch, mask_row = _lib.ATTN_MASK_NONE, 0, 0, 0
+    if mask is not None:
+        m3 = mask[:, 0] if mask.dim() == 4 and mask.shape[1] == 1 else mask
+        if m3.dim() != 3 or m3.shape[0] not in (1, b) or m3.shape[1] != s or (m3.shape[2] > 1 and m3.stride(2) != 1):
+            raise no(f"the mask must be [B, 1, S, L] or [B, S, L] with B = {b} or 1, S = {s} and inner stride 1 (got {tuple(mask.shape)}, strides {tuple(mask.stride())})")
+        if mask.dtype == torch.bool:
+            kind = _lib.ATTN_MASK_BOOL
+        elif mask.dtype == q.dtype and mask.data_ptr() % 2 == 0:
+            kind = _lib.ATTN_MASK_ADDITIVE
+        else:
+            raise no(f"the mask must be bool or additive in {str(q.dtype)[6:]} (got {str(mask.dtype)[6:]})")
+        mask_len, mask_batch, mask_row = m3.shape[2], (m3.stride(0) if m3.shape[0] > 1 else 0), m3.stride(1)
+        if mask_len < need or mask_batch < 0 or mask_row < 0:
+            raise no(f"the mask must cover {need} positions (got {mask_len})")
+    return (b, hq, hkv, d, s, max_len) + tuple(qs) + tuple(cs) + (kind, mask_len, mask_batch, mask_row)
+
+
+def attn_prefill_describe(batch: int, q_heads: int, kv_heads: int, head_dim: int, q_len: int, max_len: int) -> str:
+    """The launch `attn_prefill` makes for these shapes ("attn_prefill q_tile=128 kv_tile=64 grid=2x32x1 group=4"), or "refused: ...".
+    Pure host code: a function of the shapes alone, never of the length."""
+    return _describe("qllm_attn_prefill_describe", 256, int(batch), int(q_heads), int(kv_heads), int(head_dim), int(q_len), int(max_len))
+
+
+def attn_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, length, mask: Optional[torch.Tensor] = None, causal: bool = True,
+                 scaling: Optional[float] = None, *, out=None, plan=None):
+    """softmax(scaling * q K^T + mask) V for S >= 2 query rows per sequence over the first `length` positions of the caches [B, Hkv, L, D],
+    which already hold the S new rows, as ONE kernel (qllm_attn_prefill, csrc/attn_prefill.hip): flash attention forward on MFMA, fp32
+    scores and softmax, one rounding at the store.  q: [B, Hq, S, D], any strides; returns [B, S, Hq, D] (contiguous: the rows o_proj
+    takes).  Query row i sits at position length - S + i; causal: key j counts for row i only if j <= length - S + i.  `length`: an int,
+    or a 0-d int64 tensor on the device that the kernel reads and clamps to S..L (a captured call then serves every length).  mask:
+    [B, 1, S, L'] or [B, S, L'], bool (True = visible) or additive, applied in addition to causality; a row with no visible key gives
+    zeros.  scaling: D ** -0.5 when None.  `attn_prefill_plan` says what is served; everything else raises QllmUnsupported before anything
+    is launched.  plan: what it returned for these very arguments."""
+    if plan is None:
+        plan = attn_prefill_plan(q, k_cache, v_cache, length, mask)
+    b, hq, hkv, d, s, max_len = plan[:6]
+    for t in (q, k_cache, v_cache):
+        if not t.is_cuda:
+            raise RuntimeError("attn_prefill: q and the caches must be HIP/CUDA tensors (qllm_amd has no CPU forward path)")
+    if out is None:
+        out = torch.empty((b, s, hq, d), dtype=q.dtype, device=q.device)
+    elif out.shape != (b, s, hq, d) or out.dtype != q.dtype or out.device != q.device or not out.is_contiguous():
+        raise RuntimeError(f"attn_prefill: out must be a contiguous {(b, s, hq, d)} {q.dtype} tensor on {q.device}")
+    on_device = isinstance(length, torch.Tensor)
+    with torch.cuda.device(q.device):
+        rc = _lib.load().qllm_attn_prefill(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), _ptr(mask), out.data_ptr(), b, hq, hkv, d, s,
+                                           0 if on_device else int(length), length.data_ptr() if on_device else None, max_len, *plan[6:16],
+                                           1 if causal else 0, float(d ** -0.5 if scaling is None else scaling), _act_dtype(q), _stream_ptr())
+    _lib.check(rc)
+    return out
+
+
 def dequant(w: QllmWeight, device: torch.device, dtype=torch.float16, transposed: bool = False) -> torch.Tensor:
     """W[K,N] (or [N,K]) bit-identical to the reference's DequantizeLinearBlockWise / unpack()."""
     lib = _lib.load()
