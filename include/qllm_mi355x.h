@@ -521,8 +521,8 @@ int qllm_rope(const void *q, const void *k, const void *cos, const void *sin, vo
  * a host kv_len outside 0..max_len (kv_len + 1 > max_len with an append), a mask too short.  QLLM_ERR_UNSUPPORTED: head_dim other than
  * 64 / 128, more than 8 query heads per kv head, batch * kv_heads > 4096.  QLLM_ERR_WORKSPACE: a missing, misaligned or small
  * workspace.  Every error is raised before any device work.  No host synchronisation; hipGraph-capturable.
- * Not built: sliding-window, quantized and paged caches, per-sequence lengths other than through the mask, rotary inside the kernel, an
- * fp8 cache.  More than one query token: qllm_attn_prefill below.
+ * Not built: a ring-buffer cache, chunked attention, quantized and paged caches, per-sequence lengths other than through the mask, rotary
+ * inside the kernel, an fp8 cache.  More than one query token: qllm_attn_prefill below.
  * ABI: the symbols are ADDITIVE within ABI 7 (QLLM_ABI_VERSION is unchanged): probe for them by symbol. */
 #define QLLM_ATTN_MASK_NONE 0
 #define QLLM_ATTN_MASK_BOOL 1
@@ -532,6 +532,19 @@ int qllm_attn_decode(const void *q, const void *k_new, const void *v_new, void *
                      int64_t q_head_stride, int64_t k_new_row_stride, int64_t k_new_head_stride, int64_t v_new_row_stride, int64_t v_new_head_stride,
                      int64_t cache_batch_stride, int64_t cache_head_stride, int64_t cache_pos_stride, int32_t mask_kind, int64_t mask_len,
                      int64_t mask_batch_stride, float scaling, int32_t act_dtype, void *workspace, size_t workspace_bytes, void *stream);
+/* qllm_attn_decode with a sliding window (transformers' sliding_window_overlay on a LINEAR cache: position j lives in slot j).  window =
+ * W >= 1: with n the number of counted positions (kv_len, + 1 with an append) the query sits at n - 1 and sees positions max(0, n - W) ..
+ * n - 1 only -- W keys including its own -- in addition to the length and the mask.  Positions below that are never loaded, a split wholly
+ * below it leaves at once and is not counted, and the lower end follows the length on the device: one captured launch serves lengths on
+ * both sides of the window.  A row whose keys inside the window are all masked stores zeros.  window = 0: no window, exactly
+ * qllm_attn_decode (which forwards here).  window < 0: QLLM_ERR_INVALID, before any device work.  Workspace, launch shape and the
+ * describe text do not depend on the window.  ADDITIVE within ABI 7: probe for it by symbol. */
+int qllm_attn_decode_window(const void *q, const void *k_new, const void *v_new, void *k_cache, void *v_cache, const void *mask, void *out, int32_t batch,
+                            int32_t q_heads, int32_t kv_heads, int32_t head_dim, int64_t kv_len, const int64_t *kv_len_dev, int64_t max_len, int64_t window,
+                            int64_t q_row_stride, int64_t q_head_stride, int64_t k_new_row_stride, int64_t k_new_head_stride, int64_t v_new_row_stride,
+                            int64_t v_new_head_stride, int64_t cache_batch_stride, int64_t cache_head_stride, int64_t cache_pos_stride, int32_t mask_kind,
+                            int64_t mask_len, int64_t mask_batch_stride, float scaling, int32_t act_dtype, void *workspace, size_t workspace_bytes,
+                            void *stream);
 /* The workspace qllm_attn_decode needs: the counter page and the splits' partial results.  Pure host code; shapes the entry refuses need
  * the page alone. */
 size_t qllm_attn_decode_workspace_bytes(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int64_t max_len);
@@ -562,14 +575,24 @@ int qllm_attn_decode_describe(int32_t batch, int32_t q_heads, int32_t kv_heads, 
  * multiple of 8, a negative mask stride, a host kv_len outside q_len..max_len, a mask shorter than kv_len (max_len with the length on the
  * device).  QLLM_ERR_UNSUPPORTED: head_dim other than 64 / 128, more than 8 query heads per kv head, q_heads or batch above 65535.  Every
  * error is raised before any device work.  No host synchronisation; hipGraph-capturable.
- * Not built: a split over the keys for short q_len behind long caches, sliding-window, quantized and paged caches, rotary or the cache
- * append inside the kernel, dropout, attention weights as an output, backward.
+ * Not built: a split over the keys for short q_len behind long caches, a ring-buffer cache, chunked attention, quantized and paged
+ * caches, rotary or the cache append inside the kernel, dropout, attention weights as an output, backward.
  * ABI: the symbols are ADDITIVE within ABI 7 (QLLM_ABI_VERSION is unchanged): probe for them by symbol. */
 int qllm_attn_prefill(const void *q, const void *k_cache, const void *v_cache, const void *mask, void *out, int32_t batch, int32_t q_heads,
                       int32_t kv_heads, int32_t head_dim, int32_t q_len, int64_t kv_len, const int64_t *kv_len_dev, int64_t max_len,
                       int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride, int64_t cache_batch_stride, int64_t cache_head_stride,
                       int64_t cache_pos_stride, int32_t mask_kind, int64_t mask_len, int64_t mask_batch_stride, int64_t mask_row_stride, int32_t causal,
                       float scaling, int32_t act_dtype, void *stream);
+/* qllm_attn_prefill with a sliding window on a linear cache.  window = W >= 1: row i at absolute position p = kv_len - q_len + i sees key j
+ * only if p - W < j <= p, in addition to the length and the mask.  A block reads no key tile wholly below the window of its first row;
+ * keys hidden by the window inside a tile it does read are loaded (weight exactly 0) and assumed finite.  window = 0: no window, exactly
+ * qllm_attn_prefill (which forwards here).  window < 0: QLLM_ERR_INVALID; window >= 1 with causal = 0: QLLM_ERR_UNSUPPORTED; both before
+ * any device work.  The launch shape does not depend on the window.  ADDITIVE within ABI 7: probe for it by symbol. */
+int qllm_attn_prefill_window(const void *q, const void *k_cache, const void *v_cache, const void *mask, void *out, int32_t batch, int32_t q_heads,
+                             int32_t kv_heads, int32_t head_dim, int32_t q_len, int64_t kv_len, const int64_t *kv_len_dev, int64_t max_len, int64_t window,
+                             int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride, int64_t cache_batch_stride, int64_t cache_head_stride,
+                             int64_t cache_pos_stride, int32_t mask_kind, int64_t mask_len, int64_t mask_batch_stride, int64_t mask_row_stride,
+                             int32_t causal, float scaling, int32_t act_dtype, void *stream);
 /* What a call would launch, as text: "attn_prefill q_tile=128 kv_tile=64 grid=2x32x1 group=4", or "refused: " and the refusal text.  Pure
  * host code. */
 int qllm_attn_prefill_describe(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t q_len, int64_t max_len, char *buf,

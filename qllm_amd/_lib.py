@@ -114,6 +114,10 @@ SIGNATURES = {
     "qllm_attn_prefill": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i64, vp, i64, i64, i64, i64, i64, i64, i64, i32, i64, i64, i64, i32,
                                     C.c_float, i32, vp]),
     "qllm_attn_prefill_describe": (C.c_int, [i32, i32, i32, i32, i32, i64, C.c_char_p, sz]),
+    "qllm_attn_decode_window": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i64, vp, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, i32,
+                                          i64, i64, C.c_float, i32, vp, sz, vp]),
+    "qllm_attn_prefill_window": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i64, vp, i64, i64, i64, i64, i64, i64, i64, i64, i32, i64, i64, i64,
+                                           i32, C.c_float, i32, vp]),
 }
 EXPORTS = tuple(SIGNATURES)
 

@@ -20,6 +20,13 @@
 // length, and the arrival counter counts those only.  kv_len is a host integer or an int64 in device
 // memory.  Positions >= kv_len are NEVER loaded.
 //
+// Sliding window (window = W >= 1; 0: none; the WIN instantiations of the kernel, compiled in attn_decode_window.hip).  With n the
+// number of counted positions (an append included) the query sits at n - 1 and sees positions lo = max(0, n - W) .. n - 1, W keys
+// with its own, in addition to the length and the mask.  Positions < lo are NEVER
+// loaded either: a split wholly below lo leaves at once like one beyond the length, the split that holds lo starts its walk AT lo, and
+// the last block combines the splits from that one on in split order.  lo follows the length, so one captured launch serves lengths on
+// both sides of the window; grid and splits do not depend on it.  A row whose keys inside the window are all masked stores zeros.
+//
 // Append.  With k_new / v_new, position kv_len is the new token: the lane group that owns that position reads the two rows from k_new /
 // v_new, stores them into the caches and uses them; no other block touches that position.  If kv_len + 1 > L_max (only possible with the
 // length on the device: the entry refuses it on the host) nothing is stored and the first L_max positions are attended.
@@ -29,324 +36,12 @@
 // a bf16 bias that is finite, above the lowest finite number and below about -7e29 has exp2(s - kNoMax) = 0: a row whose visible keys ALL
 // carry such a bias stores zeros instead of a softmax among them (fp16 has no such value; transformers masks with finfo.min).
 //
-// Not built: sliding-window and quantized caches, paged caches, per-sequence lengths other than through the mask,
-// head_dim other than 64 / 128, rotary inside the kernel, an fp8 cache, P.V on MFMA.  More than one query token: attn_prefill.hip.
-#include "kernels.hpp"
+// Not built: a ring-buffer cache (position j lives in slot j), chunked attention, quantized caches, paged caches, per-sequence lengths
+// other than through the mask, head_dim other than 64 / 128, rotary inside the kernel, an fp8 cache, P.V on MFMA.  More than one query
+// token: attn_prefill.hip.
+#include "attn_decode_kernel.hpp"
 
 namespace qllm {
-
-namespace {
-
-constexpr int kU = 4;          // wave loads of K (and of V) per block step
-constexpr int kCombine = 8;    // splits whose partial results the combining block loads at a time
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kNoMax = -1e30f;  // the running maximum before any visible key: finite, so that exp2(m - m) never sees inf - inf
-
-template <int CTRL>
-__device__ __forceinline__ float ad_dpp_add(float v) {
-  return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-// sum over the LPP (8 or 16) lanes that share a position; every one of them gets it
-template <int LPP>
-__device__ __forceinline__ float ad_group_sum(float v) {
-  v = ad_dpp_add<0xB1>(v);   // quad_perm [1,0,3,2]
-  v = ad_dpp_add<0x4E>(v);   // quad_perm [2,3,0,1]
-  v = ad_dpp_add<0x141>(v);  // row_half_mirror
-  if constexpr (LPP == 16) v = ad_dpp_add<0x140>(v);  // row_mirror
-  return v;
-}
-template <bool BF16>
-__device__ __forceinline__ void ad_unpack(uint4_t v, float (&f)[8]) {
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    if constexpr (BF16) {
-      f[2 * i] = __builtin_bit_cast(float, w[i] << 16);
-      f[2 * i + 1] = __builtin_bit_cast(float, w[i] & 0xffff0000u);
-    } else {
-      const half2_t h = __builtin_bit_cast(half2_t, w[i]);
-      f[2 * i] = (float)h.x;
-      f[2 * i + 1] = (float)h.y;
-    }
-  }
-}
-template <bool BF16>
-__device__ __forceinline__ uint32_t ad_round(float f) {
-  if constexpr (BF16) return f32_to_bf16(f);
-  else return __builtin_bit_cast(uint16_t, (half_t)f);
-}
-template <bool BF16>
-__device__ __forceinline__ uint4_t ad_pack(const float (&f)[8]) {
-  uint32_t w[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) w[i] = ad_round<BF16>(f[2 * i]) | (ad_round<BF16>(f[2 * i + 1]) << 16);
-  return uint4_t{w[0], w[1], w[2], w[3]};
-}
-__device__ __forceinline__ float ad_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-// (m, l, a[8]) <- the softmax state of both key sets; symmetric in its two arguments, bit for bit
-__device__ __forceinline__ void ad_merge(float &m, float &l, float (&a)[8], float m2, float l2, const float (&a2)[8]) {
-  const float mx = fmaxf(m, m2), f = ad_exp2(m - mx), f2 = ad_exp2(m2 - mx);
-  l = l * f + l2 * f2;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) a[e] = a[e] * f + a2[e] * f2;
-  m = mx;
-}
-
-template <bool BF16, int D, int G>
-__global__ __launch_bounds__(256) void attn_decode_kernel(const AttnDecodeParams p) {
-  constexpr int LPP = D / 8, GPW = 64 / LPP, TILE = 4 * GPW * kU;
-  constexpr int ROW = D + 2, PROW = D + 4;  // m, l, acc[D] of one query head in LDS; m, l, two pads, acc[D] in the workspace (16-byte pieces)
-  __shared__ float red[4 * G * ROW + 1];
-  int &s_ticket = *(int *)(red + 4 * G * ROW);  // (one LDS object: the ticket lives behind the waves' rows)
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, grp = lane / LPP, sub = lane % LPP;
-  const int split = blockIdx.x, kvh = blockIdx.y, b = blockIdx.z;
-  const int S = gridDim.x;
-
-  int64_t len = p.kv_len_dev ? *p.kv_len_dev : p.kv_len;
-  len = len < 0 ? 0 : len > p.max_len ? p.max_len : len;
-  const bool append = p.k_new != nullptr && len < p.max_len;
-  const int64_t n = len + (append ? 1 : 0), app_pos = append ? len : -1;  // n <= max_len positions count
-  const int64_t beg = (int64_t)split * p.chunk, end = beg + p.chunk < n ? beg + p.chunk : n;
-  // the splits that hold a position < n.  Every block knows the number, so a block beyond it leaves at once -- it has nothing to hand
-  // over, and the arrival counter counts the live blocks only -- except that with no position at all split 0 stores the zeros.
-  const int live = (int)((n + p.chunk - 1) / p.chunk);
-  if (split >= live && (split > 0 || live > 0)) return;
-
-  const uint4_t *kc = (const uint4_t *)p.k_cache + ((int64_t)b * p.c_batch + (int64_t)kvh * p.c_head) / 8 + sub;
-  const uint4_t *vc = (const uint4_t *)p.v_cache + ((int64_t)b * p.c_batch + (int64_t)kvh * p.c_head) / 8 + sub;
-  const int64_t cpos = p.c_pos / 8;
-
-  if (beg < end) {
-    float qf[G][8], acc[G][8], m[G], l[G];
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      const uint4_t qv = *((const uint4_t *)p.q + ((int64_t)b * p.q_row + (int64_t)(kvh * G + g) * p.q_head) / 8 + sub);
-      ad_unpack<BF16>(qv, qf[g]);
-      m[g] = kNoMax;
-      l[g] = 0.f;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) acc[g][e] = 0.f;
-    }
-    const uint4_t *kn = p.k_new ? (const uint4_t *)p.k_new + ((int64_t)b * p.kn_row + (int64_t)kvh * p.kn_head) / 8 + sub : nullptr;
-    const uint4_t *vn = p.v_new ? (const uint4_t *)p.v_new + ((int64_t)b * p.vn_row + (int64_t)kvh * p.vn_head) / 8 + sub : nullptr;
-    const uint8_t *mask8 = (const uint8_t *)p.mask + (int64_t)b * p.mask_batch;
-    const uint16_t *mask16 = (const uint16_t *)p.mask + (int64_t)b * p.mask_batch;
-
-    // one tile: K and V rows of this lane's kU positions (zeros where there is none) and what the mask adds to their scores: 0, a finite
-    // value, or -inf (hidden, or no such position)
-    auto load_tile = [&](int64_t base, uint4_t (&kk)[kU], uint4_t (&vv)[kU], float (&bias)[kU]) {
-#pragma unroll
-      for (int u = 0; u < kU; ++u) {
-        const int64_t pos = base + (u * 4 + wave) * GPW + grp;
-        kk[u] = vv[u] = uint4_t{0u, 0u, 0u, 0u};
-        bias[u] = -INFINITY;
-        if (pos < end) {
-          if (pos == app_pos) {
-            kk[u] = *kn;
-            vv[u] = *vn;
-            *((uint4_t *)kc + pos * cpos) = kk[u];
-            *((uint4_t *)vc + pos * cpos) = vv[u];
-          } else {
-            kk[u] = kc[pos * cpos];
-            vv[u] = vc[pos * cpos];
-          }
-          bias[u] = 0.f;
-          if (p.mask_kind == 1) {
-            if (!mask8[pos]) bias[u] = -INFINITY;
-          } else if (p.mask_kind == 2) {
-            const uint32_t raw = mask16[pos];
-            const float a = BF16 ? __builtin_bit_cast(float, raw << 16) : (float)__builtin_bit_cast(half_t, (uint16_t)raw);
-            bias[u] = a <= (BF16 ? -3.3895313892515355e38f : -65504.f) ? -INFINITY : a;
-          }
-        }
-      }
-    };
-    uint4_t kk[kU], vv[kU], nk[kU], nv[kU];
-    float bias[kU], nbias[kU];
-    load_tile(beg, kk, vv, bias);
-    for (int64_t base = beg; base < end; base += TILE) {
-      load_tile(base + TILE, nk, nv, nbias);  // the next tile is on its way while this one is computed (nothing is loaded past `end`)
-      float s[kU][G];
-#pragma unroll
-      for (int u = 0; u < kU; ++u) {
-        float kf[8];
-        ad_unpack<BF16>(kk[u], kf);
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-          float d = 0.f;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) d = __builtin_fmaf(qf[g][e], kf[e], d);
-          s[u][g] = (p.scaling * ad_group_sum<LPP>(d) + bias[u]) * kLog2e;
-        }
-      }
-      float pw[kU][G];
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        float mx = m[g];
-#pragma unroll
-        for (int u = 0; u < kU; ++u) mx = fmaxf(mx, s[u][g]);
-        const float alpha = ad_exp2(m[g] - mx);
-        float sum = 0.f;
-#pragma unroll
-        for (int u = 0; u < kU; ++u) {
-          pw[u][g] = ad_exp2(s[u][g] - mx);
-          sum += pw[u][g];
-        }
-        l[g] = l[g] * alpha + sum;
-        m[g] = mx;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[g][e] *= alpha;
-      }
-#pragma unroll
-      for (int u = 0; u < kU; ++u) {
-        float vf[8];
-        ad_unpack<BF16>(vv[u], vf);
-#pragma unroll
-        for (int g = 0; g < G; ++g)
-#pragma unroll
-          for (int e = 0; e < 8; ++e) acc[g][e] = __builtin_fmaf(pw[u][g], vf[e], acc[g][e]);
-      }
-#pragma unroll
-      for (int u = 0; u < kU; ++u) kk[u] = nk[u], vv[u] = nv[u], bias[u] = nbias[u];
-    }
-    // the lane groups of the wave: xor shuffles (both partners compute the same bits), then lane group 0 holds the wave's state
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-#pragma unroll
-      for (int x = LPP; x < 64; x <<= 1) {
-        float a2[8];
-        const float m2 = __shfl_xor(m[g], x, 64), l2 = __shfl_xor(l[g], x, 64);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) a2[e] = __shfl_xor(acc[g][e], x, 64);
-        ad_merge(m[g], l[g], acc[g], m2, l2, a2);
-      }
-      if (grp == 0) {
-        float *row = red + (wave * G + g) * ROW;
-        if (sub == 0) {
-          row[0] = m[g];
-          row[1] = l[g];
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) row[2 + 8 * sub + e] = acc[g][e];
-      }
-    }
-  }
-  __syncthreads();
-
-  // thread (g, sub) of the first G * LPP: chunk `sub` of query head g
-  const bool owner = tid < G * LPP;
-  const int g = tid / LPP;
-  float M = kNoMax, L = 0.f, A[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (owner && beg < end) {
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const float *row = red + (w * G + g) * ROW;
-      float a2[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) a2[e] = row[2 + 8 * sub + e];
-      ad_merge(M, L, A, row[0], row[1], a2);
-    }
-  }
-  if (live > 1) {
-    // the hand-off of strip1_body.inc: 16-byte stores, drained by every wave; one lane's agent-scope release; one relaxed agent-scope
-    // ticket per (batch, kv head); the last of the live blocks to arrive re-arms the counter, acquires, and combines them in split order
-    // with 16-byte loads.  (One live split: its block stores directly.)
-    const int bh = b * gridDim.y + kvh;
-    float4_t *part = (float4_t *)(p.partials + ((size_t)bh * S) * (G * PROW));
-    if (owner) {
-      float4_t *row = part + ((size_t)split * G + g) * (PROW / 4);
-      if (sub == 0) row[0] = float4_t{M, L, 0.f, 0.f};
-      row[1 + 2 * sub] = float4_t{A[0], A[1], A[2], A[3]};
-      row[2 + 2 * sub] = float4_t{A[4], A[5], A[6], A[7]};
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the stores have left every wave ...
-    __syncthreads();
-    if (tid == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");  // ... and are visible to the device before the ticket says so
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      s_ticket = __hip_atomic_fetch_add(p.counters + bh, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    if (s_ticket != live - 1) return;
-    if (tid == 0) {
-      __hip_atomic_store(p.counters + bh, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // the other blocks' tickets, and the stores in front of them
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __syncthreads();
-    // The combine, in split order: the block's threads form R sets of G * LPP owners; set r folds the r-th run of consecutive live splits
-    // from left to right (kCombine splits' loads issued together, then merged one after the other), and the R results are folded in the
-    // order of the runs.  The association is fixed by (live, R) alone, so the bits do not depend on which block arrives last.
-    constexpr int R = G * LPP <= 64 ? 4 : 2, SET = 256 / R;
-    const int r = tid / SET, t = tid % SET, cg = t / LPP, csub = t % LPP;
-    const int per = (live + R - 1) / R, s_beg = r * per, s_end = s_beg + per < live ? s_beg + per : live;
-    M = kNoMax;
-    L = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) A[e] = 0.f;
-    if (t < G * LPP) {
-      for (int sp0 = s_beg; sp0 < s_end; sp0 += kCombine) {
-        float4_t ml[kCombine], lo[kCombine], hi[kCombine];
-#pragma unroll
-        for (int j = 0; j < kCombine; ++j) {
-          const int sp = sp0 + j < s_end ? sp0 + j : s_end - 1;  // (past the run's last: loaded again, not merged)
-          const float4_t *row = part + ((size_t)sp * G + cg) * (PROW / 4);
-          ml[j] = row[0], lo[j] = row[1 + 2 * csub], hi[j] = row[2 + 2 * csub];
-        }
-#pragma unroll
-        for (int j = 0; j < kCombine; ++j) {
-          const float a2[8] = {lo[j].x, lo[j].y, lo[j].z, lo[j].w, hi[j].x, hi[j].y, hi[j].z, hi[j].w};
-          if (sp0 + j < s_end) ad_merge(M, L, A, ml[j].x, ml[j].y, a2);
-        }
-      }
-      float *row = red + (r * G + cg) * ROW;  // (the waves' rows were read two barriers ago)
-      if (csub == 0) {
-        row[0] = M;
-        row[1] = L;
-      }
-#pragma unroll
-      for (int e = 0; e < 8; ++e) row[2 + 8 * csub + e] = A[e];
-    }
-    __syncthreads();
-    if (!owner) return;
-    M = kNoMax;
-    L = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) A[e] = 0.f;
-#pragma unroll
-    for (int rr = 0; rr < R; ++rr) {
-      const float *row = red + (rr * G + g) * ROW;
-      float a2[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) a2[e] = row[2 + 8 * sub + e];
-      ad_merge(M, L, A, row[0], row[1], a2);
-    }
-  }
-  if (!owner) return;
-  float o[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = L > 0.f ? A[e] / L : 0.f;  // no visible key: zeros
-  *((uint4_t *)p.out + ((int64_t)b * p.q_heads + kvh * G + g) * LPP + sub) = ad_pack<BF16>(o);
-}
-
-template <bool BF16, int D>
-int launch_d(const AttnDecodeParams &p, int G, dim3 grid, hipStream_t stream) {
-  switch (G) {
-#define QLLM_AD_CASE(GG)                                                                          \
-  case GG:                                                                                        \
-    hipLaunchKernelGGL((attn_decode_kernel<BF16, D, GG>), grid, dim3(256), 0, stream, p);         \
-    break;
-    QLLM_AD_CASE(1) QLLM_AD_CASE(2) QLLM_AD_CASE(3) QLLM_AD_CASE(4) QLLM_AD_CASE(5) QLLM_AD_CASE(6) QLLM_AD_CASE(7) QLLM_AD_CASE(8)
-#undef QLLM_AD_CASE
-    default:
-      return set_error(QLLM_ERR_UNSUPPORTED, "attn_decode serves 1..%d query heads per kv head (got %d)", kAttnDecodeMaxGroup, G);
-  }
-  QLLM_HIP_CHECK(hipGetLastError());
-  return QLLM_OK;
-}
-
-}  // namespace
 
 // tile: positions per block step; splits: blocks per (batch, kv head), about two blocks per compute unit in all, at most kAttnDecodeMaxSplits
 // and one per tile; chunk: positions per split, a multiple of the tile.  A function of the shapes and the CU count alone.
@@ -367,12 +62,10 @@ AttnDecodeGeom attn_decode_geom(int batch, int q_heads, int kv_heads, int head_d
   return g;
 }
 
-// shapes, strides and alignment checked by the entry (capi.hip); p.splits / p.chunk from attn_decode_geom
+// the kernels without a window are this unit's, those with one attn_decode_window.hip's
 int launch_attn_decode(const AttnDecodeParams &p, int head_dim, int act_bf16, hipStream_t stream) {
-  const dim3 grid((unsigned)p.splits, (unsigned)p.kv_heads, (unsigned)p.batch);
-  const int G = p.q_heads / p.kv_heads;
-  if (head_dim == 128) return act_bf16 ? launch_d<true, 128>(p, G, grid, stream) : launch_d<false, 128>(p, G, grid, stream);
-  return act_bf16 ? launch_d<true, 64>(p, G, grid, stream) : launch_d<false, 64>(p, G, grid, stream);
+  if (p.window > 0) return launch_attn_decode_window(p, head_dim, act_bf16, stream);
+  return launch_attn_decode_variant<false>(p, head_dim, act_bf16, stream);
 }
 
 }  // namespace qllm

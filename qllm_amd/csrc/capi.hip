@@ -1059,10 +1059,22 @@ int qllm_attn_decode(const void *q, const void *k_new, const void *v_new, void *
                      int64_t q_head_stride, int64_t k_new_row_stride, int64_t k_new_head_stride, int64_t v_new_row_stride, int64_t v_new_head_stride,
                      int64_t cache_batch_stride, int64_t cache_head_stride, int64_t cache_pos_stride, int32_t mask_kind, int64_t mask_len,
                      int64_t mask_batch_stride, float scaling, int32_t act_dtype, void *workspace, size_t workspace_bytes, void *stream) {
+  return qllm_attn_decode_window(q, k_new, v_new, k_cache, v_cache, mask, out, batch, q_heads, kv_heads, head_dim, kv_len, kv_len_dev, max_len, 0, q_row_stride,
+                                 q_head_stride, k_new_row_stride, k_new_head_stride, v_new_row_stride, v_new_head_stride, cache_batch_stride, cache_head_stride,
+                                 cache_pos_stride, mask_kind, mask_len, mask_batch_stride, scaling, act_dtype, workspace, workspace_bytes, stream);
+}
+
+int qllm_attn_decode_window(const void *q, const void *k_new, const void *v_new, void *k_cache, void *v_cache, const void *mask, void *out, int32_t batch,
+                            int32_t q_heads, int32_t kv_heads, int32_t head_dim, int64_t kv_len, const int64_t *kv_len_dev, int64_t max_len, int64_t window,
+                            int64_t q_row_stride, int64_t q_head_stride, int64_t k_new_row_stride, int64_t k_new_head_stride, int64_t v_new_row_stride,
+                            int64_t v_new_head_stride, int64_t cache_batch_stride, int64_t cache_head_stride, int64_t cache_pos_stride, int32_t mask_kind,
+                            int64_t mask_len, int64_t mask_batch_stride, float scaling, int32_t act_dtype, void *workspace, size_t workspace_bytes,
+                            void *stream) {
   clear_error();
   if (!q || !k_cache || !v_cache || !out) return set_error(QLLM_ERR_INVALID, "q / k_cache / v_cache / out must not be NULL");
   int rc = check_attn_decode_shape(batch, q_heads, kv_heads, head_dim, max_len);
   if (rc != QLLM_OK) return rc;
+  if (window < 0) return set_error(QLLM_ERR_INVALID, "window must be 0 (none) or >= 1 (got %lld)", (long long)window);
   if (act_dtype != QLLM_F16 && act_dtype != QLLM_BF16) return set_error(QLLM_ERR_INVALID, "act_dtype must be QLLM_F16 or QLLM_BF16");
   if (mask_kind != QLLM_ATTN_MASK_NONE && mask_kind != QLLM_ATTN_MASK_BOOL && mask_kind != QLLM_ATTN_MASK_ADDITIVE)
     return set_error(QLLM_ERR_INVALID, "mask_kind must be QLLM_ATTN_MASK_NONE, _BOOL or _ADDITIVE (got %d)", mask_kind);
@@ -1091,7 +1103,7 @@ int qllm_attn_decode(const void *q, const void *k_new, const void *v_new, void *
 
   AttnDecodeParams p;
   p.q = q, p.k_new = k_new, p.v_new = v_new, p.k_cache = k_cache, p.v_cache = v_cache, p.mask = mask, p.out = out;
-  p.kv_len_dev = kv_len_dev, p.kv_len = kv_len, p.max_len = max_len;
+  p.kv_len_dev = kv_len_dev, p.kv_len = kv_len, p.max_len = max_len, p.window = window;
   p.q_row = q_row_stride, p.q_head = q_head_stride, p.kn_row = k_new_row_stride, p.kn_head = k_new_head_stride, p.vn_row = v_new_row_stride,
   p.vn_head = v_new_head_stride, p.c_batch = cache_batch_stride, p.c_head = cache_head_stride, p.c_pos = cache_pos_stride, p.mask_batch = mask_batch_stride;
   p.chunk = g.chunk, p.batch = batch, p.q_heads = q_heads, p.kv_heads = kv_heads, p.mask_kind = mask_kind, p.splits = g.splits, p.scaling = scaling;
@@ -1136,10 +1148,21 @@ int qllm_attn_prefill(const void *q, const void *k_cache, const void *v_cache, c
                       int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride, int64_t cache_batch_stride, int64_t cache_head_stride,
                       int64_t cache_pos_stride, int32_t mask_kind, int64_t mask_len, int64_t mask_batch_stride, int64_t mask_row_stride, int32_t causal,
                       float scaling, int32_t act_dtype, void *stream) {
+  return qllm_attn_prefill_window(q, k_cache, v_cache, mask, out, batch, q_heads, kv_heads, head_dim, q_len, kv_len, kv_len_dev, max_len, 0, q_batch_stride,
+                                  q_head_stride, q_row_stride, cache_batch_stride, cache_head_stride, cache_pos_stride, mask_kind, mask_len, mask_batch_stride,
+                                  mask_row_stride, causal, scaling, act_dtype, stream);
+}
+
+int qllm_attn_prefill_window(const void *q, const void *k_cache, const void *v_cache, const void *mask, void *out, int32_t batch, int32_t q_heads,
+                             int32_t kv_heads, int32_t head_dim, int32_t q_len, int64_t kv_len, const int64_t *kv_len_dev, int64_t max_len, int64_t window,
+                             int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride, int64_t cache_batch_stride, int64_t cache_head_stride,
+                             int64_t cache_pos_stride, int32_t mask_kind, int64_t mask_len, int64_t mask_batch_stride, int64_t mask_row_stride,
+                             int32_t causal, float scaling, int32_t act_dtype, void *stream) {
   clear_error();
   if (!q || !k_cache || !v_cache || !out) return set_error(QLLM_ERR_INVALID, "q / k_cache / v_cache / out must not be NULL");
   int rc = check_attn_prefill_shape(batch, q_heads, kv_heads, head_dim, q_len, max_len);
   if (rc != QLLM_OK) return rc;
+  if (window < 0) return set_error(QLLM_ERR_INVALID, "window must be 0 (none) or >= 1 (got %lld)", (long long)window);
   if (act_dtype != QLLM_F16 && act_dtype != QLLM_BF16) return set_error(QLLM_ERR_INVALID, "act_dtype must be QLLM_F16 or QLLM_BF16");
   if (mask_kind != QLLM_ATTN_MASK_NONE && mask_kind != QLLM_ATTN_MASK_BOOL && mask_kind != QLLM_ATTN_MASK_ADDITIVE)
     return set_error(QLLM_ERR_INVALID, "mask_kind must be QLLM_ATTN_MASK_NONE, _BOOL or _ADDITIVE (got %d)", mask_kind);
@@ -1162,10 +1185,11 @@ int qllm_attn_prefill(const void *q, const void *k_cache, const void *v_cache, c
                      (long long)mask_row_stride);
   rc = check_attn_prefill_served(batch, q_heads, kv_heads, head_dim);
   if (rc != QLLM_OK) return rc;
+  if (window > 0 && !causal) return set_error(QLLM_ERR_UNSUPPORTED, "attn_prefill serves a sliding window on causal calls only (got window=%lld causal=0)", (long long)window);
 
   AttnPrefillParams p;
   p.q = q, p.k_cache = k_cache, p.v_cache = v_cache, p.mask = mask, p.out = out;
-  p.kv_len_dev = kv_len_dev, p.kv_len = kv_len, p.max_len = max_len;
+  p.kv_len_dev = kv_len_dev, p.kv_len = kv_len, p.max_len = max_len, p.window = window;
   p.q_batch = q_batch_stride, p.q_head = q_head_stride, p.q_row = q_row_stride, p.c_batch = cache_batch_stride, p.c_head = cache_head_stride,
   p.c_pos = cache_pos_stride, p.mask_batch = mask_batch_stride, p.mask_row = mask_row_stride;
   p.batch = batch, p.q_heads = q_heads, p.kv_heads = kv_heads, p.q_len = q_len, p.mask_kind = mask_kind, p.causal = causal, p.scaling = scaling;

@@ -298,6 +298,7 @@ struct AttnDecodeParams {
   float scaling;
   float *partials;                // [batch * kv_heads][splits][G][4 + head_dim] fp32: m, l, two pads, acc
   int *counters;                  // one arrival counter per (batch entry, kv head) (zero before and after the launch)
+  int64_t window;                 // 0: none; W >= 1: the query sees the last W counted positions only (the last field)
 };
 struct AttnDecodeGeom {
   int tile, splits;
@@ -306,6 +307,7 @@ struct AttnDecodeGeom {
 };
 AttnDecodeGeom attn_decode_geom(int batch, int q_heads, int kv_heads, int head_dim, int64_t max_len);
 int launch_attn_decode(const AttnDecodeParams &p, int head_dim, int act_bf16, hipStream_t stream);
+int launch_attn_decode_window(const AttnDecodeParams &p, int head_dim, int act_bf16, hipStream_t stream);  // p.window >= 1 (attn_decode_window.hip)
 
 // ---- attn_prefill.hip: q_len >= 2 query rows per sequence against the first kv_len positions of a KV cache (flash attention forward) -----
 constexpr int kAttnPrefillQTile = 128;  // query rows per block: 32 per wave
@@ -319,8 +321,10 @@ struct AttnPrefillParams {
   int64_t q_batch, q_head, q_row, c_batch, c_head, c_pos, mask_batch, mask_row;  // strides in elements
   int batch, q_heads, kv_heads, q_len, mask_kind, causal;
   float scaling;
+  int64_t window;                 // 0: none; W >= 1 (causal only): row i sees keys q_start + i - W + 1 .. q_start + i (the last field)
 };
 int launch_attn_prefill(const AttnPrefillParams &p, int head_dim, int act_bf16, hipStream_t stream);
+int launch_attn_prefill_window(const AttnPrefillParams &p, int head_dim, int act_bf16, hipStream_t stream);  // p.window >= 1 (attn_prefill_window.hip)
 
 // ---- native.hip (reference layouts <-> the strip-major native layout) -------------------------------------------------------
 int launch_repack_native(const qllm_weight_t &src, int zero_kind, void *qweight_out, void *scales_out, void *qzeros_out, hipStream_t stream);

@@ -8,9 +8,10 @@ row once for all query heads of its group, and takes the length from device memo
 `install_fused_attention` gives each whitelisted attention INSTANCE the restated forward of fused_rope.py (one text for both installs: the
 class's data flow, no transformers global touched) with `_fused_core` behind the rotary embedding.  The core serves a call when q_len == 1,
 q / k / v are device tensors of one fp16 / bf16 type, nothing is being differentiated, the module is not training, the attention
-implementation is sdpa or eager, no sliding window reaches the call, no kwarg changes the mathematics, the mask is None or one of the two
-forms transformers builds at q_len == 1 ([B, 1, 1, L] bool or additive), the cache layer is EXACTLY a DynamicLayer or an initialised
-StaticLayer of a cache that does not offload, and `ops.attn_decode_plan` serves the shapes:
+implementation is sdpa or eager, no kwarg changes the mathematics (a `sliding_window` handed in by the caller does), the mask is None or
+one of the two forms transformers builds at q_len == 1 ([B, 1, 1, L] bool or additive), the cache layer is EXACTLY a DynamicLayer or an
+initialised StaticLayer of a cache that does not offload -- with a sliding window W (config.sliding_window for Mistral, the module's own
+for Qwen2) EXACTLY one of the two sliding layers below -- and `ops.attn_decode_plan` serves the shapes:
 
   DynamicLayer  `update` as before, then the kernel over what it returned with the host length.
   StaticLayer   `update` as before, then the kernel over the layer's buffers with the length read from `layer.cumulative_length` on the
@@ -18,8 +19,25 @@ StaticLayer of a cache that does not offload, and `ops.attn_decode_plan` serves 
                 -- needs a host-side bound on the length that holds across `reset`, `crop` and foreign updates of the layer; it is not
                 used here.)
 
-Everything else -- sliding layers, quantized and offloaded caches, no cache, CPU and fp32 tensors, training, output_attentions --
-runs the family's own route unchanged.  Composes with install_fused_rope and the other installs in any order.
+  DynamicSlidingWindowLayer   of that very window W, not recording its past: `update` as before (it returns the W - 1 positions it kept
+                and the new ones), then the kernel over what it returned with the host length and `window=W`.
+  StaticSlidingWindowLayer    that holds at most W positions: `update` as before, then the kernel with `window=W` over what it returned:
+                the layer's buffers with the length from `layer.cumulative_length` on the device while `layer.cumulative_length_int <=
+                layer.max_cache_len`; once the layer has overflowed it stops updating that tensor (a 5-token prompt into a window of 4
+                leaves it at 0), and everything `update` returns is valid: the host length.  The layer branches on a Python int at the
+                point where it fills (index_copy before, roll or cat after), fused or not, so a manually captured step cannot cross that
+                point: capture before it or after it.  Past it the layer rolls its whole buffer at every token; a ring-buffer layer of
+                our own would remove that and is not built, nor are chunked attention and `record_past`.
+On the full layers the calls carry no `window`.  On the sliding ones a decode call carries it, but it hides nothing there: a dynamic
+sliding layer returns at most W positions and a static one holds at most W, so the lowest visible position is 0 and the windowed kernel
+reads what the kernel without a window would.  The decode window skips keys only for direct callers of `ops.attn_decode` on a linear
+cache longer than the window; through the modules the gain at decode is that sliding layers are served at all (the valid keys, the
+length from the device), and the window itself pays at prefill, where `update` returns more than W positions.
+QLLM_FUSE_ATTENTION_SLIDING=0 puts every call that a window reaches back on the family's route.
+
+Everything else -- a window on a full layer, a sliding layer without a window or of another window, subclasses of the sliding layers,
+quantized and offloaded caches, no cache, CPU and fp32 tensors, training, output_attentions -- runs the family's own route unchanged.
+Composes with install_fused_rope and the other installs in any order.
 Opt-in: `load_quantized(..., fuse_attention=True)`.
 
 Prefill (q_len >= 2) runs the family's route unless the install is made with `prefill=True` (`load_quantized(...,
@@ -45,19 +63,39 @@ def _on_device(*ts) -> bool:
     return all(t.is_cuda for t in ts)
 
 
-def _layer_of(past_key_values, layer_idx, uninitialized=False):
-    """The cache layer the core may serve -- exactly a DynamicLayer or an initialised StaticLayer (with `uninitialized`: any StaticLayer)
-    of a cache that does not offload -- else None."""
-    from transformers.cache_utils import DynamicLayer, StaticLayer
+def _layer_of(past_key_values, layer_idx, uninitialized=False, sliding=None):
+    """(the cache layer the core may serve, its kind) or (None, None).  Without a window (`sliding` None): exactly a DynamicLayer
+    ("dynamic") or an initialised StaticLayer ("static"; with `uninitialized`: any StaticLayer).  With the window W of the call: exactly a
+    DynamicSlidingWindowLayer of that window that does not record its past ("dynamic_sliding"), or exactly a StaticSlidingWindowLayer
+    (initialised, or any with `uninitialized`) that holds at most W positions ("static_sliding"), unless QLLM_FUSE_ATTENTION_SLIDING=0.
+    Always of a cache that does not offload; a window on a full layer, a sliding layer without one and subclasses are not served."""
+    from transformers.cache_utils import DynamicLayer, DynamicSlidingWindowLayer, StaticLayer, StaticSlidingWindowLayer
     layers = getattr(past_key_values, "layers", None)
     if not isinstance(layers, list) or not isinstance(layer_idx, int) or not 0 <= layer_idx < len(layers) or getattr(past_key_values, "offloading", False):
-        return None
+        return None, None
     layer = layers[layer_idx]
-    if type(layer) is DynamicLayer:
-        return layer
-    if type(layer) is StaticLayer and (layer.is_initialized or uninitialized):
-        return layer
-    return None
+    if sliding is None:
+        if type(layer) is DynamicLayer:
+            return layer, "dynamic"
+        if type(layer) is StaticLayer and (layer.is_initialized or uninitialized):
+            return layer, "static"
+        return None, None
+    if isinstance(sliding, bool) or not isinstance(sliding, int) or sliding < 1 or os.environ.get("QLLM_FUSE_ATTENTION_SLIDING", "1") == "0":
+        return None, None
+    if type(layer) is DynamicSlidingWindowLayer and layer.sliding_window == sliding and not layer.record_past:
+        return layer, "dynamic_sliding"
+    if type(layer) is StaticSlidingWindowLayer and layer.max_cache_len <= sliding and (layer.is_initialized or uninitialized):
+        return layer, "static_sliding"
+    return None, None
+
+
+def _length_after_update(layer, kind, keys):
+    """The number of valid positions of what `update` returned.  A static layer: its device counter.  A static sliding layer: its device
+    counter while the layer has not overflowed (it stops updating the tensor from then on: the tensor is wrong and must not be used), then
+    the length of what `update` returned -- all of it is valid.  A dynamic layer of either kind: the length of what `update` returned."""
+    if kind == "static" or (kind == "static_sliding" and layer.cumulative_length_int <= layer.max_cache_len):
+        return layer.cumulative_length
+    return keys.shape[2]
 
 
 def _fused_core(self, q, k, v, attention_mask, past_key_values, kwargs, window):
@@ -71,24 +109,25 @@ def _fused_core(self, q, k, v, attention_mask, past_key_values, kwargs, window):
     if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
         return no
     sliding = getattr(self.config, "sliding_window", None) if window == "config" else getattr(self, "sliding_window", None) if window == "self" else None
-    if sliding is not None or any(val is not None and val is not False for name, val in kwargs.items() if name not in _BENIGN):
+    if any(val is not None and val is not False for name, val in kwargs.items() if name not in _BENIGN):
         return no
     if attention_mask is not None and not (isinstance(attention_mask, torch.Tensor) and attention_mask.dim() == 4 and attention_mask.shape[1] == 1
                                            and attention_mask.shape[2] == 1 and (attention_mask.dtype == torch.bool or attention_mask.dtype == q.dtype)):
         return no
-    layer = _layer_of(past_key_values, self.layer_idx)
+    layer, kind = _layer_of(past_key_values, self.layer_idx, sliding=sliding)
     if layer is None:
         return no
-    static = hasattr(layer, "cumulative_length")
-    if static and (layer.keys.dtype != q.dtype or layer.keys.shape[0] != q.shape[0] or layer.keys.shape[3] != q.shape[3]):
+    if kind.startswith("static") and (layer.keys.dtype != q.dtype or layer.keys.shape[0] != q.shape[0] or layer.keys.shape[3] != q.shape[3]):
         return no
     keys, values = past_key_values.update(k, v, self.layer_idx)
-    length = layer.cumulative_length if static else keys.shape[2]
+    length = _length_after_update(layer, kind, keys)
     try:
         plan = ops.attn_decode_plan(q, keys, values, length, mask=attention_mask)
     except ops.QllmUnsupported:
         return None, keys, values, True
     with torch.no_grad():
+        if sliding is not None:
+            return ops.attn_decode(q, keys, values, length, mask=attention_mask, scaling=self.scaling, plan=plan, window=sliding), keys, values, True
         return ops.attn_decode(q, keys, values, length, mask=attention_mask, scaling=self.scaling, plan=plan), keys, values, True
 
 
@@ -100,25 +139,56 @@ def _fused_core(self, q, k, v, attention_mask, past_key_values, kwargs, window):
 # 2048, and a chunk of 128 rows behind 1024 cached tokens loses (0.78 to 0.96: B x Hq blocks walk the keys alone, there is no split over
 # them), so there only first prompts of at most PREFILL_DYNAMIC_MASKED_MAX_ROWS rows are routed.
 PREFILL_DYNAMIC_MASKED_MAX_ROWS = 128
+
+
+class Windows(float):
+    """A q_len bound of PREFILL_ROUTES given in multiples of the call's sliding window."""
+
+
 PREFILL_ROUTES = {
     ("dynamic", False): (2, None, True),
     ("dynamic", True): (2, PREFILL_DYNAMIC_MASKED_MAX_ROWS, False),
     ("static", False): (2, None, True),
     ("static", True): (2, None, True),
+    # The two sliding kinds, by the same rule, from profiles/attn_sliding.md, "Prefill": measured at ONE window, W = 4096
+    # (tools/attn_prefill_bench.py --window 4096; fp16, (32, 8, 128) and (32, 32, 128); first prompts of 128 .. 8192 rows and a 128-row
+    # chunk behind a full window), so every bound that the window decides is written in windows (`Windows`), not in rows.  An entry may
+    # hold several ranges, and an upper end may be the lower of two bounds.  Without a mask (a first prompt shorter than the window on a
+    # dynamic sliding layer) every point wins (1.11 to 1.23 times).  With the band mask and the prompt inside half a window -- where the
+    # window hides nothing and the call is the masked path of the full layers -- the kernel wins up to 128 rows on a dynamic and up to 2048
+    # rows (half the window) on a static sliding layer (1.04 to 9.0 times), and loses at 512 / 2048 rows on the dynamic one.  At one window
+    # (4096 rows) it loses on both (0.83 to 0.92: the whole prompt lies inside the window, nothing is skipped and the mask is read byte by
+    # byte).  At two windows (8192 rows) it wins (1.48 to 1.63): half the causal triangle lies below the window and is never read; nothing
+    # between one and two windows was measured.  The chunk behind a full window loses (0.39 to 0.43: no split over the keys).  A static
+    # sliding layer without a mask was not measured (transformers always hands it one): not routed.
+    ("dynamic_sliding", False): (2, None, False),
+    ("dynamic_sliding", True): ((2, (PREFILL_DYNAMIC_MASKED_MAX_ROWS, Windows(0.5)), False), (Windows(2), None, False)),
+    ("static_sliding", False): (1, 0, False),
+    ("static_sliding", True): ((2, (2048, Windows(0.5)), False), (Windows(2), None, False)),
 }
 
 
-def _prefill_routed(static: bool, masked: bool, q_len: int, behind: bool) -> bool:
-    """`behind`: the host knows that the layer held tokens before this call (a dynamic layer's length; a static layer's is on the device)."""
-    lo, hi, chunks = PREFILL_ROUTES.get(("static" if static else "dynamic", masked), (1, 0, False))
-    return q_len >= lo and (hi is None or q_len <= hi) and (chunks or not behind)
+def _rows(bound, window):
+    """A bound of PREFILL_ROUTES in rows: an int, `Windows(x)` (x times the call's window, rounded down), or the lowest of a tuple of these."""
+    if isinstance(bound, tuple):
+        return min(_rows(b, window) for b in bound)
+    return int(bound * window) if isinstance(bound, Windows) else bound
+
+
+def _prefill_routed(kind: str, masked: bool, q_len: int, behind: bool, window: Optional[int] = None) -> bool:
+    """`behind`: the host knows that the layer held tokens before this call (a dynamic layer's length and a static sliding layer's
+    Python counter; a static layer's length is on the device).  `window`: the call's sliding window, for the bounds written in windows."""
+    entry = PREFILL_ROUTES.get((kind, masked), (1, 0, False))
+    ranges = entry if isinstance(entry[0], tuple) else (entry,)
+    return any(q_len >= _rows(lo, window) and (hi is None or q_len <= _rows(hi, window)) and (chunks or not behind) for lo, hi, chunks in ranges)
 
 
 def _fused_core_prefill(self, q, k, v, attention_mask, past_key_values, kwargs, window):
     """`_fused_core` for q_len == 1; for q_len >= 2 the same tuple with ops.attn_prefill's [B, S, Hq, D] output: the kernel under
     `_fused_core`'s conditions on types, device, autograd, training, implementation, sliding window, kwargs and cache layer (a StaticLayer
-    may also be uninitialised: `update` initialises it), and in addition: the module is causal (`self.is_causal`); the mask is None or 4-D
-    [B, 1, S, L'], bool or of the activation type; with mask None the cache layer holds nothing before this call and that is known on the
+    or StaticSlidingWindowLayer may also be uninitialised: `update` initialises it; on the sliding layers first prompts and continuation
+    chunks alike go to the kernel with `window=W`, over what `update` returned), and in addition: the module is causal
+    (`self.is_causal`); the mask is None or 4-D [B, 1, S, L'], bool or of the activation type; with mask None the cache layer holds nothing before this call and that is known on the
     host (sdpa's own is_causal rule: a DynamicLayer of length 0, a StaticLayer not yet initialised); `PREFILL_ROUTES` routes the
     combination.  The kernel runs with causal = 1 plus the mask: a hand-made mask that shows a causal model keys above the diagonal is
     not honoured there."""
@@ -132,30 +202,33 @@ def _fused_core_prefill(self, q, k, v, attention_mask, past_key_values, kwargs, 
     if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
         return no
     sliding = getattr(self.config, "sliding_window", None) if window == "config" else getattr(self, "sliding_window", None) if window == "self" else None
-    if sliding is not None or any(val is not None and val is not False for name, val in kwargs.items() if name not in _BENIGN):
+    if any(val is not None and val is not False for name, val in kwargs.items() if name not in _BENIGN):
         return no
     s = q.shape[2]
     if attention_mask is not None and not (isinstance(attention_mask, torch.Tensor) and attention_mask.dim() == 4 and attention_mask.shape[1] == 1
                                            and attention_mask.shape[2] == s and (attention_mask.dtype == torch.bool or attention_mask.dtype == q.dtype)):
         return no
-    layer = _layer_of(past_key_values, self.layer_idx, uninitialized=True)
+    layer, kind = _layer_of(past_key_values, self.layer_idx, uninitialized=True, sliding=sliding)
     if layer is None:
         return no
-    static = hasattr(layer, "cumulative_length")
+    static = kind.startswith("static")
     held = layer.is_initialized if static else layer.get_seq_length() != 0   # (a static layer: may hold tokens; its length is on the device)
-    if not _prefill_routed(static, attention_mask is not None, s, held and not static):
+    behind = layer.is_initialized and layer.cumulative_length_int != 0 if kind == "static_sliding" else held and not static
+    if not _prefill_routed(kind, attention_mask is not None, s, behind, sliding):
         return no
     if attention_mask is None and held:
         return no
     if static and layer.is_initialized and (layer.keys.dtype != q.dtype or layer.keys.shape[0] != q.shape[0] or layer.keys.shape[3] != q.shape[3]):
         return no
     keys, values = past_key_values.update(k, v, self.layer_idx)
-    length = layer.cumulative_length if static else keys.shape[2]
+    length = _length_after_update(layer, kind, keys)
     try:
         plan = ops.attn_prefill_plan(q, keys, values, length, mask=attention_mask)
     except ops.QllmUnsupported:
         return None, keys, values, True
     with torch.no_grad():
+        if sliding is not None:
+            return ops.attn_prefill(q, keys, values, length, mask=attention_mask, causal=True, scaling=self.scaling, plan=plan, window=sliding), keys, values, True
         return ops.attn_prefill(q, keys, values, length, mask=attention_mask, causal=True, scaling=self.scaling, plan=plan), keys, values, True
 
 

@@ -605,6 +605,16 @@ def _attn_heads(t: torch.Tensor, name: str):
     return b, h, d, row, head
 
 
+def _attn_window(window, name: str) -> int:
+    """The `window` keyword of attn_decode / attn_prefill as the C entries take it: None -> 0 (no window), an int >= 1 -> itself;
+    anything else is refused."""
+    if window is None:
+        return 0
+    if isinstance(window, bool) or not isinstance(window, int) or window < 1:
+        raise QllmUnsupported(_lib.QLLM_ERR_UNSUPPORTED, f"{name}: window must be None or an int >= 1 (got {window!r})")
+    return window
+
+
 def attn_decode_plan(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, length, k_new: Optional[torch.Tensor] = None,
                      v_new: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None):
     """What `attn_decode` hands to qllm_attn_decode for these tensors -- (batch, q_heads, kv_heads, head_dim, max_len, q row / head stride,
@@ -681,7 +691,8 @@ def attn_decode_describe(batch: int, q_heads: int, kv_heads: int, head_dim: int,
 
 
 def attn_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, length, k_new: Optional[torch.Tensor] = None,
-                v_new: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, scaling: Optional[float] = None, *, out=None, plan=None):
+                v_new: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, scaling: Optional[float] = None, *, out=None, plan=None,
+                window: Optional[int] = None):
     """softmax(scaling * q K^T + mask) V for one query token per sequence over the first `length` positions of the caches [B, Hkv, L, D], as
     ONE kernel (qllm_attn_decode, csrc/attn_decode.hip): a K / V row is read once for all query heads of its kv head, positions >= length
     are never loaded, fp32 scores and softmax, one rounding at the store.  Returns [B, Hq, D] (contiguous: the row o_proj takes).
@@ -689,7 +700,11 @@ def attn_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, l
     the new token's rows; the kernel stores them at position `length` of the caches and attends over length + 1 positions (with the
     length on the device and length + 1 > L it stores nothing and attends over the first L positions).  mask: [B, 1, 1, L'] or [B, L'],
     bool (True = visible) or additive; a row with no visible key gives zeros.  scaling: D ** -0.5 when None.  `attn_decode_plan` says what
-    is served; everything else raises QllmUnsupported before anything is launched.  plan: what it returned for these very arguments."""
+    is served; everything else raises QllmUnsupported before anything is launched.  plan: what it returned for these very arguments.
+    window: None, or an int W >= 1 -- a sliding window on the linear cache: the query (the last counted position, the appended token
+    included) sees the last W counted positions only, in addition to length and mask; earlier positions are never loaded, and with the
+    length on the device the lower end follows it.  The plan does not depend on the window; None gives the bits of a call without it."""
+    window = _attn_window(window, "attn_decode")
     if plan is None:
         plan = attn_decode_plan(q, k_cache, v_cache, length, k_new, v_new, mask)
     b, hq, hkv, d, max_len = plan[:5]
@@ -705,9 +720,10 @@ def attn_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, l
     with torch.cuda.device(q.device):
         nbytes = lib.qllm_attn_decode_workspace_bytes(b, hq, hkv, d, max_len)
         ws = workspace(q.device, nbytes)
-        rc = lib.qllm_attn_decode(q.data_ptr(), _ptr(k_new), _ptr(v_new), k_cache.data_ptr(), v_cache.data_ptr(), _ptr(mask), out.data_ptr(),
-                                  b, hq, hkv, d, 0 if on_device else int(length), length.data_ptr() if on_device else None, max_len,
-                                  *plan[5:], float(d ** -0.5 if scaling is None else scaling), _act_dtype(q), ws.data_ptr(), ws.numel(), _stream_ptr())
+        rc = lib.qllm_attn_decode_window(q.data_ptr(), _ptr(k_new), _ptr(v_new), k_cache.data_ptr(), v_cache.data_ptr(), _ptr(mask), out.data_ptr(),
+                                         b, hq, hkv, d, 0 if on_device else int(length), length.data_ptr() if on_device else None, max_len, window,
+                                         *plan[5:], float(d ** -0.5 if scaling is None else scaling), _act_dtype(q), ws.data_ptr(), ws.numel(),
+                                         _stream_ptr())
     _lib.check(rc)
     return out
 
@@ -787,7 +803,7 @@ def attn_prefill_describe(batch: int, q_heads: int, kv_heads: int, head_dim: int
 
 
 def attn_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, length, mask: Optional[torch.Tensor] = None, causal: bool = True,
-                 scaling: Optional[float] = None, *, out=None, plan=None):
+                 scaling: Optional[float] = None, *, out=None, plan=None, window: Optional[int] = None):
     """softmax(scaling * q K^T + mask) V for S >= 2 query rows per sequence over the first `length` positions of the caches [B, Hkv, L, D],
     which already hold the S new rows, as ONE kernel (qllm_attn_prefill, csrc/attn_prefill.hip): flash attention forward on MFMA, fp32
     scores and softmax, one rounding at the store.  q: [B, Hq, S, D], any strides; returns [B, S, Hq, D] (contiguous: the rows o_proj
@@ -795,7 +811,13 @@ def attn_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, 
     or a 0-d int64 tensor on the device that the kernel reads and clamps to S..L (a captured call then serves every length).  mask:
     [B, 1, S, L'] or [B, S, L'], bool (True = visible) or additive, applied in addition to causality; a row with no visible key gives
     zeros.  scaling: D ** -0.5 when None.  `attn_prefill_plan` says what is served; everything else raises QllmUnsupported before anything
-    is launched.  plan: what it returned for these very arguments."""
+    is launched.  plan: what it returned for these very arguments.  window: None, or an int W >= 1 -- a sliding window on the linear
+    cache: row i at position p = length - S + i sees key j only if p - W < j <= p, in addition to length, causality and mask; key tiles
+    wholly below the window of a block's first row are never read.  Needs causal=True (QllmUnsupported otherwise).  The plan does not
+    depend on the window; None gives the bits of a call without it."""
+    window = _attn_window(window, "attn_prefill")
+    if window and not causal:
+        raise QllmUnsupported(_lib.QLLM_ERR_UNSUPPORTED, "attn_prefill: a sliding window is served on causal calls only")
     if plan is None:
         plan = attn_prefill_plan(q, k_cache, v_cache, length, mask)
     b, hq, hkv, d, s, max_len = plan[:6]
@@ -808,9 +830,10 @@ def attn_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, 
         raise RuntimeError(f"attn_prefill: out must be a contiguous {(b, s, hq, d)} {q.dtype} tensor on {q.device}")
     on_device = isinstance(length, torch.Tensor)
     with torch.cuda.device(q.device):
-        rc = _lib.load().qllm_attn_prefill(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), _ptr(mask), out.data_ptr(), b, hq, hkv, d, s,
-                                           0 if on_device else int(length), length.data_ptr() if on_device else None, max_len, *plan[6:16],
-                                           1 if causal else 0, float(d ** -0.5 if scaling is None else scaling), _act_dtype(q), _stream_ptr())
+        rc = _lib.load().qllm_attn_prefill_window(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), _ptr(mask), out.data_ptr(), b, hq, hkv, d, s,
+                                                  0 if on_device else int(length), length.data_ptr() if on_device else None, max_len, window,
+                                                  *plan[6:16], 1 if causal else 0, float(d ** -0.5 if scaling is None else scaling), _act_dtype(q),
+                                                  _stream_ptr())
     _lib.check(rc)
     return out
 

@@ -18,7 +18,17 @@ transformers runs there, fp16, in ONE process on one box, the two versions alter
 The two versions' outputs are compared in every row (maximum absolute difference, printed; both finite).  Prints a table and one JSON line
 per row.
 
-  python tools/attn_decode_bench.py [--links 16] [--seconds 0.4] [--repeats 3]"""
+  --window W   instead of the points above, the sliding layers of a Mistral-shaped config with that window, (32, 8, 128) and (32, 32, 128):
+          the step below the window (W / 4 tokens cached), at it (W - 1 cached: the step fills it) and past it (W + 1000 cached), us per
+          step under graph replay --
+            dynamic  DynamicSlidingWindowLayer.update's own statements (torch.cat of the W - 1 positions it keeps, or fewer, and the new
+                     row), then sdpa with mask None over what it returns  |  the same statements, then ops.attn_decode(window=W)
+            static   StaticSlidingWindowLayer.update (index_copy_ until the layer is full; past the window its statements restated: roll,
+                     index put and copy_ of the whole buffer at every token), then sdpa over all W positions behind the bool mask  |  the same update, then
+                     ops.attn_decode(window=W) with the length the modules hand over; past the window also the update ALONE, which
+                     both versions pay.
+
+  python tools/attn_decode_bench.py [--links 16] [--seconds 0.4] [--repeats 3] [--window W]"""
 import argparse
 import json
 import os
@@ -33,7 +43,7 @@ from qllm_amd import ops  # noqa: E402
 from qllm_amd.modeling.q_layers import (WQLinear_GEMM, install_fused_attention, install_fused_mlp, install_fused_norm, install_fused_residual,  # noqa: E402
                                         install_fused_rope, install_sibling_groups, uninstall_fused_attention)
 from rope_bench import decoder_layers  # noqa: E402
-from swiglu_bench import ab, row  # noqa: E402
+from swiglu_bench import ab, row, timed  # noqa: E402
 
 DEV = "cuda:0"
 L_MAX = 4096
@@ -84,17 +94,120 @@ def max_diff(tag, ya, yb):
     return diff
 
 
+def sliding_points(args, gen):
+    """The --window points: see the module text."""
+    from transformers.cache_utils import StaticSlidingWindowLayer
+    from transformers.integrations.sdpa_attention import sdpa_attention_forward
+    from qllm_amd.modeling.q_layers.fused_attention import _length_after_update
+    n, w = args.links, args.window
+    for hq, hk, d in ((32, 8, 128), (32, 32, 128)):
+        print(ops.attn_decode_describe(1, hq, hk, d, w), flush=True)
+        module = types.SimpleNamespace(num_key_value_groups=hq // hk, is_causal=True)
+        r = lambda *shape: torch.randn(shape, device=DEV, dtype=torch.float16, generator=gen)
+        qs = [r(1, 1, hq, d).transpose(1, 2) for _ in range(n)]
+        kns, vns = [r(1, 1, hk, d).transpose(1, 2) for _ in range(n)], [r(1, 1, hk, d).transpose(1, 2) for _ in range(n)]
+        for where, cached in (("below", w // 4), ("at", w - 1), ("past", w + 1000)):
+            tag = f"({hq},{hk},{d}) W={w} {where}"
+            # dynamic: the layer keeps the last W - 1 positions (all of them below the window)
+            kept = min(cached, w - 1)
+            pks, pvs = [r(1, hk, kept, d) for _ in range(n)], [r(1, hk, kept, d) for _ in range(n)]
+
+            def dyn_eager():
+                outs = []
+                for q, kn, vn, pk, pv in zip(qs, kns, vns, pks, pvs):
+                    k, v = torch.cat([pk, kn], dim=-2), torch.cat([pv, vn], dim=-2)
+                    outs.append(sdpa_attention_forward(module, q, k, v, None, dropout=0.0, scaling=d ** -0.5, is_causal=False)[0])
+                return outs
+
+            def dyn_kernel():
+                outs = []
+                for q, kn, vn, pk, pv in zip(qs, kns, vns, pks, pvs):
+                    k, v = torch.cat([pk, kn], dim=-2), torch.cat([pv, vn], dim=-2)
+                    outs.append(ops.attn_decode(q, k, v, k.shape[2], scaling=d ** -0.5, window=w))
+                return outs
+
+            g_a, y_a = capture(dyn_eager)
+            g_b, y_b = capture(dyn_kernel)
+            max_diff(tag + " dynamic", y_a, y_b)
+            a, b = ab(g_a, g_b, n, args.seconds, args.repeats)
+            row(tag, "dyn", "eager", "kernel", a, b)
+            del g_a, g_b, y_a, y_b, pks, pvs
+            # static: layers of W positions; the layer itself branches on its Python counter, so every call sets it first
+            lens_a, lens_b = torch.zeros(n, dtype=torch.int64, device=DEV), torch.zeros(n, dtype=torch.int64, device=DEV)
+            la, lb = [], []
+            for lens, layers in ((lens_a, la), (lens_b, lb)):
+                for i in range(n):
+                    layer = StaticSlidingWindowLayer(max_cache_len=w, sliding_window=w)
+                    layer.lazy_initialization(torch.empty(1, hk, 1, d, device=DEV, dtype=torch.float16), torch.empty(1, hk, 1, d, device=DEV, dtype=torch.float16))
+                    layer.cumulative_length = lens[i]
+                    layers.append(layer)
+            for x, y in zip(la, lb):
+                x.keys.copy_(r(*x.keys.shape)), x.values.copy_(r(*x.values.shape))
+                y.keys.copy_(x.keys), y.values.copy_(x.values)
+            mask = (torch.arange(w, device=DEV) <= cached).view(1, 1, 1, w)                    # past the window: every position
+
+            last = torch.tensor([-1], dtype=torch.int64, device=DEV)
+
+            def update(layers, lens, kn_vn):
+                lens.fill_(min(cached, w))
+                out = []
+                for layer, (kn, vn) in zip(layers, kn_vn):
+                    layer.cumulative_length_int = cached
+                    if cached < w:
+                        out.append(layer.update(kn, vn))
+                        continue
+                    # the layer's own statements once it is full, with the index tensor it builds from a Python list at every call
+                    # (a host-to-device copy, which a capture does not take) made once above
+                    new_keys, new_values = layer.keys.roll(-1, dims=-2), layer.values.roll(-1, dims=-2)
+                    new_keys[:, :, last], new_values[:, :, last] = kn, vn
+                    layer.keys.copy_(new_keys), layer.values.copy_(new_values)
+                    layer.cumulative_length_int = cached + 1
+                    out.append((layer.keys, layer.values))
+                return out
+
+            def st_eager():
+                return [sdpa_attention_forward(module, q, k, v, mask, dropout=0.0, scaling=d ** -0.5)[0] for q, (k, v) in zip(qs, update(la, lens_a, zip(kns, vns)))]
+
+            def st_kernel():
+                outs = []
+                for q, layer, (k, v) in zip(qs, lb, update(lb, lens_b, zip(kns, vns))):
+                    outs.append(ops.attn_decode(q, k, v, _length_after_update(layer, "static_sliding", k), mask=mask, scaling=d ** -0.5, window=w))
+                return outs
+
+            g_a, y_a = capture(st_eager)
+            g_b, y_b = capture(st_kernel)
+            max_diff(tag + " static", y_a, y_b)
+            a, b = ab(g_a, g_b, n, args.seconds, args.repeats)
+            row(tag, "stat", "eager", "kernel", a, b)
+            if where == "past":
+                g_u, _ = capture(lambda: update(lb, lens_b, zip(kns, vns)))
+                u = [timed(g_u, n, args.seconds) for _ in range(args.repeats)]
+                mu, mb = sum(u) / len(u), sum(b) / len(b)
+                rec = dict(config=tag, what="roll", update_alone_us=[round(x, 3) for x in u], update_mean_us=round(mu, 3), kernel_mean_us=round(mb, 3),
+                           eager_mean_us=round(sum(a) / len(a), 3), share_of_kernel_step=round(mu / mb, 4))
+                print(f"{tag:14s} the layer's update alone (roll, index put, copy_): {mu:.2f} us = {100 * mu / mb:.1f} % of the kernel step", flush=True)
+                print("JSON " + json.dumps(rec), flush=True)
+                del g_u
+            del g_a, g_b, y_a, y_b, la, lb
+            torch.cuda.empty_cache()
+
+
 def main():
     from transformers.integrations.sdpa_attention import sdpa_attention_forward
     ap = argparse.ArgumentParser()
     ap.add_argument("--links", type=int, default=16)
     ap.add_argument("--seconds", type=float, default=0.4)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--window", type=int, default=0, help="the sliding-layer points for this window instead of the full-attention ones")
     args = ap.parse_args()
     n = args.links
     print(f"device: {torch.cuda.get_device_name(0)}  CUs: {torch.cuda.get_device_properties(0).multi_processor_count}  "
           f"torch {torch.__version__}  steps per graph: {n}  L_max: {L_MAX}", flush=True)
     gen = torch.Generator(device=DEV).manual_seed(7)
+    if args.window > 0:
+        with torch.no_grad():
+            sliding_points(args, gen)
+        return
     with torch.no_grad():
         for hq, hk, d in ((32, 32, 128), (32, 8, 128), (28, 4, 128)):
             print(ops.attn_decode_describe(1, hq, hk, d, L_MAX), flush=True)

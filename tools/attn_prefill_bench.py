@@ -18,10 +18,17 @@ runs there, fp16, in ONE process on one box, the two versions alternating A, B, 
   layer   one Llama-2-7B-shaped decoder layer (AWQ 4-bit linears, 128-wide groups, sdpa) at S = 2048 with fuse_mlp, fuse_norm, fuse_residual
           and fuse_rope installed, a StaticCache of 4096 positions and the padded mask of (c), without and with the prefill core.
 
+  --window W   instead of the points above, the sliding layers of a Mistral-shaped config with that window, (32, 8, 128) and (32, 32, 128):
+          first prompts of 128, 512, W / 2, W and 2 W rows and a 128-row chunk behind a full window, on a DynamicSlidingWindowLayer (its update's own
+          statements: torch.cat of what it kept and the new rows) and on a StaticSlidingWindowLayer of W positions (its update), behind the
+          mask transformers builds there: none for the prompts below W on the dynamic layer (and those prompts left-padded by 3 as second
+          points), the causal band [1, 1, S, L] otherwise  |  the same update, then ops.attn_prefill(window=W) with the same mask and the
+          length the modules hand over.  The table at the end is what the two sliding kinds of PREFILL_ROUTES are set from.
+
 A point "wins" when the kernel's mean is below eager's by more than the spread (the larger of the two versions' max - min).  The table at the
 end is what q_layers/fused_attention.py's PREFILL_ROUTES is set from.  Prints one JSON line per row.
 
-  python tools/attn_prefill_bench.py [--links 8] [--seconds 0.15] [--repeats 3] [--no-layer]"""
+  python tools/attn_prefill_bench.py [--links 8] [--seconds 0.15] [--repeats 3] [--no-layer] [--window W]"""
 import argparse
 import json
 import os
@@ -149,6 +156,89 @@ def op_points(args, gen):
             torch.cuda.empty_cache()
 
 
+def band_mask(s, behind, width, window, pad=0):
+    """The bool mask of `s` rows behind `behind` positions under a sliding window, [1, 1, s, width]: j <= behind + i, j > behind + i - window,
+    j >= pad."""
+    j, i = torch.arange(width, device=DEV)[None, :], torch.arange(s, device=DEV)[:, None]
+    return ((j <= behind + i) & (j > behind + i - window) & (j >= pad)).view(1, 1, s, width)
+
+
+def sliding_points(args, gen):
+    """The --window points: see the module text."""
+    from transformers.cache_utils import StaticSlidingWindowLayer
+    from transformers.integrations.sdpa_attention import sdpa_attention_forward
+    from qllm_amd.modeling.q_layers.fused_attention import _length_after_update
+    w = args.window
+    r = lambda *shape: torch.randn(shape, device=DEV, dtype=torch.float16, generator=gen)
+    for shape in ((32, 8, 128), (32, 32, 128)):
+        hq, hk, d = shape
+        module = types.SimpleNamespace(num_key_value_groups=hq // hk, is_causal=True)
+        for s, cached in ((128, 0), (512, 0), (w // 2, 0), (w, 0), (2 * w, 0), (CHUNK, w + 1000)):
+            n = max(2, min(args.links, 4096 // s))
+            qs = [r(1, s, hq, d).transpose(1, 2) for _ in range(n)]
+            ks, vs = [r(1, s, hk, d).transpose(1, 2) for _ in range(n)], [r(1, s, hk, d).transpose(1, 2) for _ in range(n)]
+            tag = f"({hq},{hk},{d}) W={w} S={s}" + (f"+{cached}" if cached else "")
+            # dynamic: the layer returns what it kept (W - 1 positions once past the window) and the new rows
+            kept = min(cached, w - 1)
+            past_k, past_v = r(1, hk, kept, d), r(1, hk, kept, d)
+            total = kept + s
+            masks = [("no mask", None), ("masked", band_mask(s, 0, total, w, PAD))] if s < w and not cached else [("masked", band_mask(s, kept, total, w))]
+            for what, mask in masks:
+                def dyn(kernel):
+                    outs = []
+                    for q, k, v in zip(qs, ks, vs):
+                        kk, vv = torch.cat([past_k, k], dim=-2), torch.cat([past_v, v], dim=-2)
+                        if kernel:
+                            outs.append(ops.attn_prefill(q, kk, vv, total, mask=mask, scaling=d ** -0.5, window=w))
+                        else:
+                            outs.append(sdpa_attention_forward(module, q, kk, vv, mask, dropout=0.0, scaling=d ** -0.5)[0])
+                    return outs
+
+                g_a, y_a = capture(lambda: dyn(False))
+                g_b, y_b = capture(lambda: dyn(True))
+                real = slice(PAD, None) if what == "masked" and s < w and not cached else slice(None)
+                diff = max_diff([y[:, real] for y in y_a], [y[:, real] for y in y_b])
+                a, b = ab(g_a, g_b, n, args.seconds, args.repeats)
+                report(tag, f"dynamic_sliding {what}", shape, s, s * (s + 1) // 2 + s * kept if mask is None else int(mask.sum()), a, b, diff)
+                del g_a, g_b, y_a, y_b
+            # static: a layer of W positions; it branches on its Python counter, which every call sets first
+            lens_a, lens_b = torch.zeros(n, dtype=torch.int64, device=DEV), torch.zeros(n, dtype=torch.int64, device=DEV)
+            la, lb = [], []
+            for lens, layers in ((lens_a, la), (lens_b, lb)):
+                for i in range(n):
+                    layer = StaticSlidingWindowLayer(max_cache_len=w, sliding_window=w)
+                    layer.lazy_initialization(torch.empty(1, hk, 1, d, device=DEV, dtype=torch.float16), torch.empty(1, hk, 1, d, device=DEV, dtype=torch.float16))
+                    layer.cumulative_length = lens[i]
+                    layers.append(layer)
+            for x, y in zip(la, lb):
+                x.keys.copy_(r(*x.keys.shape)), x.values.copy_(r(*x.values.shape))
+                y.keys.copy_(x.keys), y.values.copy_(x.values)
+            # what the layer returns: its W positions while the rows fit, the new rows alone when an empty layer overflows, W - 1 kept positions
+            # and the new rows once it is full
+            width, behind = (w, 0) if cached + s <= w else (s, 0) if not cached else (w - 1 + s, w - 1)
+            mask = band_mask(s, behind, width, w)
+
+            def stat(kernel, layers, lens):
+                lens.fill_(min(cached, w))
+                outs = []
+                for layer, q, k, v in zip(layers, qs, ks, vs):
+                    layer.cumulative_length_int = cached
+                    kk, vv = layer.update(k, v)
+                    if kernel:
+                        outs.append(ops.attn_prefill(q, kk, vv, _length_after_update(layer, "static_sliding", kk), mask=mask, scaling=d ** -0.5, window=w))
+                    else:
+                        outs.append(sdpa_attention_forward(module, q, kk, vv, mask, dropout=0.0, scaling=d ** -0.5)[0])
+                return outs
+
+            g_a, y_a = capture(lambda: stat(False, la, lens_a))
+            g_b, y_b = capture(lambda: stat(True, lb, lens_b))
+            diff = max_diff(y_a, y_b)
+            a, b = ab(g_a, g_b, n, args.seconds, args.repeats)
+            report(tag, "static_sliding masked", shape, s, int(mask.sum()), a, b, diff)
+            del g_a, g_b, y_a, y_b, la, lb, qs, ks, vs
+            torch.cuda.empty_cache()
+
+
 def layer_point(args, gen):
     import bench
     from transformers import StaticCache
@@ -191,19 +281,23 @@ def main():
     ap.add_argument("--seconds", type=float, default=0.15)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--no-layer", action="store_true")
+    ap.add_argument("--window", type=int, default=0, help="the sliding-layer points for this window instead of the full-attention ones")
     args = ap.parse_args()
     print(f"device: {torch.cuda.get_device_name(0)}  CUs: {torch.cuda.get_device_properties(0).multi_processor_count}  torch {torch.__version__}  "
           f"L_max: {L_MAX}", flush=True)
     gen = torch.Generator(device=DEV).manual_seed(7)
     with torch.no_grad():
-        op_points(args, gen)
+        if args.window > 0:
+            sliding_points(args, gen)
+        else:
+            op_points(args, gen)
         print("\nModule routing: (cache layer kind, mask) x rows -> eager / kernel at each shape; WIN: faster beyond the spread")
         for what in sorted({r["what"] for r in results}):
             for tag_rows in sorted({(r["rows"], "+" in r["config"]) for r in results if r["what"] == what}):
                 rs = [r for r in results if r["what"] == what and (r["rows"], "+" in r["config"]) == tag_rows]
                 cells = "  ".join(f"{tuple(r['shape'])}: {'WIN' if r['wins'] else 'no '} x{r['eager_mean_us'] / r['kernel_mean_us']:.2f}" for r in rs)
-                print(f"  {what:16s} S={tag_rows[0]:5d}{' behind ' + str(BEHIND) if tag_rows[1] else '':12s} {cells}", flush=True)
-        if not args.no_layer:
+                print(f"  {what:16s} S={tag_rows[0]:5d}{' behind ' + (str(BEHIND) if not args.window else 'a full window') if tag_rows[1] else '':12s} {cells}", flush=True)
+        if not args.no_layer and not args.window:
             layer_point(args, gen)
 
 
