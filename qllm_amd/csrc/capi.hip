@@ -9,6 +9,8 @@
 // The six launches of the batch-1 kernel (launch_strip1 / _allreduce / _swiglu / _norm / _resid / _swiglu_resid) fill one Strip1Params
 // here and share ONE form table and launch site, strip1_forms.hpp: a further fused family is the struct that header describes plus its
 // entry here -- no pair table and no launch of its own.
+// The attention entries (qllm_attn_decode / _prefill and their _window forms) share check_attn_shape / _served / _call / _layout:
+// a rule both kernels have is one text there, and an entry's body holds the calls and the few rules that are its own.
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -1017,26 +1019,71 @@ int qllm_rope(const void *q, const void *k, const void *cos, const void *sin, vo
                      act_dtype == QLLM_BF16, (hipStream_t)stream);
 }
 
-// ---- single-token attention over the KV cache (attn_decode.hip) ------------------------------------------------------------------------
-// the shape checks the three entries share: sizes, the head ratio, then what the kernel is built for
-static int check_attn_decode_shape(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int64_t max_len) {
+// ---- attention over the KV cache: the host rules of the decode and the prefill entries, each written once -----------------------------------
+// What differs between the two kernels is an argument: the name in the "%s serves ..." texts, the pointers and strides an entry has and
+// the words its texts call them by.  The entries call these in one order -- the call,
+// the layout, the length and the mask's reach (their own: one row of one stride against rows of two), what the kernel serves -- with the
+// rules only one of them has in between.
+
+// sizes, the number of query rows (q_len NULL: one, the decode entries), the head ratio
+static int check_attn_shape(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, const int32_t *q_len, int64_t max_len) {
   if (batch <= 0 || q_heads <= 0 || kv_heads <= 0 || head_dim <= 0 || max_len <= 0)
     return set_error(QLLM_ERR_INVALID, "batch, q_heads, kv_heads, head_dim and max_len must be >= 1 (got %d, %d, %d, %d, %lld)", batch, q_heads, kv_heads,
                      head_dim, (long long)max_len);
+  if (q_len && (*q_len < 2 || *q_len > max_len))
+    return set_error(QLLM_ERR_INVALID, "q_len must lie in 2..max_len (got q_len=%d max_len=%lld); one token is qllm_attn_decode's", *q_len, (long long)max_len);
   if (q_heads % kv_heads != 0) return set_error(QLLM_ERR_INVALID, "kv_heads must divide q_heads (got q_heads=%d kv_heads=%d)", q_heads, kv_heads);
   return QLLM_OK;
 }
-static int check_attn_decode_served(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim) {
-  if (head_dim != 64 && head_dim != 128) return set_error(QLLM_ERR_UNSUPPORTED, "attn_decode serves head_dim 64 and 128 (got %d)", head_dim);
+
+// what both kernels are built for; the bound on the grid is each entry's own
+static int check_attn_served(const char *name, int32_t q_heads, int32_t kv_heads, int32_t head_dim) {
+  if (head_dim != 64 && head_dim != 128) return set_error(QLLM_ERR_UNSUPPORTED, "%s serves head_dim 64 and 128 (got %d)", name, head_dim);
   if (q_heads / kv_heads > kAttnDecodeMaxGroup)
-    return set_error(QLLM_ERR_UNSUPPORTED, "attn_decode serves 1..%d query heads per kv head (got %d)", kAttnDecodeMaxGroup, q_heads / kv_heads);
+    return set_error(QLLM_ERR_UNSUPPORTED, "%s serves 1..%d query heads per kv head (got %d)", name, kAttnDecodeMaxGroup, q_heads / kv_heads);
+  return QLLM_OK;
+}
+
+// the head of a call: the four pointers every call has, the shape, the window, the activation type, the mask and its kind
+static int check_attn_call(const void *q, const void *k_cache, const void *v_cache, const void *out, int32_t batch, int32_t q_heads, int32_t kv_heads,
+                           int32_t head_dim, const int32_t *q_len, int64_t max_len, int64_t window, int32_t act_dtype, int32_t mask_kind, const void *mask) {
+  if (!q || !k_cache || !v_cache || !out) return set_error(QLLM_ERR_INVALID, "q / k_cache / v_cache / out must not be NULL");
+  int rc = check_attn_shape(batch, q_heads, kv_heads, head_dim, q_len, max_len);
+  if (rc != QLLM_OK) return rc;
+  if (window < 0) return set_error(QLLM_ERR_INVALID, "window must be 0 (none) or >= 1 (got %lld)", (long long)window);
+  if (act_dtype != QLLM_F16 && act_dtype != QLLM_BF16) return set_error(QLLM_ERR_INVALID, "act_dtype must be QLLM_F16 or QLLM_BF16");
+  if (mask_kind != QLLM_ATTN_MASK_NONE && mask_kind != QLLM_ATTN_MASK_BOOL && mask_kind != QLLM_ATTN_MASK_ADDITIVE)
+    return set_error(QLLM_ERR_INVALID, "mask_kind must be QLLM_ATTN_MASK_NONE, _BOOL or _ADDITIVE (got %d)", mask_kind);
+  if ((mask_kind == QLLM_ATTN_MASK_NONE) != (mask == nullptr)) return set_error(QLLM_ERR_INVALID, "mask must be NULL exactly with QLLM_ATTN_MASK_NONE");
+  return QLLM_OK;
+}
+
+// alignment of the `n_ptrs` tensors `ptr_names` lists (a NULL one is aligned), of the device length and of an additive mask; then the
+// first `n_strides` strides, which `stride_words` names
+static int check_attn_layout(const char *ptr_names, const void *const *ptrs, int n_ptrs, const int64_t *kv_len_dev, int32_t mask_kind, const void *mask,
+                             const char *stride_words, const int64_t *strides, int n_strides) {
+  for (int i = 0; i < n_ptrs; ++i)
+    if ((uintptr_t)ptrs[i] % 16) return set_error(QLLM_ERR_INVALID, "%s must be 16-byte aligned", ptr_names);
+  if ((uintptr_t)kv_len_dev % 8 || (mask_kind == QLLM_ATTN_MASK_ADDITIVE && (uintptr_t)mask % 2))
+    return set_error(QLLM_ERR_INVALID, "kv_len_dev must be 8-byte aligned and an additive mask 2-byte aligned");
+  for (int i = 0; i < n_strides; ++i)
+    if (strides[i] < 0 || strides[i] % 8 != 0)
+      return set_error(QLLM_ERR_INVALID, "%s strides must be non-negative multiples of 8 elements (got %lld)", stride_words, (long long)strides[i]);
+  return QLLM_OK;
+}
+
+// ---- single-token attention over the KV cache (attn_decode.hip) ------------------------------------------------------------------------
+// what the kernel serves, and one arrival counter per (sequence, kv head) in the counter page
+static int check_attn_decode_served(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim) {
+  int rc = check_attn_served("attn_decode", q_heads, kv_heads, head_dim);
+  if (rc != QLLM_OK) return rc;
   if (batch > 65535 || kv_heads > 65535 || (int64_t)batch * kv_heads > (int64_t)(kCounterBytes / sizeof(int)))
     return set_error(QLLM_ERR_UNSUPPORTED, "attn_decode serves batch * kv_heads <= %d (got %lld)", (int)(kCounterBytes / sizeof(int)), (long long)batch * kv_heads);
   return QLLM_OK;
 }
 
 size_t qllm_attn_decode_workspace_bytes(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int64_t max_len) {
-  const bool refused = check_attn_decode_shape(batch, q_heads, kv_heads, head_dim, max_len) != QLLM_OK ||
+  const bool refused = check_attn_shape(batch, q_heads, kv_heads, head_dim, nullptr, max_len) != QLLM_OK ||
                        check_attn_decode_served(batch, q_heads, kv_heads, head_dim) != QLLM_OK;
   clear_error();
   return refused ? kCounterBytes : kCounterBytes + attn_decode_geom(batch, q_heads, kv_heads, head_dim, max_len).partial_bytes;
@@ -1045,7 +1092,7 @@ size_t qllm_attn_decode_workspace_bytes(int32_t batch, int32_t q_heads, int32_t 
 int qllm_attn_decode_describe(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int64_t max_len, char *buf, size_t buflen) {
   clear_error();
   if (!buf || buflen == 0) return set_error(QLLM_ERR_INVALID, "buf must not be NULL or empty");
-  int rc = check_attn_decode_shape(batch, q_heads, kv_heads, head_dim, max_len);
+  int rc = check_attn_shape(batch, q_heads, kv_heads, head_dim, nullptr, max_len);
   if (rc == QLLM_OK) rc = check_attn_decode_served(batch, q_heads, kv_heads, head_dim);
   if (rc != QLLM_OK) return describe_refusal(rc, kRefused, buf, buflen);
   const AttnDecodeGeom g = attn_decode_geom(batch, q_heads, kv_heads, head_dim, max_len);
@@ -1071,24 +1118,15 @@ int qllm_attn_decode_window(const void *q, const void *k_new, const void *v_new,
                             int64_t mask_len, int64_t mask_batch_stride, float scaling, int32_t act_dtype, void *workspace, size_t workspace_bytes,
                             void *stream) {
   clear_error();
-  if (!q || !k_cache || !v_cache || !out) return set_error(QLLM_ERR_INVALID, "q / k_cache / v_cache / out must not be NULL");
-  int rc = check_attn_decode_shape(batch, q_heads, kv_heads, head_dim, max_len);
+  int rc = check_attn_call(q, k_cache, v_cache, out, batch, q_heads, kv_heads, head_dim, nullptr, max_len, window, act_dtype, mask_kind, mask);
   if (rc != QLLM_OK) return rc;
-  if (window < 0) return set_error(QLLM_ERR_INVALID, "window must be 0 (none) or >= 1 (got %lld)", (long long)window);
-  if (act_dtype != QLLM_F16 && act_dtype != QLLM_BF16) return set_error(QLLM_ERR_INVALID, "act_dtype must be QLLM_F16 or QLLM_BF16");
-  if (mask_kind != QLLM_ATTN_MASK_NONE && mask_kind != QLLM_ATTN_MASK_BOOL && mask_kind != QLLM_ATTN_MASK_ADDITIVE)
-    return set_error(QLLM_ERR_INVALID, "mask_kind must be QLLM_ATTN_MASK_NONE, _BOOL or _ADDITIVE (got %d)", mask_kind);
-  if ((mask_kind == QLLM_ATTN_MASK_NONE) != (mask == nullptr)) return set_error(QLLM_ERR_INVALID, "mask must be NULL exactly with QLLM_ATTN_MASK_NONE");
   if ((k_new == nullptr) != (v_new == nullptr)) return set_error(QLLM_ERR_INVALID, "k_new and v_new must be given together or not at all");
-  if ((uintptr_t)q % 16 || (uintptr_t)k_new % 16 || (uintptr_t)v_new % 16 || (uintptr_t)k_cache % 16 || (uintptr_t)v_cache % 16 || (uintptr_t)out % 16)
-    return set_error(QLLM_ERR_INVALID, "q / k_new / v_new / k_cache / v_cache / out must be 16-byte aligned");
-  if ((uintptr_t)kv_len_dev % 8 || (mask_kind == QLLM_ATTN_MASK_ADDITIVE && (uintptr_t)mask % 2))
-    return set_error(QLLM_ERR_INVALID, "kv_len_dev must be 8-byte aligned and an additive mask 2-byte aligned");
   const int64_t strides[9] = {q_row_stride, q_head_stride, cache_batch_stride, cache_head_stride, cache_pos_stride,
-                              k_new_row_stride, k_new_head_stride, v_new_row_stride, v_new_head_stride};
-  for (int i = 0; i < (k_new ? 9 : 5); ++i)
-    if (strides[i] < 0 || strides[i] % 8 != 0)
-      return set_error(QLLM_ERR_INVALID, "row, head, batch and position strides must be non-negative multiples of 8 elements (got %lld)", (long long)strides[i]);
+                              k_new_row_stride, k_new_head_stride, v_new_row_stride, v_new_head_stride};  // the last four count with an append only
+  const void *const ptrs[6] = {q, k_new, v_new, k_cache, v_cache, out};
+  rc = check_attn_layout("q / k_new / v_new / k_cache / v_cache / out", ptrs, 6, kv_len_dev, mask_kind, mask, "row, head, batch and position", strides,
+                         k_new ? 9 : 5);
+  if (rc != QLLM_OK) return rc;
   const int64_t need_len = kv_len_dev ? max_len : kv_len + (k_new ? 1 : 0);  // the positions a call may reach
   if (!kv_len_dev && (kv_len < 0 || need_len > max_len))
     return set_error(QLLM_ERR_INVALID, "kv_len%s must lie in 0..max_len (got kv_len=%lld max_len=%lld)", k_new ? " + 1 (append)" : "", (long long)kv_len, (long long)max_len);
@@ -1112,20 +1150,10 @@ int qllm_attn_decode_window(const void *q, const void *k_new, const void *v_new,
 }
 
 // ---- prefill attention over the KV cache (attn_prefill.hip) ------------------------------------------------------------------------------
-// the shape checks the two entries share: sizes, the head ratio, then what the kernel is built for
-static int check_attn_prefill_shape(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t q_len, int64_t max_len) {
-  if (batch <= 0 || q_heads <= 0 || kv_heads <= 0 || head_dim <= 0 || max_len <= 0)
-    return set_error(QLLM_ERR_INVALID, "batch, q_heads, kv_heads, head_dim and max_len must be >= 1 (got %d, %d, %d, %d, %lld)", batch, q_heads, kv_heads,
-                     head_dim, (long long)max_len);
-  if (q_len < 2 || q_len > max_len)
-    return set_error(QLLM_ERR_INVALID, "q_len must lie in 2..max_len (got q_len=%d max_len=%lld); one token is qllm_attn_decode's", q_len, (long long)max_len);
-  if (q_heads % kv_heads != 0) return set_error(QLLM_ERR_INVALID, "kv_heads must divide q_heads (got q_heads=%d kv_heads=%d)", q_heads, kv_heads);
-  return QLLM_OK;
-}
+// what the kernel serves, and a grid of (row tiles, q_heads, batch)
 static int check_attn_prefill_served(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim) {
-  if (head_dim != 64 && head_dim != 128) return set_error(QLLM_ERR_UNSUPPORTED, "attn_prefill serves head_dim 64 and 128 (got %d)", head_dim);
-  if (q_heads / kv_heads > kAttnDecodeMaxGroup)
-    return set_error(QLLM_ERR_UNSUPPORTED, "attn_prefill serves 1..%d query heads per kv head (got %d)", kAttnDecodeMaxGroup, q_heads / kv_heads);
+  int rc = check_attn_served("attn_prefill", q_heads, kv_heads, head_dim);
+  if (rc != QLLM_OK) return rc;
   if (batch > 65535 || q_heads > 65535)
     return set_error(QLLM_ERR_UNSUPPORTED, "attn_prefill serves batch <= 65535 and q_heads <= 65535 (got %d, %d)", batch, q_heads);
   return QLLM_OK;
@@ -1135,7 +1163,7 @@ int qllm_attn_prefill_describe(int32_t batch, int32_t q_heads, int32_t kv_heads,
                                size_t buflen) {
   clear_error();
   if (!buf || buflen == 0) return set_error(QLLM_ERR_INVALID, "buf must not be NULL or empty");
-  int rc = check_attn_prefill_shape(batch, q_heads, kv_heads, head_dim, q_len, max_len);
+  int rc = check_attn_shape(batch, q_heads, kv_heads, head_dim, &q_len, max_len);
   if (rc == QLLM_OK) rc = check_attn_prefill_served(batch, q_heads, kv_heads, head_dim);
   if (rc != QLLM_OK) return describe_refusal(rc, kRefused, buf, buflen);
   snprintf(buf, buflen, "attn_prefill q_tile=%d kv_tile=%d grid=%dx%dx%d group=%d", kAttnPrefillQTile, kAttnPrefillKvTile,
@@ -1159,23 +1187,13 @@ int qllm_attn_prefill_window(const void *q, const void *k_cache, const void *v_c
                              int64_t cache_pos_stride, int32_t mask_kind, int64_t mask_len, int64_t mask_batch_stride, int64_t mask_row_stride,
                              int32_t causal, float scaling, int32_t act_dtype, void *stream) {
   clear_error();
-  if (!q || !k_cache || !v_cache || !out) return set_error(QLLM_ERR_INVALID, "q / k_cache / v_cache / out must not be NULL");
-  int rc = check_attn_prefill_shape(batch, q_heads, kv_heads, head_dim, q_len, max_len);
+  int rc = check_attn_call(q, k_cache, v_cache, out, batch, q_heads, kv_heads, head_dim, &q_len, max_len, window, act_dtype, mask_kind, mask);
   if (rc != QLLM_OK) return rc;
-  if (window < 0) return set_error(QLLM_ERR_INVALID, "window must be 0 (none) or >= 1 (got %lld)", (long long)window);
-  if (act_dtype != QLLM_F16 && act_dtype != QLLM_BF16) return set_error(QLLM_ERR_INVALID, "act_dtype must be QLLM_F16 or QLLM_BF16");
-  if (mask_kind != QLLM_ATTN_MASK_NONE && mask_kind != QLLM_ATTN_MASK_BOOL && mask_kind != QLLM_ATTN_MASK_ADDITIVE)
-    return set_error(QLLM_ERR_INVALID, "mask_kind must be QLLM_ATTN_MASK_NONE, _BOOL or _ADDITIVE (got %d)", mask_kind);
-  if ((mask_kind == QLLM_ATTN_MASK_NONE) != (mask == nullptr)) return set_error(QLLM_ERR_INVALID, "mask must be NULL exactly with QLLM_ATTN_MASK_NONE");
   if (causal != 0 && causal != 1) return set_error(QLLM_ERR_INVALID, "causal must be 0 or 1 (got %d)", causal);
-  if ((uintptr_t)q % 16 || (uintptr_t)k_cache % 16 || (uintptr_t)v_cache % 16 || (uintptr_t)out % 16)
-    return set_error(QLLM_ERR_INVALID, "q / k_cache / v_cache / out must be 16-byte aligned");
-  if ((uintptr_t)kv_len_dev % 8 || (mask_kind == QLLM_ATTN_MASK_ADDITIVE && (uintptr_t)mask % 2))
-    return set_error(QLLM_ERR_INVALID, "kv_len_dev must be 8-byte aligned and an additive mask 2-byte aligned");
   const int64_t strides[6] = {q_batch_stride, q_head_stride, q_row_stride, cache_batch_stride, cache_head_stride, cache_pos_stride};
-  for (int i = 0; i < 6; ++i)
-    if (strides[i] < 0 || strides[i] % 8 != 0)
-      return set_error(QLLM_ERR_INVALID, "batch, head, row and position strides must be non-negative multiples of 8 elements (got %lld)", (long long)strides[i]);
+  const void *const ptrs[4] = {q, k_cache, v_cache, out};
+  rc = check_attn_layout("q / k_cache / v_cache / out", ptrs, 4, kv_len_dev, mask_kind, mask, "batch, head, row and position", strides, 6);
+  if (rc != QLLM_OK) return rc;
   if (!kv_len_dev && (kv_len < q_len || kv_len > max_len))
     return set_error(QLLM_ERR_INVALID, "kv_len must lie in q_len..max_len (got kv_len=%lld q_len=%d max_len=%lld)", (long long)kv_len, q_len, (long long)max_len);
   const int64_t need_len = kv_len_dev ? max_len : kv_len;  // the positions a call may reach

@@ -98,37 +98,56 @@ def _length_after_update(layer, kind, keys):
     return keys.shape[2]
 
 
+def _gate(self, q, k, v, attention_mask, past_key_values, kwargs, window, rows, uninitialized=False):
+    """The conditions both cores share, for a call of `rows` query rows: (the cache layer, its kind, the call's sliding window or None),
+    or None for the family's route.  Implementation, training, types, device, autograd, kwargs, the mask's form ([B, 1, rows, L'], bool
+    or of the activation type), `_layer_of` (`uninitialized`: a static layer may still be empty) and, on a static layer that holds its
+    buffers, their type, batch and head size.  Nothing here touches the cache."""
+    if past_key_values is None or self.training or self.config._attn_implementation not in ("sdpa", "eager"):
+        return None
+    if q.dtype not in _ACT_DTYPES or k.dtype != q.dtype or v.dtype != q.dtype or not _on_device(q, k, v):
+        return None
+    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+        return None
+    sliding = getattr(self.config, "sliding_window", None) if window == "config" else getattr(self, "sliding_window", None) if window == "self" else None
+    if any(val is not None and val is not False for name, val in kwargs.items() if name not in _BENIGN):
+        return None
+    if attention_mask is not None and not (isinstance(attention_mask, torch.Tensor) and attention_mask.dim() == 4 and attention_mask.shape[1] == 1
+                                           and attention_mask.shape[2] == rows and (attention_mask.dtype == torch.bool or attention_mask.dtype == q.dtype)):
+        return None
+    layer, kind = _layer_of(past_key_values, self.layer_idx, uninitialized=uninitialized, sliding=sliding)
+    if layer is None:
+        return None
+    if kind.startswith("static") and layer.is_initialized and (layer.keys.dtype != q.dtype or layer.keys.shape[0] != q.shape[0] or layer.keys.shape[3] != q.shape[3]):
+        return None
+    return layer, kind, sliding
+
+
+def _update_and_attend(self, q, k, v, attention_mask, past_key_values, layer, kind, sliding):
+    """Behind the last refusal that leaves the cache alone: `update`, once, then ops.attn_decode (one query row) or ops.attn_prefill
+    (causal) over what it returned where that op's plan serves it -- with `window=` on a sliding layer only -- else None and the updated
+    states for the family's route."""
+    keys, values = past_key_values.update(k, v, self.layer_idx)
+    length = _length_after_update(layer, kind, keys)
+    decode = q.shape[2] == 1
+    try:
+        plan = (ops.attn_decode_plan if decode else ops.attn_prefill_plan)(q, keys, values, length, mask=attention_mask)
+    except ops.QllmUnsupported:
+        return None, keys, values, True
+    how = {} if decode else {"causal": True}
+    if sliding is not None:
+        how["window"] = sliding
+    with torch.no_grad():
+        return (ops.attn_decode if decode else ops.attn_prefill)(q, keys, values, length, mask=attention_mask, scaling=self.scaling, plan=plan, **how), keys, values, True
+
+
 def _fused_core(self, q, k, v, attention_mask, past_key_values, kwargs, window):
     """(the attention output [B, Hq, D] or None, key states, value states, whether the cache has been updated) of one forward: the kernel
     where the conditions of this file's docstring hold, else None and the states for the family's route."""
-    no = (None, k, v, False)
-    if q.shape[2] != 1 or past_key_values is None or self.training or self.config._attn_implementation not in ("sdpa", "eager"):
-        return no
-    if q.dtype not in _ACT_DTYPES or k.dtype != q.dtype or v.dtype != q.dtype or not _on_device(q, k, v):
-        return no
-    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
-        return no
-    sliding = getattr(self.config, "sliding_window", None) if window == "config" else getattr(self, "sliding_window", None) if window == "self" else None
-    if any(val is not None and val is not False for name, val in kwargs.items() if name not in _BENIGN):
-        return no
-    if attention_mask is not None and not (isinstance(attention_mask, torch.Tensor) and attention_mask.dim() == 4 and attention_mask.shape[1] == 1
-                                           and attention_mask.shape[2] == 1 and (attention_mask.dtype == torch.bool or attention_mask.dtype == q.dtype)):
-        return no
-    layer, kind = _layer_of(past_key_values, self.layer_idx, sliding=sliding)
-    if layer is None:
-        return no
-    if kind.startswith("static") and (layer.keys.dtype != q.dtype or layer.keys.shape[0] != q.shape[0] or layer.keys.shape[3] != q.shape[3]):
-        return no
-    keys, values = past_key_values.update(k, v, self.layer_idx)
-    length = _length_after_update(layer, kind, keys)
-    try:
-        plan = ops.attn_decode_plan(q, keys, values, length, mask=attention_mask)
-    except ops.QllmUnsupported:
-        return None, keys, values, True
-    with torch.no_grad():
-        if sliding is not None:
-            return ops.attn_decode(q, keys, values, length, mask=attention_mask, scaling=self.scaling, plan=plan, window=sliding), keys, values, True
-        return ops.attn_decode(q, keys, values, length, mask=attention_mask, scaling=self.scaling, plan=plan), keys, values, True
+    served = _gate(self, q, k, v, attention_mask, past_key_values, kwargs, window, 1) if q.shape[2] == 1 else None
+    if served is None:
+        return None, k, v, False
+    return _update_and_attend(self, q, k, v, attention_mask, past_key_values, *served)
 
 
 # What `_fused_core_prefill` hands to ops.attn_prefill, by (cache layer kind, whether the call carries a mask): the q_len range (lowest,
@@ -195,41 +214,17 @@ def _fused_core_prefill(self, q, k, v, attention_mask, past_key_values, kwargs, 
     if q.shape[2] == 1:
         return _fused_core(self, q, k, v, attention_mask, past_key_values, kwargs, window)
     no = (None, k, v, False)
-    if past_key_values is None or self.training or self.config._attn_implementation not in ("sdpa", "eager") or not getattr(self, "is_causal", False):
-        return no
-    if q.dtype not in _ACT_DTYPES or k.dtype != q.dtype or v.dtype != q.dtype or not _on_device(q, k, v):
-        return no
-    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
-        return no
-    sliding = getattr(self.config, "sliding_window", None) if window == "config" else getattr(self, "sliding_window", None) if window == "self" else None
-    if any(val is not None and val is not False for name, val in kwargs.items() if name not in _BENIGN):
-        return no
     s = q.shape[2]
-    if attention_mask is not None and not (isinstance(attention_mask, torch.Tensor) and attention_mask.dim() == 4 and attention_mask.shape[1] == 1
-                                           and attention_mask.shape[2] == s and (attention_mask.dtype == torch.bool or attention_mask.dtype == q.dtype)):
+    served = _gate(self, q, k, v, attention_mask, past_key_values, kwargs, window, s, uninitialized=True) if getattr(self, "is_causal", False) else None
+    if served is None:
         return no
-    layer, kind = _layer_of(past_key_values, self.layer_idx, uninitialized=True, sliding=sliding)
-    if layer is None:
-        return no
+    layer, kind, sliding = served
     static = kind.startswith("static")
     held = layer.is_initialized if static else layer.get_seq_length() != 0   # (a static layer: may hold tokens; its length is on the device)
     behind = layer.is_initialized and layer.cumulative_length_int != 0 if kind == "static_sliding" else held and not static
-    if not _prefill_routed(kind, attention_mask is not None, s, behind, sliding):
+    if not _prefill_routed(kind, attention_mask is not None, s, behind, sliding) or (attention_mask is None and held):
         return no
-    if attention_mask is None and held:
-        return no
-    if static and layer.is_initialized and (layer.keys.dtype != q.dtype or layer.keys.shape[0] != q.shape[0] or layer.keys.shape[3] != q.shape[3]):
-        return no
-    keys, values = past_key_values.update(k, v, self.layer_idx)
-    length = _length_after_update(layer, kind, keys)
-    try:
-        plan = ops.attn_prefill_plan(q, keys, values, length, mask=attention_mask)
-    except ops.QllmUnsupported:
-        return None, keys, values, True
-    with torch.no_grad():
-        if sliding is not None:
-            return ops.attn_prefill(q, keys, values, length, mask=attention_mask, causal=True, scaling=self.scaling, plan=plan, window=sliding), keys, values, True
-        return ops.attn_prefill(q, keys, values, length, mask=attention_mask, causal=True, scaling=self.scaling, plan=plan), keys, values, True
+    return _update_and_attend(self, q, k, v, attention_mask, past_key_values, layer, kind, sliding)
 
 
 def count_fused_attention_prefill(model: torch.nn.Module) -> int:

@@ -586,6 +586,8 @@ def rope(q: torch.Tensor, k: Optional[torch.Tensor], cos: torch.Tensor, sin: tor
 
 ATTN_DECODE_HEAD_DIMS = (64, 128)   # what csrc/attn_decode.hip is built for
 ATTN_DECODE_MAX_GROUP = 8           # kAttnDecodeMaxGroup of csrc/kernels.hpp
+ATTN_DECODE_COUNTERS = 4096         # kCounterBytes / sizeof(int) of csrc/planner.hpp: attn_decode takes one arrival counter per (sequence, kv
+                                    # head) from the counter page at the head of the workspace
 
 
 def _attn_heads(t: torch.Tensor, name: str):
@@ -615,6 +617,84 @@ def _attn_window(window, name: str) -> int:
     return window
 
 
+# ---- the rules attn_decode_plan and attn_prefill_plan share, each written once; `no(why)` makes the caller's QllmUnsupported ----------------
+def _attn_refusal(name: str):
+    return lambda why: QllmUnsupported(_lib.QLLM_ERR_UNSUPPORTED, name + ": " + why)
+
+
+def _attn_one_type_and_device(no, who: str, ts, mask):
+    """q (ts[0]) and the other tensors of `ts` -- `who` names them -- have one fp16 / bf16 type, and with the mask one device."""
+    dtype, device = ts[0].dtype, ts[0].device
+    if dtype not in (torch.float16, torch.bfloat16) or [t.dtype for t in ts].count(dtype) != len(ts):
+        raise no(who + " must share one type, float16 or bfloat16 (got " + ", ".join(str(t.dtype)[6:] for t in ts) + ")")
+    if [t.device for t in ts].count(device) != len(ts) or (mask is not None and mask.device != device):
+        raise no("every tensor must be on one device")
+
+
+def _attn_cache_shape(no, k_cache, v_cache, b: int, d: int):
+    """(kv heads, positions) of two [B, Hkv, L, D] caches of one shape and layout that go with q's B and D."""
+    shape = k_cache.shape
+    if len(shape) != 4 or shape != v_cache.shape or k_cache.stride() != v_cache.stride() or shape[0] != b or shape[3] != d:
+        raise no(f"the caches must be two [B, Hkv, L, D] tensors of one shape and layout with q's B and D (got {tuple(shape)}, {tuple(v_cache.shape)})")
+    if shape[1] == 0 or shape[2] == 0:
+        raise no("empty caches")
+    return shape[1], shape[2]
+
+
+def _attn_served_heads(no, hq: int, hkv: int, d: int):
+    if hq % hkv:
+        raise no(f"the kv heads must divide the query heads (got {hq}, {hkv})")
+    if d not in ATTN_DECODE_HEAD_DIMS:
+        raise no(f"head_dim 64 or 128 (got {d})")
+    if hq // hkv > ATTN_DECODE_MAX_GROUP:
+        raise no(f"at most {ATTN_DECODE_MAX_GROUP} query heads per kv head (got {hq // hkv})")
+
+
+def _attn_cache_strides(no, k_cache, v_cache):
+    """The caches' batch, head and position strides (0 for a dimension of one entry); behind the head rules, as the refusals are ordered."""
+    shape, strides = k_cache.shape, k_cache.stride()
+    cs = tuple([strides[i] if shape[i] > 1 else 0 for i in range(3)])
+    if strides[3] != 1 or [x for x in cs if x % 8 or x < 0] or k_cache.data_ptr() % 16 or v_cache.data_ptr() % 16:
+        raise no(f"the caches must have contiguous head rows, 16-byte aligned, with strides that are multiples of 8 (got {strides})")
+    return cs
+
+
+def _attn_length_on_device(no, length, q) -> bool:
+    """Whether `length` is a tensor the kernel reads: then a 0-d int64 one on q's device."""
+    if not isinstance(length, torch.Tensor):
+        return False
+    if length.dim() != 0 or length.dtype != torch.int64 or length.device != q.device:
+        raise no("a length on the device must be a 0-d int64 tensor on q's device")
+    return True
+
+
+def _attn_mask_kind(no, mask, q, mask_len: int, need: int, *strides) -> int:
+    """The kind of a mask whose form the caller has accepted: bool, or additive in q's type; it covers the `need` positions the call may reach."""
+    if mask.dtype == torch.bool:
+        kind = _lib.ATTN_MASK_BOOL
+    elif mask.dtype == q.dtype and mask.data_ptr() % 2 == 0:
+        kind = _lib.ATTN_MASK_ADDITIVE
+    else:
+        raise no(f"the mask must be bool or additive in {str(q.dtype)[6:]} (got {str(mask.dtype)[6:]})")
+    if mask_len < need or min(strides) < 0:
+        raise no(f"the mask must cover {need} positions (got {mask_len})")
+    return kind
+
+
+def _attn_call(name: str, q, k_cache, v_cache, length, scaling, out, shape, d: int):
+    """What attn_decode and attn_prefill settle behind the plan: device tensors, `out` (made when None), and (out, kv_len, kv_len_dev,
+    scaling) as the C entries take them."""
+    for t in (q, k_cache, v_cache):
+        if not t.is_cuda:
+            raise RuntimeError(f"{name}: q and the caches must be HIP/CUDA tensors (qllm_amd has no CPU forward path)")
+    if out is None:
+        out = torch.empty(shape, dtype=q.dtype, device=q.device)
+    elif out.shape != shape or out.dtype != q.dtype or out.device != q.device or not out.is_contiguous():
+        raise RuntimeError(f"{name}: out must be a contiguous {shape} {q.dtype} tensor on {q.device}")
+    on_device = isinstance(length, torch.Tensor)
+    return out, 0 if on_device else int(length), length.data_ptr() if on_device else None, float(d ** -0.5 if scaling is None else scaling)
+
+
 def attn_decode_plan(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, length, k_new: Optional[torch.Tensor] = None,
                      v_new: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None):
     """What `attn_decode` hands to qllm_attn_decode for these tensors -- (batch, q_heads, kv_heads, head_dim, max_len, q row / head stride,
@@ -624,32 +704,16 @@ def attn_decode_plan(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
     strides; Hkv divides Hq, at most 8 query heads per kv head; D 64 or 128; mask None, [B, 1, 1, L'] or [B, L'] (B or 1 rows), bool or of
     the activation type, inner stride 1; `length` an int (0..L, L - 1 at most with an append; the mask covers it) or a 0-d int64 tensor on
     the device (the mask then covers L).  Pure host code, any device."""
-    def no(why):
-        return QllmUnsupported(_lib.QLLM_ERR_UNSUPPORTED, "attn_decode: " + why)
+    no = _attn_refusal("attn_decode")
     if (k_new is None) != (v_new is None):
         raise no("k_new and v_new must be given together or not at all")
-    ts = [("q", q), ("k_cache", k_cache), ("v_cache", v_cache)] + ([("k_new", k_new), ("v_new", v_new)] if k_new is not None else [])
-    if q.dtype not in (torch.float16, torch.bfloat16) or any(t.dtype != q.dtype for _, t in ts):
-        raise no("q, the caches and k_new / v_new must share one type, float16 or bfloat16 (got " + ", ".join(str(t.dtype)[6:] for _, t in ts) + ")")
-    if any(t.device != q.device for _, t in ts) or (mask is not None and mask.device != q.device):
-        raise no("every tensor must be on one device")
+    _attn_one_type_and_device(no, "q, the caches and k_new / v_new", (q, k_cache, v_cache) + ((k_new, v_new) if k_new is not None else ()), mask)
     b, hq, d, q_row, q_head = _attn_heads(q, "q")
-    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape or k_cache.stride() != v_cache.stride() or k_cache.shape[0] != b or k_cache.shape[3] != d:
-        raise no(f"the caches must be two [B, Hkv, L, D] tensors of one shape and layout with q's B and D (got {tuple(k_cache.shape)}, {tuple(v_cache.shape)})")
-    hkv, max_len = k_cache.shape[1], k_cache.shape[2]
-    if hkv == 0 or max_len == 0:
-        raise no("empty caches")
-    if hq % hkv:
-        raise no(f"the kv heads must divide the query heads (got {hq}, {hkv})")
-    if d not in ATTN_DECODE_HEAD_DIMS:
-        raise no(f"head_dim 64 or 128 (got {d})")
-    if hq // hkv > ATTN_DECODE_MAX_GROUP:
-        raise no(f"at most {ATTN_DECODE_MAX_GROUP} query heads per kv head (got {hq // hkv})")
-    if b * hkv > 4096 or b > 65535:
-        raise no(f"batch * kv_heads <= 4096 (got {b * hkv})")
-    cs = [k_cache.stride(i) if k_cache.shape[i] > 1 else 0 for i in range(3)]
-    if k_cache.stride(3) != 1 or any(s % 8 or s < 0 for s in cs) or k_cache.data_ptr() % 16 or v_cache.data_ptr() % 16:
-        raise no(f"the caches must have contiguous head rows, 16-byte aligned, with strides that are multiples of 8 (got {tuple(k_cache.stride())})")
+    hkv, max_len = _attn_cache_shape(no, k_cache, v_cache, b, d)
+    _attn_served_heads(no, hq, hkv, d)
+    if b * hkv > ATTN_DECODE_COUNTERS or b > 65535:
+        raise no(f"batch * kv_heads <= {ATTN_DECODE_COUNTERS} (got {b * hkv})")
+    cs = _attn_cache_strides(no, k_cache, v_cache)
     new = (0, 0, 0, 0)
     if k_new is not None:
         kb, kh, kd, k_row, k_head = _attn_heads(k_new, "k_new")
@@ -657,12 +721,8 @@ def attn_decode_plan(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
         if (kb, kh, kd) != (b, hkv, d) or (vb, vh, vd) != (b, hkv, d):
             raise no(f"k_new and v_new must be one token of [{b}, {hkv}, {d}] (got {tuple(k_new.shape)}, {tuple(v_new.shape)})")
         new = (k_row, k_head, v_row, v_head)
-    on_device = isinstance(length, torch.Tensor)
-    if on_device:
-        if length.dim() != 0 or length.dtype != torch.int64 or length.device != q.device:
-            raise no("a length on the device must be a 0-d int64 tensor on q's device")
-        need = max_len
-    else:
+    need = max_len
+    if not _attn_length_on_device(no, length, q):
         length = int(length)
         need = length + (1 if k_new is not None else 0)
         if length < 0 or need > max_len:
@@ -672,16 +732,9 @@ def attn_decode_plan(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
         m2 = mask[:, 0, 0] if mask.dim() == 4 and mask.shape[1] == 1 and mask.shape[2] == 1 else mask
         if m2.dim() != 2 or m2.shape[0] not in (1, b) or (m2.shape[1] > 1 and m2.stride(1) != 1):
             raise no(f"the mask must be [B, 1, 1, L] or [B, L] with B = {b} or 1 and inner stride 1 (got {tuple(mask.shape)}, strides {tuple(mask.stride())})")
-        if mask.dtype == torch.bool:
-            kind = _lib.ATTN_MASK_BOOL
-        elif mask.dtype == q.dtype and mask.data_ptr() % 2 == 0:
-            kind = _lib.ATTN_MASK_ADDITIVE
-        else:
-            raise no(f"the mask must be bool or additive in {str(q.dtype)[6:]} (got {str(mask.dtype)[6:]})")
         mask_len, mask_batch = m2.shape[1], (m2.stride(0) if m2.shape[0] > 1 else 0)
-        if mask_len < need or mask_batch < 0:
-            raise no(f"the mask must cover {need} positions (got {mask_len})")
-    return (b, hq, hkv, d, max_len, q_row, q_head) + new + tuple(cs) + (kind, mask_len, mask_batch)
+        kind = _attn_mask_kind(no, mask, q, mask_len, need, mask_batch)
+    return (b, hq, hkv, d, max_len, q_row, q_head) + new + cs + (kind, mask_len, mask_batch)
 
 
 def attn_decode_describe(batch: int, q_heads: int, kv_heads: int, head_dim: int, max_len: int) -> str:
@@ -708,21 +761,13 @@ def attn_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, l
     if plan is None:
         plan = attn_decode_plan(q, k_cache, v_cache, length, k_new, v_new, mask)
     b, hq, hkv, d, max_len = plan[:5]
-    for t in (q, k_cache, v_cache):
-        if not t.is_cuda:
-            raise RuntimeError("attn_decode: q and the caches must be HIP/CUDA tensors (qllm_amd has no CPU forward path)")
-    if out is None:
-        out = torch.empty((b, hq, d), dtype=q.dtype, device=q.device)
-    elif out.shape != (b, hq, d) or out.dtype != q.dtype or out.device != q.device or not out.is_contiguous():
-        raise RuntimeError(f"attn_decode: out must be a contiguous {(b, hq, d)} {q.dtype} tensor on {q.device}")
-    on_device = isinstance(length, torch.Tensor)
+    out, kv_len, kv_len_dev, scaling = _attn_call("attn_decode", q, k_cache, v_cache, length, scaling, out, (b, hq, d), d)
     lib = _lib.load()
     with torch.cuda.device(q.device):
         nbytes = lib.qllm_attn_decode_workspace_bytes(b, hq, hkv, d, max_len)
         ws = workspace(q.device, nbytes)
         rc = lib.qllm_attn_decode_window(q.data_ptr(), _ptr(k_new), _ptr(v_new), k_cache.data_ptr(), v_cache.data_ptr(), _ptr(mask), out.data_ptr(),
-                                         b, hq, hkv, d, 0 if on_device else int(length), length.data_ptr() if on_device else None, max_len, window,
-                                         *plan[5:], float(d ** -0.5 if scaling is None else scaling), _act_dtype(q), ws.data_ptr(), ws.numel(),
+                                         b, hq, hkv, d, kv_len, kv_len_dev, max_len, window, *plan[5:], scaling, _act_dtype(q), ws.data_ptr(), ws.numel(),
                                          _stream_ptr())
     _lib.check(rc)
     return out
@@ -736,13 +781,8 @@ def attn_prefill_plan(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
     strides, already holding the S new rows; Hkv divides Hq, at most 8 query heads per kv head; D 64 or 128; mask None, [B, 1, S, L'] or
     [B, S, L'] (B or 1 batch rows, expanded views included), bool or of the activation type, inner stride 1; `length` an int (S..L; the mask
     covers it) or a 0-d int64 tensor on the device (the mask then covers L).  Pure host code, any device."""
-    def no(why):
-        return QllmUnsupported(_lib.QLLM_ERR_UNSUPPORTED, "attn_prefill: " + why)
-    ts = [("q", q), ("k_cache", k_cache), ("v_cache", v_cache)]
-    if q.dtype not in (torch.float16, torch.bfloat16) or any(t.dtype != q.dtype for _, t in ts):
-        raise no("q and the caches must share one type, float16 or bfloat16 (got " + ", ".join(str(t.dtype)[6:] for _, t in ts) + ")")
-    if any(t.device != q.device for _, t in ts) or (mask is not None and mask.device != q.device):
-        raise no("every tensor must be on one device")
+    no = _attn_refusal("attn_prefill")
+    _attn_one_type_and_device(no, "q and the caches", (q, k_cache, v_cache), mask)
     if q.dim() != 4 or 0 in q.shape:
         raise no(f"q must be a non-empty [B, Hq, S, D] tensor or view (got {tuple(q.shape)})")
     b, hq, s, d = q.shape
@@ -750,32 +790,18 @@ def attn_prefill_plan(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
         raise no(f"q must hold at least two rows per sequence (got {s}); one token is attn_decode's")
     if q.stride(3) != 1:
         raise no(f"the last dimension of q must have stride 1 (got {q.stride(3)})")
-    qs = [q.stride(i) if q.shape[i] > 1 else 0 for i in range(3)]
+    qs = tuple(q.stride(i) if q.shape[i] > 1 else 0 for i in range(3))
     if any(x % 8 or x < 0 for x in qs) or q.data_ptr() % 16:
         raise no(f"q must be 16-byte aligned with strides that are non-negative multiples of 8 (got {tuple(q.stride())})")
-    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape or k_cache.stride() != v_cache.stride() or k_cache.shape[0] != b or k_cache.shape[3] != d:
-        raise no(f"the caches must be two [B, Hkv, L, D] tensors of one shape and layout with q's B and D (got {tuple(k_cache.shape)}, {tuple(v_cache.shape)})")
-    hkv, max_len = k_cache.shape[1], k_cache.shape[2]
-    if hkv == 0 or max_len == 0:
-        raise no("empty caches")
-    if hq % hkv:
-        raise no(f"the kv heads must divide the query heads (got {hq}, {hkv})")
-    if d not in ATTN_DECODE_HEAD_DIMS:
-        raise no(f"head_dim 64 or 128 (got {d})")
-    if hq // hkv > ATTN_DECODE_MAX_GROUP:
-        raise no(f"at most {ATTN_DECODE_MAX_GROUP} query heads per kv head (got {hq // hkv})")
+    hkv, max_len = _attn_cache_shape(no, k_cache, v_cache, b, d)
+    _attn_served_heads(no, hq, hkv, d)
     if b > 65535 or hq > 65535:
         raise no(f"batch <= 65535 and q_heads <= 65535 (got {b}, {hq})")
     if s > max_len:
         raise no(f"the caches must hold the {s} query rows (got {max_len} positions)")
-    cs = [k_cache.stride(i) if k_cache.shape[i] > 1 else 0 for i in range(3)]
-    if k_cache.stride(3) != 1 or any(x % 8 or x < 0 for x in cs) or k_cache.data_ptr() % 16 or v_cache.data_ptr() % 16:
-        raise no(f"the caches must have contiguous head rows, 16-byte aligned, with strides that are multiples of 8 (got {tuple(k_cache.stride())})")
-    if isinstance(length, torch.Tensor):
-        if length.dim() != 0 or length.dtype != torch.int64 or length.device != q.device:
-            raise no("a length on the device must be a 0-d int64 tensor on q's device")
-        need = max_len
-    else:
+    cs = _attn_cache_strides(no, k_cache, v_cache)
+    need = max_len
+    if not _attn_length_on_device(no, length, q):
         need = int(length)
         if need < s or need > max_len:
             raise no(f"the length must lie in {s}..{max_len} (got {need})")
@@ -784,16 +810,9 @@ def attn_prefill_plan(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
         m3 = mask[:, 0] if mask.dim() == 4 and mask.shape[1] == 1 else mask
         if m3.dim() != 3 or m3.shape[0] not in (1, b) or m3.shape[1] != s or (m3.shape[2] > 1 and m3.stride(2) != 1):
             raise no(f"the mask must be [B, 1, S, L] or [B, S, L] with B = {b} or 1, S = {s} and inner stride 1 (got {tuple(mask.shape)}, strides {tuple(mask.stride())})")
-        if mask.dtype == torch.bool:
-            kind = _lib.ATTN_MASK_BOOL
-        elif mask.dtype == q.dtype and mask.data_ptr() % 2 == 0:
-            kind = _lib.ATTN_MASK_ADDITIVE
-        else:
-            raise no(f"the mask must be bool or additive in {str(q.dtype)[6:]} (got {str(mask.dtype)[6:]})")
         mask_len, mask_batch, mask_row = m3.shape[2], (m3.stride(0) if m3.shape[0] > 1 else 0), m3.stride(1)
-        if mask_len < need or mask_batch < 0 or mask_row < 0:
-            raise no(f"the mask must cover {need} positions (got {mask_len})")
-    return (b, hq, hkv, d, s, max_len) + tuple(qs) + tuple(cs) + (kind, mask_len, mask_batch, mask_row)
+        kind = _attn_mask_kind(no, mask, q, mask_len, need, mask_batch, mask_row)
+    return (b, hq, hkv, d, s, max_len) + qs + cs + (kind, mask_len, mask_batch, mask_row)
 
 
 def attn_prefill_describe(batch: int, q_heads: int, kv_heads: int, head_dim: int, q_len: int, max_len: int) -> str:
@@ -821,19 +840,10 @@ def attn_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, 
     if plan is None:
         plan = attn_prefill_plan(q, k_cache, v_cache, length, mask)
     b, hq, hkv, d, s, max_len = plan[:6]
-    for t in (q, k_cache, v_cache):
-        if not t.is_cuda:
-            raise RuntimeError("attn_prefill: q and the caches must be HIP/CUDA tensors (qllm_amd has no CPU forward path)")
-    if out is None:
-        out = torch.empty((b, s, hq, d), dtype=q.dtype, device=q.device)
-    elif out.shape != (b, s, hq, d) or out.dtype != q.dtype or out.device != q.device or not out.is_contiguous():
-        raise RuntimeError(f"attn_prefill: out must be a contiguous {(b, s, hq, d)} {q.dtype} tensor on {q.device}")
-    on_device = isinstance(length, torch.Tensor)
+    out, kv_len, kv_len_dev, scaling = _attn_call("attn_prefill", q, k_cache, v_cache, length, scaling, out, (b, s, hq, d), d)
     with torch.cuda.device(q.device):
         rc = _lib.load().qllm_attn_prefill_window(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), _ptr(mask), out.data_ptr(), b, hq, hkv, d, s,
-                                                  0 if on_device else int(length), length.data_ptr() if on_device else None, max_len, window,
-                                                  *plan[6:16], 1 if causal else 0, float(d ** -0.5 if scaling is None else scaling), _act_dtype(q),
-                                                  _stream_ptr())
+                                                  kv_len, kv_len_dev, max_len, window, *plan[6:16], 1 if causal else 0, scaling, _act_dtype(q), _stream_ptr())
     _lib.check(rc)
     return out
 

@@ -7,6 +7,7 @@ Module tolerance: the restated op rounds once where the eager route rounds score
 ulps of the activation type; logits of the tiny fp16 models (magnitude below 2) are held to 2e-2 absolute, and the float32 models'
 logits, which take the family's route, to exact equality."""
 import ctypes as C
+import functools
 import os
 import re
 
@@ -14,6 +15,7 @@ import pytest
 import torch
 
 from attn_decode_cases import eager, oracle, parse_describe, restated
+from attn_entry_cases import DECODE_PTRS, DECODE_STRIDES, decode_call
 from kernel_resources import resources
 from test_rope_cpu import module_dicts
 
@@ -62,14 +64,8 @@ def test_symbols_are_exported_declared_and_bound(lib):
 
 def test_every_argument_check_fires_before_any_device_work(lib):
     INV, UNS, WS = _lib.QLLM_ERR_INVALID, _lib.QLLM_ERR_UNSUPPORTED, _lib.QLLM_ERR_WORKSPACE
-    P = {n: 4096 * (i + 1) for i, n in enumerate(("q", "k_new", "v_new", "k_cache", "v_cache", "mask", "out", "len_dev", "ws"))}
-    S0 = (512, 64, 128, 64, 128, 64, 2 * 100 * 64, 100 * 64, 64)
-
-    def call(b=2, hq=8, hk=2, d=64, kv_len=10, max_len=100, strides=S0, mask_kind=_lib.ATTN_MASK_BOOL, mask_len=100, mask_batch=100, dt=_lib.DT_F16,
-             ws_bytes=1 << 30, **ptrs):
-        p = dict(dict(P, len_dev=None, ws=None), **ptrs)   # no workspace: a call that passes every other check ends at that one, never at a launch
-        return lib.qllm_attn_decode(p["q"], p["k_new"], p["v_new"], p["k_cache"], p["v_cache"], p["mask"], p["out"], b, hq, hk, d, kv_len, p["len_dev"], max_len,
-                                    *strides, mask_kind, mask_len, mask_batch, 0.125, dt, p["ws"], ws_bytes, None)
+    P, S0 = DECODE_PTRS, DECODE_STRIDES
+    call = functools.partial(decode_call, lib)   # no workspace: a call that passes every other check ends at that one, never at a launch
 
     for name in ("q", "k_cache", "v_cache", "out"):
         assert call(**{name: None}) == INV and "must not be NULL" in _lib.last_error(), name

@@ -6,6 +6,7 @@ and the modules of q_layers/fused_attention.py with ops.attn_prefill (and ops.at
 Module tolerance: tests/test_attn_decode_cpu.py's (the restated op rounds once where the eager route rounds scores, weights and output):
 logits of the tiny fp16 models are held to 2e-2 absolute, and wherever the family's route runs, to exact equality."""
 import ctypes as C
+import functools
 import inspect
 import os
 import re
@@ -13,6 +14,7 @@ import re
 import pytest
 import torch
 
+from attn_entry_cases import PREFILL_PTRS, PREFILL_STRIDES, prefill_call
 from attn_prefill_cases import oracle, eager, parse_describe, restated
 from kernel_resources import resources
 from test_attn_decode_cpu import FAMILIES, close, fake_op, make_cache, prefill_and_decode, tiny_model
@@ -64,14 +66,8 @@ def test_symbols_are_exported_declared_and_bound(lib):
 def test_every_argument_check_fires_before_any_device_work(lib):
     """Every call here is refused: none reaches a launch, so the fake pointers are never dereferenced."""
     INV, UNS = _lib.QLLM_ERR_INVALID, _lib.QLLM_ERR_UNSUPPORTED
-    P = {n: 4096 * (i + 1) for i, n in enumerate(("q", "k_cache", "v_cache", "mask", "out", "len_dev"))}
-    S0 = (5 * 512, 64, 512, 2 * 100 * 64, 100 * 64, 64)
-
-    def call(b=2, hq=8, hk=2, d=64, s=5, kv_len=10, max_len=100, strides=S0, mask_kind=_lib.ATTN_MASK_BOOL, mask_len=100, mask_batch=500, mask_row=100,
-             causal=1, dt=_lib.DT_F16, **ptrs):
-        p = dict(dict(P, len_dev=None), **ptrs)
-        return lib.qllm_attn_prefill(p["q"], p["k_cache"], p["v_cache"], p["mask"], p["out"], b, hq, hk, d, s, kv_len, p["len_dev"], max_len, *strides,
-                                     mask_kind, mask_len, mask_batch, mask_row, causal, 0.125, dt, None)
+    P, S0 = PREFILL_PTRS, PREFILL_STRIDES
+    call = functools.partial(prefill_call, lib)
 
     def refused(status, text, **kw):
         return call(**kw) == status and text in _lib.last_error()
