@@ -124,7 +124,8 @@ int qllm_is_lab_build(void);
  *   QLLM_GEMM2_MIN_M >= 33, QLLM_GEMM3_MIN_M >= 0 (0: the measured 384 / 768 line), QLLM_GEMM2_SPLITK 0|1, QLLM_GEMM3_TAIL 0|1, QLLM_GEMM3_BF16 0|1, QLLM_GEMM3_GROUP 0|1,
  *   QLLM_SKINNY_MAX_M 0..64, QLLM_STRIP_MIN >= 0, QLLM_S1_T256_NW16 0|1 (batch 1, K = 6272..8192: 16 waves x 16 k-steps instead of 8 x 32), QLLM_BITGEMV 0|1, QLLM_BITPANEL 0|1, QLLM_BITPANEL_LDS 0|1, QLLM_BITPANEL_MAX_M 17..512 (the last three: qllm_linear_forward_bitpanel, no route),
  *   QLLM_BITGROUP 0|1, QLLM_BITGROUP_MAX_M 0..16 (qllm_linear_forward_bitgroup, no route),
- *   QLLM_BITGEMM 0|1, QLLM_BITGEMM_MIN_M 129..65536 (qllm_linear_forward_bitgemm, no route).
+ *   QLLM_BITGEMM 0|1, QLLM_BITGEMM_MIN_M 129..65536 (qllm_linear_forward_bitgemm, no route),
+ *   QLLM_GATHER_ROWS 0|1 (qllm_gather_columns, no route; qllm_gather_describe reflects it).
  * qllm_plan_describe() reflects them (it asks the same decision functions the forward calls execute).  QLLM_ERR_INVALID for any other name. */
 int qllm_set_knob(const char *name, int32_t value);
 int qllm_get_knob(const char *name, int32_t *value, int32_t *is_set);
@@ -265,6 +266,13 @@ int qllm_pack_qweight(const int32_t *q_kn, int32_t layout, int32_t bits, int32_t
  * permutation applied to the columns of x at every forward.  perm: K int32 on the device, a permutation of 0..K-1 (entries are
  * not range-checked).  x, perm, out 16-byte aligned, out must not alias x; K % 8 == 0 and K <= 28672, else QLLM_ERR_UNSUPPORTED. */
 int qllm_gather_columns(const void *x, const int32_t *perm, void *out, int32_t M, int32_t K, int32_t act_dtype, void *stream);
+/* The launch qllm_gather_columns makes for M rows of K columns, as text in buf: "gather rows=2 cpt=4 grid=33 lds=57344" (the kernel that
+ * stages `rows` rows per step, `cpt` 8-column chunks per thread) or "gather columns chunks=4 parts=2 rows_per_block=2 grid=32x2 lds=44032"
+ * (the row-at-a-time kernel); "unsupported (...)" for a K the entry refuses, "gather nothing (M=0)" for no rows.  Pure host code, the rule
+ * the launcher itself executes: a function of M, K, the device's CU count (256 without a device) and the knob QLLM_GATHER_ROWS 0|1
+ * (qllm_set_knob; 0: every M on the row-at-a-time kernel).  QLLM_ERR_INVALID: NULL or empty buf, M < 0, K < 1.
+ * ABI: the symbol is ADDITIVE within ABI 7 (QLLM_ABI_VERSION is unchanged): probe for it by symbol. */
+int qllm_gather_describe(int32_t M, int32_t K, char *buf, size_t buflen);
 
 /* y[M,N] = x[:, perm_k] . dequant(w) (+ bias): qllm_gather_columns and qllm_linear_forward in ONE launch, for the layers the bit-stream
  * matvec serves (csrc/bitgemv_ao.hip: the gather happens while the kernel stages x in LDS; no gathered copy of x is written).  The

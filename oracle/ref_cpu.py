@@ -182,13 +182,26 @@ def _dequant_from_ints(q: np.ndarray, scales, zeros, g_idx, groupsize: int) -> n
     return (sq - sz[g]).astype(np.float16)  # one rounding
 
 
+def f16_to_bf16_bits(w16) -> np.ndarray:
+    """The bf16 bit patterns (uint16) of finite fp16 values, rounded to nearest even: what `.to(torch.bfloat16)` gives and what
+    qllm_dequant's bf16 output must hold.  fp16 -> fp32 is exact; bf16 is the top half of the fp32 word, so the rounding is integer
+    work on the 32-bit pattern (the carry into the exponent is the correct result there)."""
+    u = np.asarray(w16, dtype=np.float16).astype(np.float32).view(np.uint32)
+    assert np.isfinite(np.asarray(w16, dtype=np.float32)).all()
+    return ((u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) >> np.uint32(16)).astype(np.uint16)
+
+
 def dequant_gptq(qweight, scales, qzeros, g_idx, bits: int, groupsize: int, in_features: int,
                  add_zero_bias: int = 0) -> np.ndarray:
     """DequantizeLinearBlockWise (quant_linear_gptq.py:13-52) -> W [K, N] fp16.
-    `g_idx=None` is the no-act-order branch (:45-48)."""
+    `g_idx=None` is the no-act-order branch (:45-48).  `qzeros=None` is a symmetric layer: every zero point is 2^(bits-1) (the
+    library's NULL qzeros; the reference stores that value in every field)."""
     n = np.asarray(scales).shape[-1]
     q = gptq_int_weight(qweight, bits, in_features)
-    z = gptq_int_zeros(qzeros, bits, n, add_zero_bias)
+    if qzeros is None:
+        z = np.full(np.asarray(scales).shape, 1 << (bits - 1), dtype=np.int32)
+    else:
+        z = gptq_int_zeros(qzeros, bits, n, add_zero_bias)
     return _dequant_from_ints(q, scales, z, g_idx, groupsize)
 
 

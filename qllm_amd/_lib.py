@@ -63,6 +63,7 @@ SIGNATURES = {
     "qllm_unpack_qweight": (C.c_int, [vp, i32, i32, i32, i32, vp, vp]),
     "qllm_pack_qweight": (C.c_int, [vp, i32, i32, i32, i32, vp, vp]),
     "qllm_gather_columns": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),
+    "qllm_gather_describe": (C.c_int, [i32, i32, C.c_char_p, sz]),
     "qllm_ort_dequantize4bits": (C.c_int, [vp, vp, vp, i32, vp, i32, i32, i32, vp, vp]),
     "qllm_plan_describe": (C.c_int, [wp, i32, i32, i32, C.c_char_p, sz]),
     "qllm_debug_timeline": (C.c_int, [vp, i32]),

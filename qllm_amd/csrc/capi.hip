@@ -483,16 +483,43 @@ int qllm_linear_forward_grouped(const qllm_weight_t *w, void *const *y, int32_t 
   return execute(d, w, y, n_weights, x, M, act_dtype, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+// the two shape checks qllm_gather_columns and qllm_gather_describe share (the entry has its pointer checks between them)
+static int check_gather_shape(int M, int K) {
+  if (M < 0 || K <= 0) return set_error(QLLM_ERR_INVALID, "M must be >= 0 and K >= 1 (got M=%d K=%d)", M, K);
+  return QLLM_OK;
+}
+static int check_gather_served(int K) {
+  if (!gather_columns_ok(K)) return set_error(QLLM_ERR_UNSUPPORTED, "column gather serves K %% 8 == 0, K <= 28672 (got %d)", K);
+  return QLLM_OK;
+}
+
 int qllm_gather_columns(const void *x, const int32_t *perm, void *out, int32_t M, int32_t K, int32_t act_dtype, void *stream) {
   clear_error();
   if (!x || !perm || !out) return set_error(QLLM_ERR_INVALID, "x / perm / out must not be NULL");
-  if (M < 0 || K <= 0) return set_error(QLLM_ERR_INVALID, "M must be >= 0 and K >= 1 (got M=%d K=%d)", M, K);
+  if (int rc = check_gather_shape(M, K)) return rc;
   if (act_dtype != QLLM_F16 && act_dtype != QLLM_BF16) return set_error(QLLM_ERR_INVALID, "act_dtype must be QLLM_F16 or QLLM_BF16");
   if ((uintptr_t)x % 16 || (uintptr_t)out % 16 || (uintptr_t)perm % 16) return set_error(QLLM_ERR_INVALID, "x / perm / out must be 16-byte aligned");
   if (x == out) return set_error(QLLM_ERR_INVALID, "the gather is not in-place: out must not alias x");
-  if (!gather_columns_ok(K)) return set_error(QLLM_ERR_UNSUPPORTED, "column gather serves K %% 8 == 0, K <= 28672 (got %d)", K);
+  if (int rc = check_gather_served(K)) return rc;
   if (M == 0) return QLLM_OK;
   return launch_gather_columns(x, perm, out, M, K, (hipStream_t)stream);
+}
+
+int qllm_gather_describe(int32_t M, int32_t K, char *buf, size_t buflen) {
+  clear_error();
+  if (!buf || buflen == 0) return set_error(QLLM_ERR_INVALID, "buf must not be NULL or empty");
+  if (int rc = check_gather_shape(M, K)) return rc;
+  if (int rc = check_gather_served(K)) return describe_refusal(rc, kUnsupported, buf, buflen);
+  if (M == 0) {
+    snprintf(buf, buflen, "gather nothing (M=0)");
+    return QLLM_OK;
+  }
+  const GatherForm f = gather_form(M, K);
+  if (f.rows)
+    snprintf(buf, buflen, "gather rows=%d cpt=%d grid=%d lds=%zu", f.rows, f.cpt, f.grid, f.lds);
+  else
+    snprintf(buf, buflen, "gather columns chunks=%d parts=%d rows_per_block=%d grid=%dx%d lds=%zu", f.chunks, f.parts, f.rows_per_block, f.grid, f.parts, f.lds);
+  return QLLM_OK;
 }
 
 int qllm_linear_forward_permuted(const qllm_weight_t *w, const int32_t *perm_k, const void *x, void *y, int32_t M, int32_t act_dtype,

@@ -122,64 +122,95 @@ __global__ __launch_bounds__(kG2Threads) void gather_rows_kernel(const uint16_t 
 
 namespace {
 template <int ROWS, int CPT>
-int launch_rows(const void *x, const int32_t *perm, void *out, int M, int K, hipStream_t stream) {
-  const size_t lds = (size_t)ROWS * K * 2;
-  if (lds > 64 * 1024) {
+int launch_rows(const GatherForm &f, const void *x, const int32_t *perm, void *out, int M, int K, hipStream_t stream) {
+  if (f.lds > 64 * 1024) {
     static DeviceLatch attr_done;
     if (int rc = lds_optin(attr_done, (const void *)gather_rows_kernel<ROWS, CPT>)) return rc;
   }
-  const int steps = (M + ROWS - 1) / ROWS;
-  const int grid = min(steps, 2 * compute_units());
-  hipLaunchKernelGGL((gather_rows_kernel<ROWS, CPT>), dim3(grid), dim3(kG2Threads), lds, stream, (const uint16_t *)x, perm, (uint16_t *)out, M, K);
+  hipLaunchKernelGGL((gather_rows_kernel<ROWS, CPT>), dim3(f.grid), dim3(kG2Threads), f.lds, stream, (const uint16_t *)x, perm, (uint16_t *)out, M, K);
   QLLM_HIP_CHECK(hipGetLastError());
   return QLLM_OK;
 }
 
 template <int CHUNKS>
-int launch_b(const void *x, const int32_t *perm, void *out, int M, int K, int parts, hipStream_t stream) {
-  // rows per block: enough blocks to cover the chip several times, at least 2 rows each so the double buffer has something to hide
-  int rows = 1;
-  while (rows < 16 && (M + 2 * rows - 1) / (2 * rows) >= 4 * compute_units()) rows *= 2;
-  if (rows == 1 && M >= 2) rows = 2;
-  const int grid = (M + rows - 1) / rows;
-  if ((size_t)K * 4 > 64 * 1024) {  // above the default dynamic-LDS limit: opt in once per device
+int launch_b(const GatherForm &f, const void *x, const int32_t *perm, void *out, int M, int K, hipStream_t stream) {
+  if (f.lds > 64 * 1024) {  // above the default dynamic-LDS limit: opt in once per device
     static DeviceLatch attr_done;
     if (int rc = lds_optin(attr_done, (const void *)gather_columns_kernel<CHUNKS>)) return rc;
   }
-  hipLaunchKernelGGL(gather_columns_kernel<CHUNKS>, dim3(grid, parts), dim3(kGatherThreads), (size_t)K * 4, stream, (const uint16_t *)x, perm,
-                     (uint16_t *)out, M, K, rows);
+  hipLaunchKernelGGL(gather_columns_kernel<CHUNKS>, dim3(f.grid, f.parts), dim3(kGatherThreads), f.lds, stream, (const uint16_t *)x, perm,
+                     (uint16_t *)out, M, K, f.rows_per_block);
   QLLM_HIP_CHECK(hipGetLastError());
   return QLLM_OK;
 }
+
+// the instantiations that are built; gather_form answers one of these and nothing else
+constexpr int kColumnChunks[] = {1, 2, 4, 6, 8, kMaxChunks};
 }  // namespace
 
 bool gather_columns_ok(int K) { return K % 8 == 0 && K >= 8 && K <= kGatherThreads * 8 * kMaxChunks && (size_t)K * 4 <= 160 * 1024; }
 
-int launch_gather_columns(const void *x, const int32_t *perm, void *out, int M, int K, hipStream_t stream) {
+// THE rule of the gather's launch (M >= 1, gather_columns_ok(K)): which kernel, which instantiation, its grid and its LDS.  The launcher
+// below executes it and qllm_gather_describe prints it; neither decides anything of its own.
+GatherForm gather_form(int M, int K) {
+  GatherForm f = {};
+  const int cus = compute_units();
   if (M >= 64 && knob("QLLM_GATHER_ROWS", 1)) {  // prefill sizes: several rows per step (<= 80 KB of LDS: two blocks per CU)
     const int cpt = ((K >> 3) + kG2Threads - 1) / kG2Threads;
-    const int want = M / (2 * compute_units());  // rows per step that still leave two steps per CU
-    if (cpt == 1) {
-      if (want >= 8) return launch_rows<8, 1>(x, perm, out, M, K, stream);
-      if (want >= 4) return launch_rows<4, 1>(x, perm, out, M, K, stream);
-      return launch_rows<2, 1>(x, perm, out, M, K, stream);
+    const int want = M / (2 * cus);  // rows per step that still leave two steps per CU
+    int rows = 0;
+    if (cpt == 1) rows = want >= 8 ? 8 : want >= 4 ? 4 : 2;
+    else if (cpt == 2) rows = want >= 4 ? 4 : 2;
+    else if (cpt == 3 || cpt == 4) rows = 2;  // cpt 3: K <= 12288 (Llama-2-7B down_proj: 11008); cpt 4: K <= 16384
+    if (rows) {
+      f.rows = rows;
+      f.cpt = cpt;
+      f.steps = (M + rows - 1) / rows;
+      f.grid = min(f.steps, 2 * cus);
+      f.lds = (size_t)rows * K * 2;
+      return f;
     }
-    if (cpt == 2) return want >= 4 ? launch_rows<4, 2>(x, perm, out, M, K, stream) : launch_rows<2, 2>(x, perm, out, M, K, stream);
-    if (cpt == 3) return launch_rows<2, 3>(x, perm, out, M, K, stream);   // K <= 12288 (Llama-2-7B down_proj: 11008)
-    if (cpt == 4) return launch_rows<2, 4>(x, perm, out, M, K, stream);
   }
   const int groups = ((K >> 3) + kGatherThreads - 1) / kGatherThreads;  // 256-thread passes over a row's chunks
   // decode-sized M: split the columns over up to `groups` blocks per row pair, so that a single row is not one block's job
   int parts = 1;
-  while (parts < groups && ((M + 1) / 2) * parts < compute_units() / 4) parts *= 2;
+  while (parts < groups && ((M + 1) / 2) * parts < cus / 4) parts *= 2;
   parts = min(parts, groups);
-  const int chunks = (groups + parts - 1) / parts;
-  if (chunks <= 1) return launch_b<1>(x, perm, out, M, K, parts, stream);
-  if (chunks <= 2) return launch_b<2>(x, perm, out, M, K, parts, stream);
-  if (chunks <= 4) return launch_b<4>(x, perm, out, M, K, parts, stream);
-  if (chunks <= 6) return launch_b<6>(x, perm, out, M, K, parts, stream);
-  if (chunks <= 8) return launch_b<8>(x, perm, out, M, K, parts, stream);
-  return launch_b<kMaxChunks>(x, perm, out, M, K, parts, stream);
+  const int need = (groups + parts - 1) / parts;
+  for (int c : kColumnChunks)
+    if (f.chunks == 0 && need <= c) f.chunks = c;
+  f.parts = parts;
+  // rows per block: enough blocks to cover the chip several times, at least 2 rows each so the double buffer has something to hide
+  int rpb = 1;
+  while (rpb < 16 && (M + 2 * rpb - 1) / (2 * rpb) >= 4 * cus) rpb *= 2;
+  if (rpb == 1 && M >= 2) rpb = 2;
+  f.rows_per_block = rpb;
+  f.grid = (M + rpb - 1) / rpb;
+  f.lds = (size_t)K * 4;
+  return f;
+}
+
+int launch_gather_columns(const void *x, const int32_t *perm, void *out, int M, int K, hipStream_t stream) {
+  const GatherForm f = gather_form(M, K);
+  switch (f.rows * 10 + f.cpt) {  // (0: the row-at-a-time kernel)
+    case 81: return launch_rows<8, 1>(f, x, perm, out, M, K, stream);
+    case 41: return launch_rows<4, 1>(f, x, perm, out, M, K, stream);
+    case 21: return launch_rows<2, 1>(f, x, perm, out, M, K, stream);
+    case 42: return launch_rows<4, 2>(f, x, perm, out, M, K, stream);
+    case 22: return launch_rows<2, 2>(f, x, perm, out, M, K, stream);
+    case 23: return launch_rows<2, 3>(f, x, perm, out, M, K, stream);
+    case 24: return launch_rows<2, 4>(f, x, perm, out, M, K, stream);
+    default: break;
+  }
+  switch (f.chunks) {
+    case 1: return launch_b<1>(f, x, perm, out, M, K, stream);
+    case 2: return launch_b<2>(f, x, perm, out, M, K, stream);
+    case 4: return launch_b<4>(f, x, perm, out, M, K, stream);
+    case 6: return launch_b<6>(f, x, perm, out, M, K, stream);
+    case 8: return launch_b<8>(f, x, perm, out, M, K, stream);
+    case kMaxChunks: return launch_b<kMaxChunks>(f, x, perm, out, M, K, stream);
+    default: return set_error(QLLM_ERR_INVALID, "internal: no gather form for M=%d K=%d", M, K);
+  }
 }
 
 }  // namespace qllm

@@ -332,6 +332,15 @@ int launch_unpack_native(const qllm_weight_t &src, int dst_layout, void *qweight
 
 // ---- gather.hip (act-order: out[m, k] = x[m, perm[k]], 2-byte elements) ------------------------------------------------------
 bool gather_columns_ok(int K);
+// what a gather of M x K launches: gather_rows_kernel<rows, cpt> (rows > 0: `steps` steps of `rows` rows over `grid` blocks) or
+// gather_columns_kernel<chunks> (grid x parts blocks of rows_per_block rows).  ONE rule, asked by the launcher and qllm_gather_describe.
+struct GatherForm {
+  int rows, cpt, steps;               // the rows kernel (rows == 0: the columns kernel)
+  int chunks, parts, rows_per_block;  // the columns kernel
+  int grid;
+  size_t lds;
+};
+GatherForm gather_form(int M, int K);
 int launch_gather_columns(const void *x, const int32_t *perm, void *out, int M, int K, hipStream_t stream);
 
 // ---- gemm.hip ------------------------------------------------------------------------------------------------

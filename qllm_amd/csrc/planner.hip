@@ -47,6 +47,8 @@ static Settable kSettable[] = {
     // (no route: the two knobs of qllm_linear_forward_bitgemm, bitgemm.hip)
     {"QLLM_BITGEMM", 0, 1, 0, 0},              // 0: the 2..8-bit prefill entry refuses every call
     {"QLLM_BITGEMM_MIN_M", 129, 65536, 0, 0},  // read by callers that route by rows (the Python modules): the fewest rows they send to that entry
+    // (no route: qllm_gather_columns, gather.hip)
+    {"QLLM_GATHER_ROWS", 0, 1, 0, 0},          // 0: every row count on the row-at-a-time gather (no several-rows-per-step kernel from 64 rows)
 };
 int g_knob_overrides = 0;
 Settable *find_knob(const char *name) {

@@ -929,6 +929,12 @@ def gather_columns(x2d: torch.Tensor, perm: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def gather_describe(m: int, k: int) -> str:
+    """The launch `gather_columns` makes for an [m, k] matrix ("gather rows=2 cpt=4 grid=33 lds=57344", "gather columns chunks=4 parts=2
+    rows_per_block=2 grid=32x2 lds=44032"), or "unsupported (...)".  Pure host code: the rule the launcher executes."""
+    return _describe("qllm_gather_describe", 256, int(m), int(k))
+
+
 def unpack_qweight(qweight: torch.Tensor, layout: str, bits: int, in_features: int, out_features: int) -> torch.Tensor:
     _check_input(qweight, "qweight")
     q = torch.empty((in_features, out_features), dtype=torch.int32, device=qweight.device)
@@ -1171,6 +1177,6 @@ def unpack_native(w: QllmWeight, keep, layout: str):
     return qweight, scales, qzeros
 
 
-__all__ = ["make_weight", "linear_forward", "linear_forward_grouped", "linear_forward_permuted", "linear_forward_bitpanel", "bitpanel_describe", "linear_forward_bitgemm", "bitgemm_describe", "bitgemm_min_m", "linear_forward_bitgroup", "bitgroup_describe", "linear_forward_swiglu", "swiglu_describe", "linear_forward_residual", "linear_forward_swiglu_residual", "residual_describe", "rmsnorm", "linear_forward_rmsnorm", "rmsnorm_describe", "linear_forward_shared", "dequant", "gather_columns", "unpack_qweight", "pack_qweight",
+__all__ = ["make_weight", "linear_forward", "linear_forward_grouped", "linear_forward_permuted", "linear_forward_bitpanel", "bitpanel_describe", "linear_forward_bitgemm", "bitgemm_describe", "bitgemm_min_m", "linear_forward_bitgroup", "bitgroup_describe", "linear_forward_swiglu", "swiglu_describe", "linear_forward_residual", "linear_forward_swiglu_residual", "residual_describe", "rmsnorm", "linear_forward_rmsnorm", "rmsnorm_describe", "linear_forward_shared", "dequant", "gather_columns", "gather_describe", "unpack_qweight", "pack_qweight",
            "workspace", "QllmUnsupported", "LAYOUTS", "plan_describe", "repack_native", "unpack_native", "hqq_quantize", "gptq_quantize",
            "gptq_quantize_static", "awq_quantize", "awq_clip_search"]

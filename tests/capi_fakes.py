@@ -31,9 +31,11 @@ def describe(lib, entry, w, m, have_ws=1):
 # ---- one recorded call: entry name + a dict of plain arguments -> what it answered ------------------------------------------------------
 # args: "w" a list of descriptor field dicts (the arguments of W; None: a NULL pointer; single-layer entries take w[0]), "n" the layer
 # count passed (default len(w)), "ys" / "y", "x", "m", "dt", "have_ws", "buf" (False: NULL) and "buflen", and per entry "perm", "gate",
-# "up", "act", "norm_weight", "eps", "rstd".  Forward entries get no workspace and the null stream.
+# "up", "act", "norm_weight", "eps", "rstd", and for the two gather entries (which take no descriptor) "k" and "perm".  Forward entries get
+# no workspace and the null stream.
 FORWARD_ENTRIES = ("qllm_linear_forward", "qllm_linear_forward_grouped", "qllm_linear_forward_permuted", "qllm_linear_forward_bitpanel",
-                   "qllm_linear_forward_bitgemm", "qllm_linear_forward_bitgroup", "qllm_linear_forward_swiglu", "qllm_linear_forward_rmsnorm")
+                   "qllm_linear_forward_bitgemm", "qllm_linear_forward_bitgroup", "qllm_linear_forward_swiglu", "qllm_linear_forward_rmsnorm",
+                   "qllm_gather_columns")
 SIZE_ENTRIES = ("qllm_bitpanel_workspace_bytes", "qllm_bitgemm_workspace_bytes", "qllm_bitgroup_workspace_bytes")
 
 
@@ -73,6 +75,10 @@ def call_entry(lib, entry, args):
         rc = fn(one, m, buf, buflen)
     elif entry == "qllm_rmsnorm_describe":
         rc = fn(many, n, m, buf, buflen)
+    elif entry == "qllm_gather_describe":
+        rc = fn(m, a.get("k", 4096), buf, buflen)
+    elif entry == "qllm_gather_columns":
+        rc = fn(x, a.get("perm", PERM), y, m, a.get("k", 4096), dt, None)
     else:
         raise KeyError(entry)
     out = {"rc": rc}

@@ -55,9 +55,9 @@ def test_the_file_covers_every_entry():
     for name in ("bitpanel", "bitgemm", "bitgroup"):
         assert {f"qllm_linear_forward_{name}", f"qllm_{name}_workspace_bytes", f"qllm_{name}_describe"} <= entries, name
     assert {"qllm_linear_forward_grouped", "qllm_linear_forward_rmsnorm", "qllm_linear_forward_permuted", "qllm_plan_describe",
-            "qllm_rmsnorm_describe", "qllm_swiglu_describe"} <= entries
+            "qllm_rmsnorm_describe", "qllm_swiglu_describe", "qllm_gather_columns", "qllm_gather_describe"} <= entries
     for rec in json.load(open(GOLDEN)):   # a forward entry is in the file with refused arguments only
-        if rec["entry"] in ("qllm_linear_forward_grouped", "qllm_linear_forward_rmsnorm", "qllm_linear_forward_permuted") or rec["entry"].startswith("qllm_linear_forward_bit"):
+        if rec["entry"] in ("qllm_linear_forward_grouped", "qllm_linear_forward_rmsnorm", "qllm_linear_forward_permuted", "qllm_gather_columns") or rec["entry"].startswith("qllm_linear_forward_bit"):
             assert rec["got"]["rc"] in (_lib.QLLM_ERR_INVALID, _lib.QLLM_ERR_UNSUPPORTED, _lib.QLLM_ERR_WORKSPACE), rec
 
 

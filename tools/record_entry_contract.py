@@ -301,6 +301,21 @@ for args in (dict(w=None), dict(w=[NATIVE4], buf=False), dict(w=[NATIVE4], bufle
     case(SWIGLU_DESC, **args)
 case(SWIGLU_DESC, {"QLLM_STRIP1": 0}, w=[NATIVE4])
 
+# ---- the column gather: what the entry refuses, and every form its rule can answer ----------------------------------------------------------
+GATHER, GATHER_DESC = "qllm_gather_columns", "qllm_gather_describe"
+for args in (dict(x=None), dict(perm=None), dict(y=None), dict(m=-1), dict(k=0), dict(dt=7), dict(x=F.X + 8), dict(perm=F.PERM + 8), dict(y=F.Y + 8),
+             dict(y=F.X), dict(k=12), dict(k=28680), dict(k=4), dict(m=-1, x=None), dict(m=-1, dt=7), dict(k=12, dt=7), dict(k=12, y=F.X),
+             dict(k=12, m=0), dict(k=12, x=F.X + 8)):
+    case(GATHER, **args)
+for args in (dict(buf=False), dict(buflen=0), dict(m=-1), dict(k=0), dict(k=-8), dict(m=-1, buf=False), dict(k=12), dict(k=28680), dict(k=12, m=-1),
+             dict(m=0), dict(m=0, k=12)):
+    case(GATHER_DESC, **args)
+for k in (8, 264, 4096, 4104, 8192, 8200, 12288, 12296, 16384, 16392, 24576, 28672):
+    for m in (1, 2, 3, 15, 31, 63, 64, 65, 300, 1027, 2047, 2048, 2050, 4095, 4099, 16390):
+        case(GATHER_DESC, m=m, k=k)
+        if m >= 64:
+            case(GATHER_DESC, {"QLLM_GATHER_ROWS": 0}, m=m, k=k)
+
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
