@@ -529,8 +529,8 @@ int qllm_rope(const void *q, const void *k, const void *cos, const void *sin, vo
  * a host kv_len outside 0..max_len (kv_len + 1 > max_len with an append), a mask too short.  QLLM_ERR_UNSUPPORTED: head_dim other than
  * 64 / 128, more than 8 query heads per kv head, batch * kv_heads > 4096.  QLLM_ERR_WORKSPACE: a missing, misaligned or small
  * workspace.  Every error is raised before any device work.  No host synchronisation; hipGraph-capturable.
- * Not built: a ring-buffer cache, chunked attention, quantized and paged caches, per-sequence lengths other than through the mask, rotary
- * inside the kernel, an fp8 cache.  More than one query token: qllm_attn_prefill below.
+ * Not built: chunked attention, quantized and paged caches, per-sequence lengths other than through the mask, rotary
+ * inside the kernel, an fp8 cache.  A ring-buffer cache: qllm_attn_decode_ring below.  More than one query token: qllm_attn_prefill below.
  * ABI: the symbols are ADDITIVE within ABI 7 (QLLM_ABI_VERSION is unchanged): probe for them by symbol. */
 #define QLLM_ATTN_MASK_NONE 0
 #define QLLM_ATTN_MASK_BOOL 1
@@ -553,6 +553,28 @@ int qllm_attn_decode_window(const void *q, const void *k_new, const void *v_new,
                             int64_t v_new_head_stride, int64_t cache_batch_stride, int64_t cache_head_stride, int64_t cache_pos_stride, int32_t mask_kind,
                             int64_t mask_len, int64_t mask_batch_stride, float scaling, int32_t act_dtype, void *workspace, size_t workspace_bytes,
                             void *stream);
+/* qllm_attn_decode over a RING-BUFFER cache (csrc/attn_decode_ring.hip): what a sliding-window layer needs past its window without moving
+ * a row.  The caches hold `slots` = C positions per (batch entry, kv head) and position j lives in slot j mod C; 1 <= window = W <= C.
+ * total: the tokens counted before the call, or with total_dev != NULL the int64 the kernel reads there; clamped below at 0 and NOT above:
+ * it grows for as long as the generation runs (64-bit throughout).  With k_new / v_new the call appends, n = total + 1, and the kernel
+ * stores the two rows into slot (n - 1) mod C; without, n = total.  The query sits at n - 1 and sees positions lo = max(0, n - W) ..
+ * n - 1, v = n - lo <= W of them; no other slot is ever loaded.  C >= W makes the append race-free: the slot it overwrites held position
+ * n - 1 - C < lo.  Mask: as qllm_attn_decode's, but column r is position lo + r (the mask transformers builds for a sliding layer); it
+ * must cover min(n, W) columns, W with the total on the device.  Launch shape, workspace and describe text are those of a linear call
+ * whose max_len is W: qllm_attn_decode_workspace_bytes(.., W) and qllm_attn_decode_describe(.., W); split s owns r = j - lo in s * chunk
+ * .. (s + 1) * chunk - 1.  The grid never depends on the total: one captured launch serves every length, on both sides of the fill.
+ * The result is, bit for bit, qllm_attn_decode's on a linear copy [batch, kv_heads, W, head_dim] holding positions lo .. n - 1 in
+ * slots 0 .. v - 1 with kv_len = v (v - 1 and the same append) and the same mask.
+ * Errors as qllm_attn_decode's, in its order, with slots for max_len; window < 1 or slots < window and a host total < 0 are
+ * QLLM_ERR_INVALID.  Every error is raised before any device work.  No host synchronisation; hipGraph-capturable.
+ * Not built: prefill written into the ring by a kernel (qllm_attn_prefill reads linear caches), a ring for full-attention layers.
+ * ADDITIVE within ABI 7: probe for it by symbol. */
+int qllm_attn_decode_ring(const void *q, const void *k_new, const void *v_new, void *k_cache, void *v_cache, const void *mask, void *out, int32_t batch,
+                          int32_t q_heads, int32_t kv_heads, int32_t head_dim, int64_t total, const int64_t *total_dev, int64_t slots, int64_t window,
+                          int64_t q_row_stride, int64_t q_head_stride, int64_t k_new_row_stride, int64_t k_new_head_stride, int64_t v_new_row_stride,
+                          int64_t v_new_head_stride, int64_t cache_batch_stride, int64_t cache_head_stride, int64_t cache_pos_stride, int32_t mask_kind,
+                          int64_t mask_len, int64_t mask_batch_stride, float scaling, int32_t act_dtype, void *workspace, size_t workspace_bytes,
+                          void *stream);
 /* The workspace qllm_attn_decode needs: the counter page and the splits' partial results.  Pure host code; shapes the entry refuses need
  * the page alone. */
 size_t qllm_attn_decode_workspace_bytes(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int64_t max_len);

@@ -8,6 +8,15 @@ from . import _lib  # noqa: F401
 
 __version__ = "0.1.0"
 
+_RING = ("RingSlidingWindowLayer", "ring_static_cache", "to_ring")   # modeling/ring_cache.py, imported on first use (it imports transformers)
+
+
+def __getattr__(name: str):
+    if name in _RING:
+        from .modeling import ring_cache
+        return getattr(ring_cache, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
 
 def is_available() -> bool:
     """True iff the HIP library is built and device 0 is gfx950."""

@@ -119,6 +119,8 @@ SIGNATURES = {
                                           i64, i64, C.c_float, i32, vp, sz, vp]),
     "qllm_attn_prefill_window": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i64, vp, i64, i64, i64, i64, i64, i64, i64, i64, i32, i64, i64, i64,
                                            i32, C.c_float, i32, vp]),
+    "qllm_attn_decode_ring": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i64, vp, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, i32,
+                                        i64, i64, C.c_float, i32, vp, sz, vp]),
 }
 EXPORTS = tuple(SIGNATURES)
 

@@ -36,7 +36,7 @@
 // a bf16 bias that is finite, above the lowest finite number and below about -7e29 has exp2(s - kNoMax) = 0: a row whose visible keys ALL
 // carry such a bias stores zeros instead of a softmax among them (fp16 has no such value; transformers masks with finfo.min).
 //
-// Not built: a ring-buffer cache (position j lives in slot j), chunked attention, quantized caches, paged caches, per-sequence lengths
+// Here position j lives in slot j; a ring-buffer cache (position j in slot j mod C) is attn_decode_ring.hip's.  Not built: chunked attention, quantized caches, paged caches, per-sequence lengths
 // other than through the mask, head_dim other than 64 / 128, rotary inside the kernel, an fp8 cache, P.V on MFMA.  More than one query
 // token: attn_prefill.hip.
 #include "attn_decode_kernel.hpp"

@@ -1176,6 +1176,50 @@ int qllm_attn_decode_window(const void *q, const void *k_new, const void *v_new,
   return launch_attn_decode(p, head_dim, act_dtype == QLLM_BF16, (hipStream_t)stream);
 }
 
+// the same call over a ring-buffer cache of `slots` positions (attn_decode_ring.hip): the decode entry's rules in its order, with `slots`
+// where it has max_len in the shape, the ring's two rules (1 <= window <= slots; a total with no upper end) in the places of the window's
+// sign and of the length's range, and the geometry, the workspace and the mask's reach of a linear call whose max_len is the window
+int qllm_attn_decode_ring(const void *q, const void *k_new, const void *v_new, void *k_cache, void *v_cache, const void *mask, void *out, int32_t batch,
+                          int32_t q_heads, int32_t kv_heads, int32_t head_dim, int64_t total, const int64_t *total_dev, int64_t slots, int64_t window,
+                          int64_t q_row_stride, int64_t q_head_stride, int64_t k_new_row_stride, int64_t k_new_head_stride, int64_t v_new_row_stride,
+                          int64_t v_new_head_stride, int64_t cache_batch_stride, int64_t cache_head_stride, int64_t cache_pos_stride, int32_t mask_kind,
+                          int64_t mask_len, int64_t mask_batch_stride, float scaling, int32_t act_dtype, void *workspace, size_t workspace_bytes,
+                          void *stream) {
+  clear_error();
+  int rc = check_attn_call(q, k_cache, v_cache, out, batch, q_heads, kv_heads, head_dim, nullptr, slots, window, act_dtype, mask_kind, mask);
+  if (rc != QLLM_OK) return rc;
+  if (window < 1 || slots < window)
+    return set_error(QLLM_ERR_INVALID, "a ring needs 1 <= window <= slots (got window=%lld slots=%lld)", (long long)window, (long long)slots);
+  if ((k_new == nullptr) != (v_new == nullptr)) return set_error(QLLM_ERR_INVALID, "k_new and v_new must be given together or not at all");
+  const int64_t strides[9] = {q_row_stride, q_head_stride, cache_batch_stride, cache_head_stride, cache_pos_stride,
+                              k_new_row_stride, k_new_head_stride, v_new_row_stride, v_new_head_stride};  // the last four count with an append only
+  const void *const ptrs[6] = {q, k_new, v_new, k_cache, v_cache, out};
+  rc = check_attn_layout("q / k_new / v_new / k_cache / v_cache / out", ptrs, 6, total_dev, mask_kind, mask, "row, head, batch and position", strides,
+                         k_new ? 9 : 5);
+  if (rc != QLLM_OK) return rc;
+  if (!total_dev && total < 0) return set_error(QLLM_ERR_INVALID, "total must be >= 0 (got %lld); it has no upper end", (long long)total);
+  // the columns a call may reach: the visible positions, at most the window's
+  const int64_t need_len = total_dev || total >= window ? window : total + (k_new ? 1 : 0);
+  if (mask && (mask_len < need_len || mask_batch_stride < 0))
+    return set_error(QLLM_ERR_INVALID, "the mask must cover %lld positions (%s) with a non-negative batch stride (got mask_len=%lld stride=%lld)", (long long)need_len,
+                     total_dev ? "the window: the total is on the device" : "min(total, + 1 with an append; window)", (long long)mask_len,
+                     (long long)mask_batch_stride);
+  rc = check_attn_decode_served(batch, q_heads, kv_heads, head_dim);
+  if (rc != QLLM_OK) return rc;
+  const AttnDecodeGeom g = attn_decode_geom(batch, q_heads, kv_heads, head_dim, window);
+  rc = check_workspace("qllm_attn_decode_ring", workspace, workspace_bytes, kCounterBytes + g.partial_bytes);
+  if (rc != QLLM_OK) return rc;
+
+  AttnDecodeParams p;
+  p.q = q, p.k_new = k_new, p.v_new = v_new, p.k_cache = k_cache, p.v_cache = v_cache, p.mask = mask, p.out = out;
+  p.kv_len_dev = total_dev, p.kv_len = total, p.max_len = slots, p.window = window;
+  p.q_row = q_row_stride, p.q_head = q_head_stride, p.kn_row = k_new_row_stride, p.kn_head = k_new_head_stride, p.vn_row = v_new_row_stride,
+  p.vn_head = v_new_head_stride, p.c_batch = cache_batch_stride, p.c_head = cache_head_stride, p.c_pos = cache_pos_stride, p.mask_batch = mask_batch_stride;
+  p.chunk = g.chunk, p.batch = batch, p.q_heads = q_heads, p.kv_heads = kv_heads, p.mask_kind = mask_kind, p.splits = g.splits, p.scaling = scaling;
+  carve(workspace, &p.counters, &p.partials);
+  return launch_attn_decode_ring(p, head_dim, act_dtype == QLLM_BF16, (hipStream_t)stream);
+}
+
 // ---- prefill attention over the KV cache (attn_prefill.hip) ------------------------------------------------------------------------------
 // what the kernel serves, and a grid of (row tiles, q_heads, batch)
 static int check_attn_prefill_served(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim) {

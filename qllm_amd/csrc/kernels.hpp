@@ -308,6 +308,9 @@ struct AttnDecodeGeom {
 AttnDecodeGeom attn_decode_geom(int batch, int q_heads, int kv_heads, int head_dim, int64_t max_len);
 int launch_attn_decode(const AttnDecodeParams &p, int head_dim, int act_bf16, hipStream_t stream);
 int launch_attn_decode_window(const AttnDecodeParams &p, int head_dim, int act_bf16, hipStream_t stream);  // p.window >= 1 (attn_decode_window.hip)
+// attn_decode_ring.hip: position j lives in slot j mod p.max_len; p.kv_len(_dev) is the unbounded total, 1 <= p.window <= p.max_len, and
+// p.chunk / p.splits / p.partials are attn_decode_geom's for max_len = p.window
+int launch_attn_decode_ring(const AttnDecodeParams &p, int head_dim, int act_bf16, hipStream_t stream);
 
 // ---- attn_prefill.hip: q_len >= 2 query rows per sequence against the first kv_len positions of a KV cache (flash attention forward) -----
 constexpr int kAttnPrefillQTile = 128;  // query rows per block: 32 per wave

@@ -11,7 +11,7 @@ q / k / v are device tensors of one fp16 / bf16 type, nothing is being different
 implementation is sdpa or eager, no kwarg changes the mathematics (a `sliding_window` handed in by the caller does), the mask is None or
 one of the two forms transformers builds at q_len == 1 ([B, 1, 1, L] bool or additive), the cache layer is EXACTLY a DynamicLayer or an
 initialised StaticLayer of a cache that does not offload -- with a sliding window W (config.sliding_window for Mistral, the module's own
-for Qwen2) EXACTLY one of the two sliding layers below -- and `ops.attn_decode_plan` serves the shapes:
+for Qwen2) EXACTLY one of the three sliding layers below -- and `ops.attn_decode_plan` serves the shapes:
 
   DynamicLayer  `update` as before, then the kernel over what it returned with the host length.
   StaticLayer   `update` as before, then the kernel over the layer's buffers with the length read from `layer.cumulative_length` on the
@@ -26,8 +26,14 @@ for Qwen2) EXACTLY one of the two sliding layers below -- and `ops.attn_decode_p
                 layer.max_cache_len`; once the layer has overflowed it stops updating that tensor (a 5-token prompt into a window of 4
                 leaves it at 0), and everything `update` returns is valid: the host length.  The layer branches on a Python int at the
                 point where it fills (index_copy before, roll or cat after), fused or not, so a manually captured step cannot cross that
-                point: capture before it or after it.  Past it the layer rolls its whole buffer at every token; a ring-buffer layer of
-                our own would remove that and is not built, nor are chunked attention and `record_past`.
+                point: capture before it or after it.  Past it the layer rolls its whole buffer at every token.  Chunked attention
+                and `record_past` are not built.
+  RingSlidingWindowLayer      (modeling/ring_cache.py; the caller builds the cache: `ring_static_cache` / `to_ring`) that holds at most W
+                positions, position j in slot j mod C: at decode NO `update` -- `ops.attn_decode_ring` over the layer's buffers in
+                place with the total from `layer.cumulative_length` on the device and the new rows stored by the kernel, then
+                `layer.advance(1)`: no roll, no copy of the cache, no branch on whether the layer is full, so ONE captured step serves
+                every length.  Where its plan refuses, `update` (which returns what the static sliding layer's returns) and the
+                family's route.  At prefill it is a static sliding layer: `update`, then the same call of `ops.attn_prefill`.
 On the full layers the calls carry no `window`.  On the sliding ones a decode call carries it, but it hides nothing there: a dynamic
 sliding layer returns at most W positions and a static one holds at most W, so the lowest visible position is 0 and the windowed kernel
 reads what the kernel without a window would.  The decode window skips keys only for direct callers of `ops.attn_decode` on a linear
@@ -68,8 +74,10 @@ def _layer_of(past_key_values, layer_idx, uninitialized=False, sliding=None):
     ("dynamic") or an initialised StaticLayer ("static"; with `uninitialized`: any StaticLayer).  With the window W of the call: exactly a
     DynamicSlidingWindowLayer of that window that does not record its past ("dynamic_sliding"), or exactly a StaticSlidingWindowLayer
     (initialised, or any with `uninitialized`) that holds at most W positions ("static_sliding"), unless QLLM_FUSE_ATTENTION_SLIDING=0.
+    Exactly a RingSlidingWindowLayer (modeling/ring_cache.py) under the static sliding layer's conditions: "ring_sliding".
     Always of a cache that does not offload; a window on a full layer, a sliding layer without one and subclasses are not served."""
     from transformers.cache_utils import DynamicLayer, DynamicSlidingWindowLayer, StaticLayer, StaticSlidingWindowLayer
+    from ..ring_cache import RingSlidingWindowLayer
     layers = getattr(past_key_values, "layers", None)
     if not isinstance(layers, list) or not isinstance(layer_idx, int) or not 0 <= layer_idx < len(layers) or getattr(past_key_values, "offloading", False):
         return None, None
@@ -86,6 +94,8 @@ def _layer_of(past_key_values, layer_idx, uninitialized=False, sliding=None):
         return layer, "dynamic_sliding"
     if type(layer) is StaticSlidingWindowLayer and layer.max_cache_len <= sliding and (layer.is_initialized or uninitialized):
         return layer, "static_sliding"
+    if type(layer) is RingSlidingWindowLayer and layer.max_cache_len <= sliding and (layer.is_initialized or uninitialized):
+        return layer, "ring_sliding"
     return None, None
 
 
@@ -93,7 +103,7 @@ def _length_after_update(layer, kind, keys):
     """The number of valid positions of what `update` returned.  A static layer: its device counter.  A static sliding layer: its device
     counter while the layer has not overflowed (it stops updating the tensor from then on: the tensor is wrong and must not be used), then
     the length of what `update` returned -- all of it is valid.  A dynamic layer of either kind: the length of what `update` returned."""
-    if kind == "static" or (kind == "static_sliding" and layer.cumulative_length_int <= layer.max_cache_len):
+    if kind == "static" or (kind in ("static_sliding", "ring_sliding") and layer.cumulative_length_int <= layer.max_cache_len):
         return layer.cumulative_length
     return keys.shape[2]
 
@@ -118,7 +128,7 @@ def _gate(self, q, k, v, attention_mask, past_key_values, kwargs, window, rows, 
     layer, kind = _layer_of(past_key_values, self.layer_idx, uninitialized=uninitialized, sliding=sliding)
     if layer is None:
         return None
-    if kind.startswith("static") and layer.is_initialized and (layer.keys.dtype != q.dtype or layer.keys.shape[0] != q.shape[0] or layer.keys.shape[3] != q.shape[3]):
+    if kind in ("static", "static_sliding", "ring_sliding") and layer.is_initialized and (layer.keys.dtype != q.dtype or layer.keys.shape[0] != q.shape[0] or layer.keys.shape[3] != q.shape[3]):
         return None
     return layer, kind, sliding
 
@@ -147,7 +157,26 @@ def _fused_core(self, q, k, v, attention_mask, past_key_values, kwargs, window):
     served = _gate(self, q, k, v, attention_mask, past_key_values, kwargs, window, 1) if q.shape[2] == 1 else None
     if served is None:
         return None, k, v, False
+    if served[1] == "ring_sliding":
+        return _attend_ring(self, q, k, v, attention_mask, past_key_values, served[0])
     return _update_and_attend(self, q, k, v, attention_mask, past_key_values, *served)
+
+
+def _attend_ring(self, q, k, v, attention_mask, past_key_values, layer):
+    """One token on a ring layer: ops.attn_decode_ring over the layer's buffers in place -- the total from `layer.cumulative_length` on the
+    device, the new rows stored by the kernel -- then `layer.advance(1)`: no launch touches more than the new rows, and nothing branches
+    on whether the layer is full.  The window of the call is the layer's size (min(W, max_cache_len): what a static sliding layer of
+    these sizes holds and shows).  Where the plan refuses nothing has touched the cache: `update`, once, and the family's route."""
+    try:
+        plan = ops.attn_decode_ring_plan(q, layer.keys, layer.values, layer.cumulative_length, layer.max_cache_len, k, v, attention_mask)
+    except ops.QllmUnsupported:
+        keys, values = past_key_values.update(k, v, self.layer_idx)
+        return None, keys, values, True
+    with torch.no_grad():
+        out = ops.attn_decode_ring(q, layer.keys, layer.values, layer.cumulative_length, layer.max_cache_len, k_new=k, v_new=v, mask=attention_mask,
+                                   scaling=self.scaling, plan=plan)
+    layer.advance(1)
+    return out, layer.keys, layer.values, True
 
 
 # What `_fused_core_prefill` hands to ops.attn_prefill, by (cache layer kind, whether the call carries a mask): the q_len range (lowest,
@@ -197,7 +226,7 @@ def _rows(bound, window):
 def _prefill_routed(kind: str, masked: bool, q_len: int, behind: bool, window: Optional[int] = None) -> bool:
     """`behind`: the host knows that the layer held tokens before this call (a dynamic layer's length and a static sliding layer's
     Python counter; a static layer's length is on the device).  `window`: the call's sliding window, for the bounds written in windows."""
-    entry = PREFILL_ROUTES.get((kind, masked), (1, 0, False))
+    entry = PREFILL_ROUTES.get(("static_sliding" if kind == "ring_sliding" else kind, masked), (1, 0, False))
     ranges = entry if isinstance(entry[0], tuple) else (entry,)
     return any(q_len >= _rows(lo, window) and (hi is None or q_len <= _rows(hi, window)) and (chunks or not behind) for lo, hi, chunks in ranges)
 
@@ -219,9 +248,9 @@ def _fused_core_prefill(self, q, k, v, attention_mask, past_key_values, kwargs, 
     if served is None:
         return no
     layer, kind, sliding = served
-    static = kind.startswith("static")
+    static = kind in ("static", "static_sliding", "ring_sliding")
     held = layer.is_initialized if static else layer.get_seq_length() != 0   # (a static layer: may hold tokens; its length is on the device)
-    behind = layer.is_initialized and layer.cumulative_length_int != 0 if kind == "static_sliding" else held and not static
+    behind = layer.is_initialized and layer.cumulative_length_int != 0 if kind in ("static_sliding", "ring_sliding") else held and not static
     if not _prefill_routed(kind, attention_mask is not None, s, behind, sliding) or (attention_mask is None and held):
         return no
     return _update_and_attend(self, q, k, v, attention_mask, past_key_values, layer, kind, sliding)

@@ -773,6 +773,74 @@ def attn_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, l
     return out
 
 
+def attn_decode_ring_plan(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, total, window, k_new: Optional[torch.Tensor] = None,
+                          v_new: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None):
+    """What `attn_decode_ring` hands to qllm_attn_decode_ring for these tensors -- (batch, q_heads, kv_heads, head_dim, slots, window, q row /
+    head stride, k_new row / head stride, v_new row / head stride, cache batch / head / position stride, mask_kind, mask_len, mask batch
+    stride) -- or QllmUnsupported with the reason.  Tensors as `attn_decode_plan` takes them, the caches [B, Hkv, C, D] with C slots;
+    `window` an int W with 1 <= W <= C; `total` an int >= 0 with no upper end (the mask covers min(total, + 1 with an append; W) columns)
+    or a 0-d int64 tensor on the device (the mask then covers W).  Pure host code, any device."""
+    no = _attn_refusal("attn_decode_ring")
+    if (k_new is None) != (v_new is None):
+        raise no("k_new and v_new must be given together or not at all")
+    _attn_one_type_and_device(no, "q, the caches and k_new / v_new", (q, k_cache, v_cache) + ((k_new, v_new) if k_new is not None else ()), mask)
+    b, hq, d, q_row, q_head = _attn_heads(q, "q")
+    hkv, slots = _attn_cache_shape(no, k_cache, v_cache, b, d)
+    if isinstance(window, bool) or not isinstance(window, int) or window < 1 or window > slots:
+        raise no(f"window must be an int in 1..{slots}, the caches' slots (got {window!r})")
+    _attn_served_heads(no, hq, hkv, d)
+    if b * hkv > ATTN_DECODE_COUNTERS or b > 65535:
+        raise no(f"batch * kv_heads <= {ATTN_DECODE_COUNTERS} (got {b * hkv})")
+    cs = _attn_cache_strides(no, k_cache, v_cache)
+    new = (0, 0, 0, 0)
+    if k_new is not None:
+        kb, kh, kd, k_row, k_head = _attn_heads(k_new, "k_new")
+        vb, vh, vd, v_row, v_head = _attn_heads(v_new, "v_new")
+        if (kb, kh, kd) != (b, hkv, d) or (vb, vh, vd) != (b, hkv, d):
+            raise no(f"k_new and v_new must be one token of [{b}, {hkv}, {d}] (got {tuple(k_new.shape)}, {tuple(v_new.shape)})")
+        new = (k_row, k_head, v_row, v_head)
+    need = window
+    if not _attn_length_on_device(no, total, q):
+        total = int(total)
+        if total < 0:
+            raise no(f"the total must be >= 0 (got {total})")
+        need = min(total + (1 if k_new is not None else 0), window)
+    kind, mask_len, mask_batch = _lib.ATTN_MASK_NONE, 0, 0
+    if mask is not None:
+        m2 = mask[:, 0, 0] if mask.dim() == 4 and mask.shape[1] == 1 and mask.shape[2] == 1 else mask
+        if m2.dim() != 2 or m2.shape[0] not in (1, b) or (m2.shape[1] > 1 and m2.stride(1) != 1):
+            raise no(f"the mask must be [B, 1, 1, L] or [B, L] with B = {b} or 1 and inner stride 1 (got {tuple(mask.shape)}, strides {tuple(mask.stride())})")
+        mask_len, mask_batch = m2.shape[1], (m2.stride(0) if m2.shape[0] > 1 else 0)
+        kind = _attn_mask_kind(no, mask, q, mask_len, need, mask_batch)
+    return (b, hq, hkv, d, slots, window, q_row, q_head) + new + cs + (kind, mask_len, mask_batch)
+
+
+def attn_decode_ring(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, total, window, k_new: Optional[torch.Tensor] = None,
+                     v_new: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, scaling: Optional[float] = None, *, out=None, plan=None):
+    """`attn_decode` over a RING-BUFFER cache [B, Hkv, C, D] in which position j lives in slot j mod C, as ONE kernel
+    (qllm_attn_decode_ring, csrc/attn_decode_ring.hip): what a sliding-window layer needs past its window without moving a row.  `total`:
+    the tokens counted before the call, an int or a 0-d int64 tensor on the device that the kernel reads; it has no upper end.  With
+    k_new / v_new the call appends: n = total + 1 and the kernel stores the rows in slot (n - 1) mod C; without, n = total.  The query
+    sits at n - 1 and sees positions lo = max(0, n - W) .. n - 1 (`window` = W, 1 <= W <= C); no other slot is loaded.  mask: as
+    `attn_decode`'s, with column r standing for position lo + r (the mask transformers builds for a sliding layer).  Returns [B, Hq, D]:
+    bit for bit what `attn_decode` gives on a linear copy [B, Hkv, W, D] of the visible positions.  The launch is that of
+    `attn_decode_describe(B, Hq, Hkv, D, W)` and never depends on the total: one captured call serves every length.
+    `attn_decode_ring_plan` says what is served; everything else raises QllmUnsupported before anything is launched."""
+    if plan is None:
+        plan = attn_decode_ring_plan(q, k_cache, v_cache, total, window, k_new, v_new, mask)
+    b, hq, hkv, d, slots, window = plan[:6]
+    out, total, total_dev, scaling = _attn_call("attn_decode_ring", q, k_cache, v_cache, total, scaling, out, (b, hq, d), d)
+    lib = _lib.load()
+    with torch.cuda.device(q.device):
+        nbytes = lib.qllm_attn_decode_workspace_bytes(b, hq, hkv, d, window)
+        ws = workspace(q.device, nbytes)
+        rc = lib.qllm_attn_decode_ring(q.data_ptr(), _ptr(k_new), _ptr(v_new), k_cache.data_ptr(), v_cache.data_ptr(), _ptr(mask), out.data_ptr(),
+                                       b, hq, hkv, d, total, total_dev, slots, window, *plan[6:], scaling, _act_dtype(q), ws.data_ptr(), ws.numel(),
+                                       _stream_ptr())
+    _lib.check(rc)
+    return out
+
+
 def attn_prefill_plan(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, length, mask: Optional[torch.Tensor] = None):
     """What `attn_prefill` hands to qllm_attn_prefill for these tensors -- (batch, q_heads, kv_heads, head_dim, q_len, max_len, q batch /
     head / row stride, cache batch / head / position stride, mask_kind, mask_len, mask batch / row stride) -- or QllmUnsupported with the

@@ -27,6 +27,9 @@ per row.
                      index put and copy_ of the whole buffer at every token), then sdpa over all W positions behind the bool mask  |  the same update, then
                      ops.attn_decode(window=W) with the length the modules hand over; past the window also the update ALONE, which
                      both versions pay.
+            ring     that fused static step (update included)  |  a RingSlidingWindowLayer of the same W: ops.attn_decode_ring over the
+                     layer's buffers with the total read from the device and the append in the kernel, then the add_ that bumps the
+                     total: no update, no roll.  Its output is held, bit for bit, against ops.attn_decode on the linearised positions.
 
   python tools/attn_decode_bench.py [--links 16] [--seconds 0.4] [--repeats 3] [--window W]"""
 import argparse
@@ -99,6 +102,7 @@ def sliding_points(args, gen):
     from transformers.cache_utils import StaticSlidingWindowLayer
     from transformers.integrations.sdpa_attention import sdpa_attention_forward
     from qllm_amd.modeling.q_layers.fused_attention import _length_after_update
+    from qllm_amd.modeling.ring_cache import RingSlidingWindowLayer
     n, w = args.links, args.window
     for hq, hk, d in ((32, 8, 128), (32, 32, 128)):
         print(ops.attn_decode_describe(1, hq, hk, d, w), flush=True)
@@ -188,7 +192,37 @@ def sliding_points(args, gen):
                 print(f"{tag:14s} the layer's update alone (roll, index put, copy_): {mu:.2f} us = {100 * mu / mb:.1f} % of the kernel step", flush=True)
                 print("JSON " + json.dumps(rec), flush=True)
                 del g_u
-            del g_a, g_b, y_a, y_b, la, lb
+            # ring: RingSlidingWindowLayers holding the same positions in slot j mod W; the step is ONE ops.attn_decode_ring (the total
+            # from the device, the append in the kernel) and the add_ that bumps the total -- what the modules run on a ring cache --
+            # against the fused static step above (update included in both)
+            lens_r = torch.zeros(n, dtype=torch.int64, device=DEV)
+            lr = []
+            for i, x in enumerate(lb):
+                layer = RingSlidingWindowLayer(max_cache_len=w, sliding_window=w)
+                layer.lazy_initialization(torch.empty(1, hk, 1, d, device=DEV, dtype=torch.float16), torch.empty(1, hk, 1, d, device=DEV, dtype=torch.float16))
+                layer.cumulative_length = lens_r[i]
+                layer.keys.copy_(x.keys), layer.values.copy_(x.values)
+                lr.append(layer)
+
+            def ring_kernel():
+                lens_r.fill_(cached)
+                outs = []
+                for q, layer, kn, vn in zip(qs, lr, kns, vns):
+                    outs.append(ops.attn_decode_ring(q, layer.keys, layer.values, layer.cumulative_length, w, k_new=kn, v_new=vn, mask=mask, scaling=d ** -0.5))
+                    layer.cumulative_length.add_(1)
+                return outs
+
+            g_r, y_r = capture(ring_kernel)
+            assert lens_r.tolist() == [cached + 1] * n
+            lo = max(0, cached + 1 - w)
+            idx = torch.arange(lo, lo + w, device=DEV) % w                                    # the linearised copy: W positions from lo on, cached + 1 - lo of them valid
+            want = [ops.attn_decode(q, layer.keys.index_select(2, idx), layer.values.index_select(2, idx), cached + 1 - lo, mask=mask, scaling=d ** -0.5)
+                    for q, layer in zip(qs, lr)]                                             # the linear call of max_len = W: the very bits
+            assert all(torch.equal(a, b) for a, b in zip(y_r, want)), tag
+            max_diff(tag + " ring (against the linearised call)", y_r, want)
+            a, b = ab(g_b, g_r, n, args.seconds, args.repeats)
+            row(tag, "ring", "static", "ring", a, b)
+            del g_a, g_b, g_r, y_a, y_b, y_r, la, lb, lr
             torch.cuda.empty_cache()
 
 
