@@ -120,6 +120,8 @@ int qllm_is_lab_build(void);
 /* Planner thresholds (ABI 6).  The kernel-selection tree was measured on Llama-2-7B / 70B shapes (profiles/r06_shape_table.md has other
  * families); a deployment may move these thresholds without rebuilding.  Process-global, not synchronised with forward calls running on
  * other threads: set them before serving.  Settable names (values outside the range every built kernel covers are refused):
+ *   QLLM_STRIP1_PRELOAD 0|1 (batch 1, 4 bits, 128-wide groups: 1 the kernels whose leading arguments are preloaded into SGPRs, 0 the kernels that read
+ *   every word from the kernel-argument segment; same results bit for bit; qllm_plan_describe names a choice off the default as args=...),
  *   QLLM_STRIP1 0|1|2, QLLM_STRIP1_MAX_M 1..4, QLLM_STRIP1_3BIT 0|1, QLLM_PANEL 0|1, QLLM_PANEL_MIN_M 17..129, QLLM_PANEL_GROUP_MIN_M 17..129, QLLM_GEMM2 0|1, QLLM_GEMM3 0|1,
  *   QLLM_GEMM2_MIN_M >= 33, QLLM_GEMM3_MIN_M >= 0 (0: the measured 384 / 768 line), QLLM_GEMM2_SPLITK 0|1, QLLM_GEMM3_TAIL 0|1, QLLM_GEMM3_BF16 0|1, QLLM_GEMM3_GROUP 0|1,
  *   QLLM_SKINNY_MAX_M 0..64, QLLM_STRIP_MIN >= 0, QLLM_S1_T256_NW16 0|1 (batch 1, K = 6272..8192: 16 waves x 16 k-steps instead of 8 x 32), QLLM_BITGEMV 0|1, QLLM_BITPANEL 0|1, QLLM_BITPANEL_LDS 0|1, QLLM_BITPANEL_MAX_M 17..512 (the last three: qllm_linear_forward_bitpanel, no route),
@@ -180,7 +182,8 @@ int qllm_linear_forward_grouped(const qllm_weight_t *w, void *const *y, int32_t 
 /* Diagnostics (process-global, not thread-safe; NULL switches it off): the next native-layout decode launches (4 bits, g128: the
  * batch-1 "lds-slab" form and the batch 2..32 "dma-A" form) each take one 192-byte slot of `buf` (device memory, n_slots x 24 x
  * u64, in launch order) and record 100 MHz device timestamps of wave 0 of their first, middle and last block: [entry, loads issued
- * (dma-A: ring requested), x staged (dma-A: first stage landed), rounds done, after the block barrier, exit, -, -] x 3.  A launch
+ * (dma-A: ring requested), x staged (dma-A: first stage landed), rounds done, after the block barrier, exit, w, -] x 3 (the batch-1 kernel: entry is read in front of its first scalar load, and w is
+ * 1 where the kernel whose leading arguments are preloaded, QLLM_STRIP1_PRELOAD, wrote the slot, else 0).  A launch
  * captured into a hipGraph keeps its slot.  tools/lab/cbench.cpp --timeline [--m 16]. */
 int qllm_debug_timeline(void *buf, int32_t n_slots);
 

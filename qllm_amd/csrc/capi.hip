@@ -201,6 +201,7 @@ static int run_strip1(const StripPlan &pl, const qllm_weight_t *w, void *const *
   Strip1Params p;
   const int max_strips = fill_strip1_params(p, w, y, n, x, M, act_dtype);
   p.dbg = (g_timeline && g_timeline_next < g_timeline_slots) ? g_timeline + 24 * (g_timeline_next++) : nullptr;
+  if (knob("QLLM_STRIP1_PRELOAD", kStrip1PreloadDefault) && strip1_pre_serves(p)) return launch_strip1_pre(p, pl.one_nw, pl.one_maxs, n, max_strips, stream);
   return launch_strip1(p, pl.one_nw, pl.one_maxs, n, max_strips, stream);
 }
 

@@ -268,6 +268,12 @@ __device__ __forceinline__ uint4_t load16_sys(const void *p) {
 bool strip1_shape(int K, int blocks, int cus, int *nw, int *maxs, bool odd64 = false);  // (odd64: K % 128 == 64 allowed -- 4-bit 64-wide groups)
 int launch_strip1(const Strip1Params &p, int nw, int maxs, int n_prob, int max_strips, hipStream_t stream);
 int launch_strip1_allreduce(const Strip1Params &p, int nw, int maxs, int n_strips, hipStream_t stream);  // (p.ar_* set; one layer)
+// strip1_pre.hip: the twins of the plain 4-bit, 128-wide-group, one-row forms whose leading arguments arrive in SGPRs (QLLM_STRIP1_PRELOAD)
+constexpr int kStrip1PreloadDefault = 1;
+// the forms that have a twin -- asked by the launcher (strip1_pre_serves) and by the plan text (planner.hip, describe)
+constexpr bool strip1_pre_forms(int M, int bits, int group_size) { return M == 1 && bits == 4 && group_size == 128; }
+bool strip1_pre_serves(const Strip1Params &p);
+int launch_strip1_pre(const Strip1Params &p, int nw, int maxs, int n_prob, int max_strips, hipStream_t stream);
 int launch_strip1_swiglu(const Strip1Params &p, int nw, int maxs, int n_strips, hipStream_t stream);     // strip1_swiglu.hip (p.x2 set; one layer)
 int launch_strip1_norm(const Strip1Params &p, int nw, int maxs, int n_prob, int max_strips, hipStream_t stream);  // strip1_norm.hip (p.norm_* set; M = 1)
 int launch_strip1_resid(const Strip1Params &p, int nw, int maxs, int n_strips, hipStream_t stream);         // strip1_resid.hip (p.residual set; one layer, M = 1)

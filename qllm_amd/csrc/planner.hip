@@ -21,6 +21,7 @@ static int env_int(const char *name, int dflt) {
 static Settable kSettable[] = {
     {"QLLM_STRIP1_3BIT", 0, 1, 0, 0},          // 0: 3-bit layers at batch 1 on the general strip kernel
     {"QLLM_STRIP1_MAX_M", 1, 4, 0, 0},         // 1: batches 2..4 on strip_dma instead of the batch-1 kernel's four-row forms
+    {"QLLM_STRIP1_PRELOAD", 0, 1, 0, 0},       // 0: the plain batch-1 forms take every word from the kernel-argument segment (strip1_kernel); 1: their preloading twins (strip1_pre.hip)
     {"QLLM_STRIP1", 0, 2, 0, 0},               // 0: batch-1 calls on the general strip kernel (the round-4 path); 2: only 128-wide groups on the batch-1 kernel
     {"QLLM_PANEL", 0, 1, 0, 0},                // 0: no panel kernel (strips to 32 rows, the 256-row tiles above)
     {"QLLM_PANEL_MIN_M", 17, 129, 0, 0},       // single layers: rows from which the panel kernel serves (no form below 17 rows)
@@ -631,11 +632,15 @@ void describe(const Decision &d, const qllm_weight_t *w, int n, int M, size_t ws
   switch (d.route) {
     case ROUTE_STRIP: {
       const StripPlan &pl = d.strip;
-      if (pl.one_nw)
-        snprintf(buf, buflen, "strip1 nw=%d round=%d%s%s%s grid=strips x %d layout=strip-major", pl.one_nw, pl.one_maxs,
+      if (pl.one_nw) {
+        // the plain one-row forms of 4 bits and 128-wide groups (strip1_pre_forms) have two kernels, chosen by QLLM_STRIP1_PRELOAD; the
+        // text names the choice where the knob has been moved off its default: args=kernarg (strip1_kernel) / args=preloaded (the twins)
+        const bool twin_forms = strip1_pre_forms(M, w[0].bits, w[0].group_size);
+        const int pre = knob("QLLM_STRIP1_PRELOAD", kStrip1PreloadDefault);
+        snprintf(buf, buflen, "strip1 nw=%d round=%d%s%s%s%s grid=strips x %d layout=strip-major", pl.one_nw, pl.one_maxs,
                  pl.one_nw * pl.one_maxs == w[0].K / 32 ? " exact" : "", w[0].group_size == 64 ? (w[0].bits == 3 ? " g64 bits=3" : " g64") : (w[0].bits == 3 ? " bits=3" : ""),
-                 M > 1 ? " rows=4" : "", n);
-      else
+                 M > 1 ? " rows=4" : "", (twin_forms && pre != kStrip1PreloadDefault) ? (pre ? " args=preloaded" : " args=kernarg") : "", n);
+      } else
         snprintf(buf, buflen, "strip nw=%d cpl=%d spw=%d form=%s row_tiles=%d%s", pl.nw, pl.cpl, pl.spw,
                  pl.ra == 2 ? "dma-A" : (pl.ra ? "register-A" : "lds-slab"), M > 32 ? 4 : (M > 16 ? 2 : 1), pl.sm ? " layout=strip-major" : "");
       return;

@@ -1,12 +1,14 @@
 // The body of strip1_kernel, strip1_swiglu_kernel, strip1_norm_kernel and the two RESID kernels (strip1_kernel.hpp, which documents it):
-// included inside all five, with NW, MAXS, EXACT, NCH, LVL, DBG, AR, G64, MR, B3, SWIGLU, NORM, NORM_PARK and RESID constants of the
-// enclosing function and `p` its Strip1Params.
+// included inside all five and inside the preloading twin (strip1_pre.hip), with NW, MAXS, EXACT, NCH, LVL, DBG, AR, G64, MR, B3, SWIGLU,
+// NORM, NORM_PARK, RESID and PRELOAD constants of the enclosing function, `p` its Strip1Params, and STRIP1_HOT_WORDS / STRIP1_LATE_PROBLEM
+// the enclosing unit's way to the hot words (below).
   static_assert(MAXS % 4 == 0 && MAXS >= 8 && MAXS <= 64, "rounds are whole 128-wide groups, at most 16 of them (round 6: 40 .. 64 k-steps for K up to 32768)");
   static_assert(!(G64 && AR), "the fused all-reduce form is built for 128-wide groups");
   static_assert(MR == 1 || (MR == 4 && !G64 && !AR && !DBG && LVL == 4), "four batch rows: 128-wide groups, the plain form");
   static_assert(!B3 || (MR == 1 && !AR && !DBG && LVL == 4), "3 bits: the plain batch-1 form");
   static_assert(!SWIGLU || (!AR && !DBG && LVL == 4), "act(gate) * up: the plain forms");
   static_assert(!NORM || (!SWIGLU && MR == 1 && !AR && !DBG && LVL == 4), "RMSNorm(x): the plain batch-1 forms");
+  static_assert(!PRELOAD || (!SWIGLU && !NORM && !RESID && !AR && !G64 && !B3 && MR == 1 && LVL == 4), "preloaded arguments: the plain batch-1 forms, 128-wide groups");
   static_assert(!RESID || (!NORM && MR == 1 && !AR && !DBG && LVL == 4), "residual + y: the plain and the SWIGLU batch-1 forms");
   constexpr int KPG = G64 ? 2 : 4;        // k-steps per group
   constexpr int NG = MAXS / KPG;          // groups per wave
@@ -20,18 +22,17 @@
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int g = lane >> 4, i = lane & 15;
   const int b = blockIdx.x;
-  // the problem record and the header in ONE batch of scalar loads: the empty asm "uses" every word here, so hipcc cannot leave
-  // any of them for a second round trip behind the surplus-block test
-  const Strip1Problem pr = p.prob[blockIdx.y];
-  asm volatile("" ::"s"(pr.qweight), "s"(pr.scales), "s"(pr.qzeros), "s"(pr.bias), "s"(pr.y), "s"(pr.n_strips), "s"(pr.zero_kind), "s"(p.x),
-               "s"(p.T), "s"(p.n_groups), "s"(p.add_zero_bias), "s"(p.act_bf16));
+  // (DBG: the entry stamp is read in front of the first scalar load, so that entry -> loads issued holds what the hot words cost)
+  uint64_t t_entry = 0;
+  if constexpr (DBG) t_entry = __builtin_amdgcn_s_memrealtime();
+  // the hot words of the launch -- hw_x, hw_T, hw_n_groups, add_zero_bias, act_bf16 and the problem's hw_qweight, hw_scales, hw_qzeros, hw_bias,
+  // hw_y, hw_n_strips, hw_zero_kind -- come from the enclosing kernel: STRIP1_HOT_WORDS declares them here.  The five kernels of
+  // strip1_kernel.hpp take all of them from ONE batch of scalar loads (QLLM_STRIP1_HOT_WORDS_KERNARG there); the preloading twins
+  // (strip1_pre.hip, PRELOAD) from their leading arguments, which the hardware hands over in SGPRs
+  STRIP1_HOT_WORDS
   if constexpr (SWIGLU) asm volatile("" ::"s"(p.x2));  // (the up vector's base: the same batch)
   if constexpr (NORM) asm volatile("" ::"s"(p.norm_w), "s"(p.norm_eps), "s"(p.rstd_out));  // (the norm's weight, epsilon, report slot)
   if constexpr (RESID) asm volatile("" ::"s"(p.residual));  // (the residual row's base: the same batch)
-  // the two flags the uniform branches and the tail read: taken from the first batch of scalar loads (as outputs of an asm they cannot
-  // be re-loaded next to their use -- hipcc otherwise sinks a second s_load of each into the decode branch and in front of the y store)
-  int add_zero_bias = p.add_zero_bias, act_bf16 = p.act_bf16;
-  asm volatile("" : "+s"(add_zero_bias), "+s"(act_bf16));
   uint64_t *dbg_slot = nullptr;
   if constexpr (DBG) {
     if (p.dbg && wave == 0 && blockIdx.y == 0) {
@@ -39,11 +40,16 @@
       else if (b == (int)gridDim.x / 2) dbg_slot = p.dbg + 8;
       else if (b == (int)gridDim.x - 1) dbg_slot = p.dbg + 16;
     }
-    if (dbg_slot && lane == 0) dbg_slot[0] = __builtin_amdgcn_s_memrealtime();
+    if (dbg_slot && lane == 0) {
+      dbg_slot[0] = t_entry;
+      dbg_slot[6] = PRELOAD ? 1 : 0;   // (which kernel wrote the slot: 1 the preloading twin)
+    }
   }
-  if (b >= pr.n_strips) return;  // (groups of layers of different widths)
+  if constexpr (!PRELOAD) {
+    if (b >= hw_n_strips) return;  // (groups of layers of different widths)
+  }
 
-  const int T = p.T;
+  const int T = hw_T;
   const int t0 = wave * MAXS;                              // the wave owns k-steps [t0, min(t0 + MAXS, T))
   const int tb = EXACT ? t0 : min(t0, T - MAXS);           // its window [tb, tb + MAXS): shifted back into the strip at the end of K
   // ---- every load of the wave, back to back: x chunk(s), one scale + one zero word per pass, MAXS weight words -----------------
@@ -66,7 +72,7 @@
 #pragma unroll
     for (int m = 0; m < MR; ++m) {                         // (MR = 4: batch row m of x, row stride K = 32 T halves; rows past M stay zero)
       xa[m][u] = uint4_t{0, 0, 0, 0};
-      if (MR == 1 || m < p.M) xa[m][u] = *(const uint4_t *)((const uint16_t *)p.x + (size_t)m * 32 * T + 32 * tb + 8 * cc);
+      if (MR == 1 || m < p.M) xa[m][u] = *(const uint4_t *)((const uint16_t *)hw_x + (size_t)m * 32 * T + 32 * tb + 8 * cc);
       if constexpr (SWIGLU) {
         xb[m][u] = uint4_t{0, 0, 0, 0};
         if (MR == 1 || m < p.M) xb[m][u] = *(const uint4_t *)((const uint16_t *)p.x2 + (size_t)m * 32 * T + 32 * tb + 8 * cc);
@@ -76,9 +82,15 @@
     const int t = tb + (c >> 2);
     xkeep[u] = EXACT ? (c < MAXS * 4) : (c < MAXS * 4 && t >= t0 && t < T);
   }
+  if constexpr (PRELOAD) {
+    // the twins: the x chunks above needed preloaded words only and are on their way.  Blocks of problem 0 have every word in SGPRs
+    // and wait for nothing; the blocks of a later sibling fetch their record now (STRIP1_LATE_PROBLEM: one batch of scalar loads)
+    STRIP1_LATE_PROBLEM
+    if (b >= hw_n_strips) return;
+  }
   const int G0 = tb / KPG;
-  const size_t grow = (size_t)b * p.n_groups + G0;         // first group row of the wave in the strip's scale / zero tables
-  const int zk = pr.zero_kind;
+  const size_t grow = (size_t)b * hw_n_groups + G0;         // first group row of the wave in the strip's scale / zero tables
+  const int zk = hw_zero_kind;
   half_t sc[NPASS][GPL];
   uint32_t zraw[NPASS][GPL], zraw2[B3 ? NPASS : 1][GPL];  // (zraw2: packed 3-bit zero points are bit 3 i of the group row's 64-bit pair)
   uint32_t w[MAXS], wh[B3 ? MAXS : 1];
@@ -86,9 +98,9 @@
     // a wave-uniform base (the wave's first group row) + a 32-bit lane offset: element (gj, i) of the [group][16] scale rows is
     // 16 gj + i; its zero point sits in dword (16 gj + i) >> 3 of the packed rows (2 dwords per group), >> 1 of the fp16 rows (8).
     // A symmetric layer has no table: the host points qzeros at the scales (a valid dword, never decoded)
-    const char *sbase = (const char *)(pr.scales + grow * 16);
+    const char *sbase = (const char *)(hw_scales + grow * 16);
     const int zmul = (zk == ZK_PACKED) ? 2 : 8;          // dwords per group row
-    const char *zb = (const char *)((const uint32_t *)pr.qzeros + grow * zmul);
+    const char *zb = (const char *)((const uint32_t *)hw_qzeros + grow * zmul);
     const uint32_t zsh = (zk == ZK_PACKED) ? 3u : 1u, pair = (B3 && zk == ZK_PACKED) ? 1u : 0u;
 #pragma unroll
     for (int ps = 0; ps < NPASS; ++ps)
@@ -108,7 +120,7 @@
   }
   if constexpr (B3) {
     // the strip is [3 T word rows][16]: k-step t = rows 3 t .. 3 t + 2; the lane's 24-bit field straddles rows {0,0,1,2}[g] / {0,1,2,2}[g]
-    const uint32_t *wl3 = pr.qweight + ((size_t)b * T + tb) * 48 + i;
+    const uint32_t *wl3 = hw_qweight + ((size_t)b * T + tb) * 48 + i;
     const int lo_off = (g == 0 ? 0 : g - 1) * 16, hi_off = (g == 3 ? 2 : g) * 16;
 #pragma unroll
     for (int s = 0; s < MAXS; ++s) {
@@ -116,7 +128,7 @@
       wh[s] = __builtin_nontemporal_load(wl3 + s * 48 + hi_off);
     }
   } else {
-    const uint32_t *wl = pr.qweight + ((size_t)b * T + tb) * 64 + lane;
+    const uint32_t *wl = hw_qweight + ((size_t)b * T + tb) * 64 + lane;
 #pragma unroll
     for (int s = 0; s < MAXS; ++s) w[s] = __builtin_nontemporal_load(wl + s * 64);
   }
@@ -461,7 +473,7 @@
       v = (float)(f & 1023u);
     }
     const int n = b * 16 + (threadIdx.x & 15), mrow = threadIdx.x >> 4;
-    if (pr.bias) v += (float)pr.bias[n];
+    if (hw_bias) v += (float)hw_bias[n];
     vfin = v;
     if constexpr (RESID) {
       // y = residual + linear(..) as the eager add of two tensors rounds it: the launch's own output rounded to the activation type (the
@@ -469,16 +481,16 @@
       // it read it in the prologue
       if (act_bf16) {
         const float h = __builtin_bit_cast(float, (uint32_t)f32_to_bf16(v) << 16);
-        ((uint16_t *)pr.y)[n] = f32_to_bf16(h + __builtin_bit_cast(float, resid << 16));
+        ((uint16_t *)hw_y)[n] = f32_to_bf16(h + __builtin_bit_cast(float, resid << 16));
       } else {
         const half_t h = (half_t)v;
-        ((half_t *)pr.y)[n] = (half_t)((float)h + (float)__builtin_bit_cast(half_t, (uint16_t)resid));
+        ((half_t *)hw_y)[n] = (half_t)((float)h + (float)__builtin_bit_cast(half_t, (uint16_t)resid));
       }
     } else if constexpr (!AR) {
       if (MR == 1 || mrow < p.M) {
-        const size_t at = (size_t)mrow * pr.n_strips * 16 + n;   // (y is [M][N], N = 16 n_strips)
-        if (act_bf16) ((uint16_t *)pr.y)[at] = f32_to_bf16(v);
-        else ((half_t *)pr.y)[at] = (half_t)v;
+        const size_t at = (size_t)mrow * hw_n_strips * 16 + n;   // (y is [M][N], N = 16 n_strips)
+        if (act_bf16) ((uint16_t *)hw_y)[at] = f32_to_bf16(v);
+        else ((half_t *)hw_y)[at] = (half_t)v;
       }
     }
   }
@@ -555,7 +567,7 @@
         if (act_bf16) o[j] = (uint32_t)f32_to_bf16(a8[2 * j]) | ((uint32_t)f32_to_bf16(a8[2 * j + 1]) << 16);
         else o[j] = as_u32(half2_t{(half_t)a8[2 * j], (half_t)a8[2 * j + 1]});
       }
-      *((uint4_t *)pr.y + c) = uint4_t{o[0], o[1], o[2], o[3]};
+      *((uint4_t *)hw_y + c) = uint4_t{o[0], o[1], o[2], o[3]};
     }
     if (threadIdx.x == 0) __hip_atomic_store(&own->epoch, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }

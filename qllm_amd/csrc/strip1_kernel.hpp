@@ -169,11 +169,31 @@ constexpr int kStrip1NormLdsBytes = 64;
 //     behind their last MFMA.  Batch 1 only,
 //     no AR; kernels of their own around the same body (strip1_resid_kernel, strip1_swiglu_resid_kernel below; strip1_resid.hip,
 //     strip1_swiglu_resid.hip), as for SWIGLU.  y may be the residual row itself: element n is read and written by the same thread.
+// The hot words of strip1_body.inc as the five kernels below get them (STRIP1_HOT_WORDS while the body is included): the problem record
+// and the header in ONE batch of scalar loads -- the empty asm "uses" every word, so hipcc cannot leave any of them for a second round
+// trip behind the surplus-block test -- and the two flags the uniform branches and the tail read as outputs of an asm (they cannot be
+// re-loaded next to their use: hipcc otherwise sinks a second s_load of each into the decode branch and in front of the y store).
+// PRELOAD (strip1_pre.hip): the twins whose leading arguments carry these words; they define the two macros themselves.
+#define QLLM_STRIP1_HOT_WORDS_KERNARG                                                                                                     \
+  const Strip1Problem pr = p.prob[blockIdx.y];                                                                                            \
+  asm volatile("" ::"s"(pr.qweight), "s"(pr.scales), "s"(pr.qzeros), "s"(pr.bias), "s"(pr.y), "s"(pr.n_strips), "s"(pr.zero_kind), "s"(p.x), \
+               "s"(p.T), "s"(p.n_groups), "s"(p.add_zero_bias), "s"(p.act_bf16));                                                         \
+  const void *const hw_x = p.x;                                                                                                           \
+  const int hw_T = p.T, hw_n_groups = p.n_groups, hw_n_strips = pr.n_strips, hw_zero_kind = pr.zero_kind;                                 \
+  const uint32_t *const hw_qweight = pr.qweight;                                                                                          \
+  const half_t *const hw_scales = pr.scales, *const hw_bias = pr.bias;                                                                    \
+  const void *const hw_qzeros = pr.qzeros;                                                                                                \
+  void *const hw_y = pr.y;                                                                                                                \
+  int add_zero_bias = p.add_zero_bias, act_bf16 = p.act_bf16;                                                                             \
+  asm volatile("" : "+s"(add_zero_bias), "+s"(act_bf16));
+#define STRIP1_HOT_WORDS QLLM_STRIP1_HOT_WORDS_KERNARG
+#define STRIP1_LATE_PROBLEM
+
 template <int NW, int MAXS, bool EXACT, int NCH = 2, int LVL = 4, bool DBG = false, bool AR = false, bool G64 = false, int MR = 1, bool B3 = false>
 // (second launch bound = minimum waves per SIMD: 64 registers up to rounds of 24 k-steps -- a CU full of waves -- 128 above)
 __global__ __launch_bounds__(NW * 64, strip1_min_waves(MAXS, G64, MR, B3)) void strip1_kernel(const Strip1Params p) {
   constexpr bool SWIGLU = false, NORM = false, NORM_PARK = false;
-  constexpr bool RESID = false;
+  constexpr bool RESID = false, PRELOAD = false;
 #include "strip1_body.inc"
 }
 
@@ -181,7 +201,7 @@ __global__ __launch_bounds__(NW * 64, strip1_min_waves(MAXS, G64, MR, B3)) void 
 template <int NW, int MAXS, bool EXACT, bool G64, int MR, bool B3, int WAVES>
 __global__ __launch_bounds__(NW * 64, WAVES) void strip1_swiglu_kernel(const Strip1Params p) {
   constexpr bool SWIGLU = true, NORM = false, NORM_PARK = false, DBG = false, AR = false;
-  constexpr bool RESID = false;
+  constexpr bool RESID = false, PRELOAD = false;
   constexpr int NCH = 2, LVL = 4;
 #include "strip1_body.inc"
 }
@@ -190,7 +210,7 @@ __global__ __launch_bounds__(NW * 64, WAVES) void strip1_swiglu_kernel(const Str
 template <int NW, int MAXS, bool EXACT, bool G64, int MR, bool B3, int WAVES>
 __global__ __launch_bounds__(NW * 64, WAVES) void strip1_norm_kernel(const Strip1Params p) {
   constexpr bool SWIGLU = false, NORM = true, DBG = false, AR = false;
-  constexpr bool RESID = false;
+  constexpr bool RESID = false, PRELOAD = false;
   constexpr bool NORM_PARK = MAXS >= 64 || (MAXS == 24 && !G64 && !B3);   // (the forms whose twins sit next to their register bound)
   constexpr int NCH = 2, LVL = 4;
 #include "strip1_body.inc"
@@ -200,7 +220,7 @@ __global__ __launch_bounds__(NW * 64, WAVES) void strip1_norm_kernel(const Strip
 template <int NW, int MAXS, bool EXACT, bool G64, bool B3, int WAVES>
 __global__ __launch_bounds__(NW * 64, WAVES) void strip1_resid_kernel(const Strip1Params p) {
   constexpr bool SWIGLU = false, NORM = false, NORM_PARK = false, DBG = false, AR = false;
-  constexpr bool RESID = true;
+  constexpr bool RESID = true, PRELOAD = false;
   constexpr int NCH = 2, LVL = 4, MR = 1;
 #include "strip1_body.inc"
 }
@@ -208,9 +228,12 @@ __global__ __launch_bounds__(NW * 64, WAVES) void strip1_resid_kernel(const Stri
 template <int NW, int MAXS, bool EXACT, bool G64, bool B3, int WAVES>
 __global__ __launch_bounds__(NW * 64, WAVES) void strip1_swiglu_resid_kernel(const Strip1Params p) {
   constexpr bool SWIGLU = true, NORM = false, NORM_PARK = false, DBG = false, AR = false;
-  constexpr bool RESID = true;
+  constexpr bool RESID = true, PRELOAD = false;
   constexpr int NCH = 2, LVL = 4, MR = 1;
 #include "strip1_body.inc"
 }
+
+#undef STRIP1_HOT_WORDS
+#undef STRIP1_LATE_PROBLEM
 
 }  // namespace qllm
