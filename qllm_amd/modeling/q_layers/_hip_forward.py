@@ -43,11 +43,28 @@ def bitgroup_serves(bits: int, n_layers: int, act_order: bool, rows: int) -> boo
     return bits in (2, 5, 6, 7, 8) and n_layers <= 4 and not act_order and 1 <= rows <= ops.bitgroup_max_m()
 
 
+_ACT_DTYPES = (torch.float16, torch.bfloat16)   # the activation types of the kernels
+
+
+def _on_device(*tensors) -> bool:
+    return all(t.is_cuda for t in tensors)
+
+
+def _act_tensors_ok(*tensors, on_device=_on_device) -> bool:
+    """What every opt-in fusion asks of the tensors of one call before anything of its own (fused residual, fused_norm, fused_rope,
+    fused_attention): device tensors of one activation type, and with grad mode on nothing to differentiate.  `on_device`: the device
+    test -- fused_attention hands in its module's name for it, which its host-logic tests replace; None where the caller has asked
+    already (fused_rope, behind its test that these are tensors at all).  A plain loop: it runs several times per layer and eager step."""
+    dtype, grad = tensors[0].dtype, torch.is_grad_enabled()
+    for t in tensors:
+        if t.dtype != dtype or (grad and t.requires_grad):
+            return False
+    return dtype in _ACT_DTYPES and (on_device is None or on_device(*tensors))
+
+
 def _fused_tensors_ok(*tensors) -> bool:
-    """What the fused residual entries ask of the tensors of one call: device tensors of one activation type, nothing to differentiate."""
-    t0 = tensors[0]
-    return (t0.dtype in (torch.float16, torch.bfloat16) and all(t.is_cuda and t.dtype == t0.dtype and t.device == t0.device for t in tensors)
-            and not (torch.is_grad_enabled() and any(t.requires_grad for t in tensors)))
+    """What the fused residual entries ask of the tensors of one call: `_act_tensors_ok`, and -- they alone -- all on ONE device."""
+    return _act_tensors_ok(*tensors) and all(t.device == tensors[0].device for t in tensors)
 
 
 # derived, pointer-holding state (ctypes descriptors, shadows, sibling groups): rebuilt on demand, never copied or pickled
@@ -208,20 +225,27 @@ class HipForwardMixin:
                 return w
         return self._descriptor(act_order_g_idx, add_zero_bias)
 
+    def _act_order_resolved(self) -> bool:
+        """Whether this is an act-order layer.  GPTQ (alone) detects that lazily, `_resolve_act_order`: do it before branching on it."""
+        resolve = getattr(self, "_resolve_act_order", None)
+        if resolve is not None:
+            resolve()
+        return bool(getattr(self, "act_order", None))
+
+    def _add_zero_bias(self) -> int:
+        """The AutoGPTQ zero-point offset of this call's descriptor: read per call, like the reference (quant_linear_gptq.py:75); GPTQ only."""
+        return autogptq_compat() if self._layout_name() == "GPTQ" else 0
+
     def forward_into(self, x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
         """y = forward(x) written into the caller's contiguous [M, out_features] tensor `out` (no allocation; used by the
         tensor-parallel wrappers, whose shard kernels write straight into their slice of the gathered output).  Layers without a
         plain fused path for the call (act-order, unsupported shapes) compute normally and copy."""
         x2d = x.reshape(-1, x.shape[-1])
-        resolve = getattr(self, "_resolve_act_order", None)   # (GPTQ detects act-order lazily: do it before branching on it)
-        if resolve is not None:
-            resolve()
-        if getattr(self, "act_order", None) or not x2d.is_contiguous() or not out.is_contiguous():
+        if self._act_order_resolved() or not x2d.is_contiguous() or not out.is_contiguous():
             out.copy_(self(x).reshape(out.shape))
             return out
-        azb = autogptq_compat() if self._layout_name() == "GPTQ" else 0
         try:
-            ops.linear_forward(self.decode_descriptor(None, azb), x2d, out=out.view(x2d.shape[0], self.outfeatures))
+            ops.linear_forward(self.decode_descriptor(None, self._add_zero_bias()), x2d, out=out.view(x2d.shape[0], self.outfeatures))
         except ops.QllmUnsupported:
             out.copy_(self(x).reshape(out.shape))
         return out
@@ -231,14 +255,9 @@ class HipForwardMixin:
         partial outputs straight into the peers' staging buffers of `reducer`, a qllm_amd.comm.OneShotAllReduce; csrc/strip1_kernel.hpp,
         AR).  False when the call is not served (rows, layout, shape, act-order): the caller then runs forward_into + the collective."""
         x2d = x.reshape(-1, x.shape[-1])
-        resolve = getattr(self, "_resolve_act_order", None)
-        if resolve is not None:
-            resolve()
-        if (x2d.shape[0] != 1 or getattr(self, "act_order", None) or not x2d.is_contiguous() or not out.is_contiguous()
-                or not hasattr(reducer, "linear_all_reduce")):
+        if self._act_order_resolved() or x2d.shape[0] != 1 or not x2d.is_contiguous() or not out.is_contiguous() or not hasattr(reducer, "linear_all_reduce"):
             return False
-        azb = autogptq_compat() if self._layout_name() == "GPTQ" else 0
-        w = self.native_descriptor(azb)
+        w = self.native_descriptor(self._add_zero_bias())
         return w is not None and reducer.linear_all_reduce(w, x2d, out.view(1, self.outfeatures))
 
     # smallest row count the fused SwiGLU entry refused for this layer (what it serves is monotone in the row count: 1, or up to 4 rows)
@@ -255,14 +274,9 @@ class HipForwardMixin:
         g2d = gate.reshape(-1, gate.shape[-1])
         u2d = up.reshape(-1, up.shape[-1])
         m = g2d.shape[0]
-        resolve = getattr(self, "_resolve_act_order", None)   # (GPTQ detects act-order lazily: do it before branching on it)
-        if resolve is not None:
-            resolve()
-        if (1 <= m <= self.swiglu_max_m and m < self._swiglu_refused_from and gate.shape == up.shape and gate.dtype == up.dtype
-                and gate.dtype in (torch.float16, torch.bfloat16) and g2d.is_contiguous() and u2d.is_contiguous()
-                and not getattr(self, "act_order", None)):
-            azb = autogptq_compat() if self._layout_name() == "GPTQ" else 0
-            w = self.native_descriptor(azb)
+        if (not self._act_order_resolved() and 1 <= m <= self.swiglu_max_m and m < self._swiglu_refused_from and gate.shape == up.shape
+                and gate.dtype == up.dtype and gate.dtype in _ACT_DTYPES and g2d.is_contiguous() and u2d.is_contiguous()):
+            w = self.native_descriptor(self._add_zero_bias())
             if w is not None:
                 try:
                     return ops.linear_forward_swiglu(w, g2d, u2d).reshape(gate.shape[:-1] + (self.outfeatures,))
@@ -283,14 +297,11 @@ class HipForwardMixin:
         non-contiguous tensors, CPU tensors, grad mode, an act-order layer, no native copy."""
         x = inputs[0]
         m = x.numel() // x.shape[-1] if x.shape[-1] else 0
-        resolve = getattr(self, "_resolve_act_order", None)   # (GPTQ detects act-order lazily: do it before branching on it)
-        if resolve is not None:
-            resolve()
-        if (refused or not 1 <= m <= self.residual_max_m or any(t.shape != x.shape for t in inputs)
+        if (self._act_order_resolved() or refused or not 1 <= m <= self.residual_max_m or any(t.shape != x.shape for t in inputs)
                 or residual.shape != x.shape[:-1] + (self.outfeatures,) or not _fused_tensors_ok(*inputs, residual)
-                or not all(t.reshape(-1, t.shape[-1]).is_contiguous() for t in (*inputs, residual)) or getattr(self, "act_order", None)):
+                or not all(t.reshape(-1, t.shape[-1]).is_contiguous() for t in (*inputs, residual))):
             return None
-        return self.native_descriptor(autogptq_compat() if self._layout_name() == "GPTQ" else 0)
+        return self.native_descriptor(self._add_zero_bias())
 
     def forward_residual(self, x: torch.Tensor, residual: torch.Tensor) -> torch.Tensor:
         """residual + forward(x) -- the o_proj (or down_proj) of a decoder layer with its residual add.  Where the batch-1 kernel serves

@@ -20,6 +20,7 @@ import torch
 
 from ... import ops
 from ._hip_forward import bitgroup_serves, tensor_version
+from ._patching import switched_off
 
 GROUP_MAX_M = 128  # the grouped entry point serves decode and mid-batch sizes (strips to 32 rows, the panel kernel to 128)
 
@@ -35,7 +36,7 @@ class SiblingGroup:
         self._ver = -1
         self._azb = 0
         self._parked: dict = {}
-        self._misses = 0     # consecutive grouped launches whose parked outputs nobody collected (see forward_for)
+        self._misses = 0     # consecutive grouped launches whose parked outputs nobody collected (see begin_launch)
         self._refused_from = GROUP_MAX_M + 1  # smallest row count the grouped entry point refused for this group (see forward_for)
         self._prefill_refused_upto = GROUP_MAX_M  # largest prefill-sized row count (> GROUP_MAX_M) the grouped entry point refused
         self.grouped_launches = 0  # diagnostics / tests
@@ -59,28 +60,58 @@ class SiblingGroup:
                 return False
         return True
 
+    # ---- the parking protocol, written ONCE: `forward_for` and fused_norm's `PreNorm.fused` run collect -> begin_launch -> their launch -> park
+    def collect(self, layer, x: torch.Tensor, add_zero_bias: int) -> Optional[torch.Tensor]:
+        """The output parked for `layer` by a sibling's launch on this very (x, its version, add_zero_bias), handed out once; else None."""
+        held = self._x() if self._x is not None else None
+        if not (held is x and tensor_version(x) == self._ver and add_zero_bias == self._azb and id(layer) in self._parked):
+            return None
+        out = self._parked.pop(id(layer))
+        self._misses = 0
+        if not self._parked:
+            self._x = None
+        return out
+
+    def begin_launch(self) -> bool:
+        """In front of a new launch: count a miss when the previous launch's parked outputs were never asked for (the caller hands every
+        sibling a NEW tensor object, e.g. through accelerate hooks: grouping then multiplies the work instead of saving launches --
+        three in a row switch the group off), drop them, and say whether the group is still enabled."""
+        if self._parked:
+            self._misses += 1
+            if self._misses >= 3:
+                self.enabled = False
+        self.forget()
+        return self.enabled
+
+    def park(self, layer, x: torch.Tensor, add_zero_bias: int, outs) -> torch.Tensor:
+        """After a launch that computed `outs` (one [M, N_l] per layer of the group) from x: park the siblings' outputs under
+        (x, its version, add_zero_bias) and return `layer`'s, each shaped like x with its layer's width."""
+        self.grouped_launches += 1
+        shape = x.shape[:-1]
+        mine = None
+        for l, o in zip(self.layers, outs):
+            o = o.reshape(shape + (l.outfeatures,))
+            if l is layer:
+                mine = o
+            else:
+                self._parked[id(l)] = o
+        self._x, self._ver, self._azb = weakref.ref(x), tensor_version(x), add_zero_bias
+        return mine
+
+    def forget(self):
+        """Drop whatever is parked (no miss counted)."""
+        self._x, self._parked = None, {}
+
     def forward_for(self, layer, x: torch.Tensor, add_zero_bias: int = 0) -> Optional[torch.Tensor]:
         """Output of `layer` for x, or None when the caller must run its own launch.  `add_zero_bias`: the caller's
         COMPATIBLE_WITH_AUTOGPTQ value for this forward (the reference reads it per call, quant_linear_gptq.py:75): it is part of
         the descriptors the group launches with and of the key the parked outputs are matched on."""
         if not self.enabled:
             return None
-        key = id(layer)
-        held = self._x() if self._x is not None else None
-        if held is x and tensor_version(x) == self._ver and add_zero_bias == self._azb and key in self._parked:
-            out = self._parked.pop(key)
-            self._misses = 0
-            if not self._parked:
-                self._x = None
+        out = self.collect(layer, x, add_zero_bias)
+        if out is not None:
             return out
-        if self._parked:
-            # the siblings' outputs of the previous launch were never asked for (the caller hands every sibling a NEW tensor
-            # object, e.g. through accelerate hooks): grouping then multiplies the work instead of saving launches
-            self._misses += 1
-            if self._misses >= 3:
-                self.enabled = False
-        self._x, self._parked = None, {}
-        if not self.enabled:
+        if not self.begin_launch():
             return None
         x2d = x.reshape(-1, x.shape[-1])
         m = x2d.shape[0]
@@ -124,17 +155,7 @@ class SiblingGroup:
             if m == 1:
                 self.enabled = False
             return None
-        self.grouped_launches += 1
-        shape = x.shape[:-1]
-        mine = None
-        for l, o in zip(self.layers, outs):
-            o = o.reshape(shape + (l.outfeatures,))
-            if l is layer:
-                mine = o
-            else:
-                self._parked[id(l)] = o
-        self._x, self._ver, self._azb = weakref.ref(x), tensor_version(x), add_zero_bias
-        return mine
+        return self.park(layer, x, add_zero_bias, outs)
 
 
 def fuse_siblings(layers: Sequence[torch.nn.Module]) -> SiblingGroup:
@@ -156,7 +177,7 @@ def install_sibling_groups(model: torch.nn.Module, q_layer_types) -> int:
     its own bits / groupsize): siblings that disagree are partitioned -- q/k at 3 bits and v at 4 become ONE grouped launch for
     q/k and v's own launch, instead of three single launches (round 6; until then such a parent got no group at all).
     QLLM_FUSE_SIBLINGS=0 disables it."""
-    if os.environ.get("QLLM_FUSE_SIBLINGS", "1") == "0":
+    if switched_off("QLLM_FUSE_SIBLINGS"):
         return 0
     n = 0
     types = tuple(q_layer_types)

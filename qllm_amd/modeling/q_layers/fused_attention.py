@@ -58,15 +58,13 @@ from typing import Iterable, Optional
 import torch
 
 from ... import ops
+from . import _patching
+from ._hip_forward import _act_tensors_ok, _on_device   # (`_on_device`: this module's name is the one `_gate` asks and the host-logic tests replace)
 from .fused_norm import ATTENTION_TYPES
-from .fused_rope import _ACT_DTYPES, _CORE, _known, _patch, _unpatch
+from .fused_rope import _CORE, _known, _patch, _unpatch
 
 # kwargs the decoder layers pass on that do not change what the attention computes; any other one must be None or False
 _BENIGN = ("position_ids", "cache_position", "use_cache", "output_hidden_states", "return_dict", "is_causal")
-
-
-def _on_device(*ts) -> bool:
-    return all(t.is_cuda for t in ts)
 
 
 def _layer_of(past_key_values, layer_idx, uninitialized=False, sliding=None):
@@ -115,9 +113,7 @@ def _gate(self, q, k, v, attention_mask, past_key_values, kwargs, window, rows, 
     buffers, their type, batch and head size.  Nothing here touches the cache."""
     if past_key_values is None or self.training or self.config._attn_implementation not in ("sdpa", "eager"):
         return None
-    if q.dtype not in _ACT_DTYPES or k.dtype != q.dtype or v.dtype != q.dtype or not _on_device(q, k, v):
-        return None
-    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+    if not _act_tensors_ok(q, k, v, on_device=_on_device):
         return None
     sliding = getattr(self.config, "sliding_window", None) if window == "config" else getattr(self, "sliding_window", None) if window == "self" else None
     if any(val is not None and val is not False for name, val in kwargs.items() if name not in _BENIGN):
@@ -268,12 +264,10 @@ def install_fused_attention(model: torch.nn.Module, attention_types: Optional[It
     QLLM_FUSE_ATTENTION=0 makes it a no-op that returns 0.  `uninstall_fused_attention` restores exactly what was there, in any order with
     `uninstall_fused_rope`.  `prefill` (opt-in, off by default): the modules get `_fused_core_prefill`, which also serves calls with two
     or more query tokens; QLLM_FUSE_ATTENTION_PREFILL=0 turns the flag into a no-op (the decode core alone is installed)."""
-    if os.environ.get("QLLM_FUSE_ATTENTION", "1") == "0":
+    if _patching.switched_off("QLLM_FUSE_ATTENTION"):
         return 0
-    core = _fused_core_prefill if prefill and os.environ.get("QLLM_FUSE_ATTENTION_PREFILL", "1") != "0" else _fused_core
-    names = set(ATTENTION_TYPES)
-    if attention_types is not None:
-        names &= {t if isinstance(t, str) else t.__name__ for t in attention_types}
+    core = _fused_core_prefill if prefill and not _patching.switched_off("QLLM_FUSE_ATTENTION_PREFILL") else _fused_core
+    names = _patching.class_names(ATTENTION_TYPES, attention_types, intersect=True)
     n = 0
     for attn in model.modules():
         if type(attn).__name__ not in names or _CORE in attn.__dict__:

@@ -10,11 +10,11 @@ does not serve (other widths, act-order ...) fall back, inside
 QuantLlamaMLP (qllm/modeling/q_layers/__init__.py:4, import commented out)."""
 from __future__ import annotations
 
-import os
-import types
 from typing import Iterable, Optional
 
 import torch
+
+from . import _patching
 
 DEFAULT_MLP_TYPES = ("LlamaMLP", "MistralMLP", "Qwen2MLP")
 _ORIGINAL = "_qllm_unfused_forward"
@@ -49,31 +49,23 @@ def install_fused_mlp(model: torch.nn.Module, q_layer_types, mlp_types: Optional
     """Patch every SwiGLU MLP of `model` whose class (or class name) is in `mlp_types` -- default LlamaMLP, MistralMLP, Qwen2MLP --
     and whose gate_proj / up_proj / down_proj are all q_layers with a SiLU act_fn (torch.nn.SiLU, torch.nn.functional.silu, or transformers' SiLUActivation).  Returns the number of modules patched;
     QLLM_FUSE_MLP=0 makes it a no-op that returns 0.  `uninstall_fused_mlp` restores the original forwards."""
-    if os.environ.get("QLLM_FUSE_MLP", "1") == "0":
+    if _patching.switched_off("QLLM_FUSE_MLP"):
         return 0
-    names = {t if isinstance(t, str) else t.__name__ for t in (DEFAULT_MLP_TYPES if mlp_types is None else mlp_types)}
+    names = _patching.class_names(DEFAULT_MLP_TYPES, mlp_types, intersect=False)
     q_types = tuple(q_layer_types)
     n = 0
     for mod in model.modules():
-        if not _eligible(mod, names, q_types):
-            continue
-        # (the instance's own forward, if it has one, else the marker None: uninstall puts back exactly what was there)
-        setattr(mod, _ORIGINAL, mod.__dict__.get("forward"))
-        mod.forward = types.MethodType(_fused_forward, mod)
-        n += 1
+        if _eligible(mod, names, q_types):
+            setattr(mod, _ORIGINAL, _patching.replace(mod, _fused_forward))
+            n += 1
     return n
 
 
 def uninstall_fused_mlp(model: torch.nn.Module) -> int:
-    """Undo `install_fused_mlp`: every patched module computes through its class's forward again.  Returns how many were restored."""
+    """Undo `install_fused_mlp`: every patched module computes through the forward it had.  Returns how many were restored."""
     n = 0
     for mod in model.modules():
-        if _ORIGINAL not in mod.__dict__:
-            continue
-        orig = mod.__dict__.pop(_ORIGINAL)
-        if orig is None:
-            mod.__dict__.pop("forward", None)
-        else:
-            mod.forward = orig
-        n += 1
+        if _ORIGINAL in mod.__dict__:
+            _patching.restore(mod, mod.__dict__.pop(_ORIGINAL))
+            n += 1
     return n

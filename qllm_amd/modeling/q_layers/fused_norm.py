@@ -19,14 +19,14 @@ q_layers/__init__.py next to the fused MLP's)."""
 from __future__ import annotations
 
 import os
-import types
 import weakref
 from typing import Iterable, Optional
 
 import torch
 
 from ... import ops
-from ._hip_forward import autogptq_compat, tensor_version
+from . import _patching
+from ._hip_forward import _act_tensors_ok, tensor_version
 from .fused_mlp import DEFAULT_MLP_TYPES
 
 DEFAULT_LAYER_TYPES = ("LlamaDecoderLayer", "MistralDecoderLayer", "Qwen2DecoderLayer")
@@ -34,19 +34,14 @@ DEFAULT_NORM_TYPES = ("LlamaRMSNorm", "MistralRMSNorm", "Qwen2RMSNorm")
 ATTENTION_TYPES = tuple(f"{fam}{kind}" for fam in ("Llama", "Mistral", "Qwen2") for kind in ("Attention", "SdpaAttention", "FlashAttention2", "FlashAttention"))
 _ORIGINAL = "_qllm_unfused_norm_forward"   # on a norm module: the instance forward it had (None: the class's)
 _PRENORM = "_qllm_prenorm"                 # on a consumer: (PreNorm, the instance forward it had or None)
-_ACT_DTYPES = (torch.float16, torch.bfloat16)
-
-
-def _original_forward(mod, orig):
-    return orig if orig is not None else types.MethodType(type(mod).forward, mod)
 
 
 def _kernel_applies(x: torch.Tensor, weight: torch.Tensor) -> bool:
-    """`ops.rmsnorm` computes this call: device tensors of one activation type, contiguous and 16-byte aligned, nothing to differentiate."""
-    return (x.is_cuda and weight.is_cuda and x.dtype in _ACT_DTYPES and weight.dtype == x.dtype and x.dim() >= 1 and x.shape[-1] == weight.shape[0]
+    """`ops.rmsnorm` computes this call: device tensors of one activation type, nothing to differentiate (`_act_tensors_ok`), of a width
+    the kernel takes, contiguous and 16-byte aligned."""
+    return (_act_tensors_ok(x, weight) and x.dim() >= 1 and x.shape[-1] == weight.shape[0]
             and x.shape[-1] % 8 == 0 and x.shape[-1] <= 65536 and x.is_contiguous() and weight.is_contiguous()
-            and x.data_ptr() % 16 == 0 and weight.data_ptr() % 16 == 0
-            and not (torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad)))
+            and x.data_ptr() % 16 == 0 and weight.data_ptr() % 16 == 0)
 
 
 class PreNorm:
@@ -64,7 +59,7 @@ class PreNorm:
         self.refused = False              # the fused entry refused this group once: not asked again
         self.fused_launches = 0
         self._x = None                    # weak reference to the tensor `_y` was computed from (never keeps the input alive)
-        self._ver = -1
+        self._x_version = -1
         self._y = None
 
     @property
@@ -78,51 +73,38 @@ class PreNorm:
     def apply(self, x: torch.Tensor) -> torch.Tensor:
         """RMSNorm(x): the same tensor object for the same (x, version), so the consumers' sibling group sees one input."""
         held = self._x() if self._x is not None else None
-        if held is x and tensor_version(x) == self._ver and self._y is not None:
+        if held is x and tensor_version(x) == self._x_version and self._y is not None:
             return self._y
         w = self.weight
         if _kernel_applies(x, w):
             with torch.no_grad():
                 y = ops.rmsnorm(x, w.detach(), self.eps)
         else:
-            y = _original_forward(self.norm, self.original)(x)
-        self._x, self._ver, self._y = weakref.ref(x), tensor_version(x), y
+            y = _patching.original(self.norm, self.original)(x)
+        self._x, self._x_version, self._y = weakref.ref(x), tensor_version(x), y
         return y
 
     def forget(self):
-        self._x, self._ver, self._y = None, -1, None
+        self._x, self._x_version, self._y = None, -1, None
 
     def fused(self, layer, x: torch.Tensor) -> Optional[torch.Tensor]:
         """`layer`'s output from the group's fused launch on the un-normed x, or None: the caller norms and runs the layer itself."""
         g = getattr(layer, "_siblings", None)
         if g is None or not g.enabled or self.refused:
             return None
-        azb = autogptq_compat() if layer._layout_name() == "GPTQ" else 0
-        key = id(layer)
-        held = g._x() if g._x is not None else None
-        if held is x and tensor_version(x) == g._ver and azb == g._azb and key in g._parked:
-            out = g._parked.pop(key)      # (parked by a sibling's fused launch on this very tensor)
-            g._misses = 0
-            if not g._parked:
-                g._x = None
+        azb = layer._add_zero_bias()
+        out = g.collect(layer, x, azb)    # (parked by a sibling's fused launch on this very tensor)
+        if out is not None:
             return out
         w = self.weight
         k = x.shape[-1]
         if (self.norm_max_m < 1 or x.numel() != k or not _kernel_applies(x, w) or len(g.layers) != len(self.consumers)
                 or {id(l) for l in g.layers} != {id(l) for l in self.consumers} or not g.compatible()):
             return None
-        for l in g.layers:
-            resolve = getattr(l, "_resolve_act_order", None)   # (GPTQ detects act-order lazily)
-            if resolve is not None:
-                resolve()
-            if getattr(l, "act_order", None):
-                return None
-        if g._parked:   # the previous launch's parked outputs were never asked for: the group's own rule (SiblingGroup.forward_for)
-            g._misses += 1
-            if g._misses >= 3:
-                g.enabled = False
-        g._x, g._parked = None, {}
-        if not g.enabled:
+        if any(l._act_order_resolved() for l in g.layers):
+            return None
+        # (only now: a call that is not for the fused entry leaves the group's parked outputs to `forward_for`, behind the wrapped forward)
+        if not g.begin_launch():
             return None
         try:
             descs = [l.decode_descriptor(None, azb) for l in g.layers]
@@ -131,18 +113,8 @@ class PreNorm:
         except ops.QllmUnsupported:
             self.refused = True
             return None
-        g.grouped_launches += 1
         self.fused_launches += 1
-        shape = x.shape[:-1]
-        mine = None
-        for l, o in zip(g.layers, outs):
-            o = o.reshape(shape + (l.outfeatures,))
-            if l is layer:
-                mine = o
-            else:
-                g._parked[id(l)] = o
-        g._x, g._ver, g._azb = weakref.ref(x), tensor_version(x), azb
-        return mine
+        return g.park(layer, x, azb, outs)
 
 
 def _identity(self, hidden_states):
@@ -154,14 +126,14 @@ def _consumer_forward(self, x):
     y = pre.fused(self, x)
     if y is not None:
         return y
-    return _original_forward(self, orig)(pre.apply(x))
+    return _patching.original(self, orig)(pre.apply(x))
 
 
 def _norm_forward(self, hidden_states):
     if _kernel_applies(hidden_states, self.weight):
         with torch.no_grad():
             return ops.rmsnorm(hidden_states, self.weight.detach(), float(self.variance_epsilon))
-    return _original_forward(self, self.__dict__[_ORIGINAL])(hidden_states)
+    return _patching.original(self, self.__dict__[_ORIGINAL])(hidden_states)
 
 
 def _norm_ok(norm, names: set, k: int) -> bool:
@@ -186,9 +158,9 @@ def install_fused_norm(model: torch.nn.Module, q_layer_types, layer_types: Optio
     fused_mlp.DEFAULT_MLP_TYPES), every consumer a q_layer of the norm's width, the norm a module with a 1-D `weight` and a float
     `variance_epsilon`.  Anything else is not guessed at (Gemma's 1 + w norm: not on the list).  Returns the number of norms folded;
     QLLM_FUSE_NORM=0 makes it a no-op that returns 0.  `uninstall_fused_norm` restores the original forwards."""
-    if os.environ.get("QLLM_FUSE_NORM", "1") == "0":
+    if _patching.switched_off("QLLM_FUSE_NORM"):
         return 0
-    names = {t if isinstance(t, str) else t.__name__ for t in (DEFAULT_LAYER_TYPES if layer_types is None else layer_types)}
+    names = _patching.class_names(DEFAULT_LAYER_TYPES, layer_types, intersect=False)
     norm_names = set(DEFAULT_NORM_TYPES)
     q_types = tuple(q_layer_types)
     n = 0
@@ -203,12 +175,10 @@ def install_fused_norm(model: torch.nn.Module, q_layer_types, layer_types: Optio
             consumers = [getattr(parent, s, None) for s in subs]
             if not _pair(norm, consumers, norm_names, q_types):
                 continue
-            pre = PreNorm(norm, norm.__dict__.get("forward"), consumers)
+            pre = PreNorm(norm, _patching.replace(norm, _identity), consumers)
             setattr(norm, _ORIGINAL, pre.original)
-            norm.forward = types.MethodType(_identity, norm)
             for c in consumers:
-                setattr(c, _PRENORM, (pre, c.__dict__.get("forward")))
-                c.forward = types.MethodType(_consumer_forward, c)
+                setattr(c, _PRENORM, (pre, _patching.replace(c, _consumer_forward)))
             n += 1
     return n
 
@@ -217,24 +187,15 @@ def make_quant_norm(model: torch.nn.Module, norm_types: Optional[Iterable] = Non
     """Give every whitelisted RMSNorm of `model` that `install_fused_norm` did not fold (the final `model.norm`; all of them when nothing
     was installed) a forward on `ops.rmsnorm`; calls the kernel does not take (CPU tensors, other dtypes, grad mode) run the original
     forward.  Returns the number of modules patched; QLLM_FUSE_NORM=0: none.  The reference's name (triton_norm.py)."""
-    if os.environ.get("QLLM_FUSE_NORM", "1") == "0":
+    if _patching.switched_off("QLLM_FUSE_NORM"):
         return 0
-    names = {t if isinstance(t, str) else t.__name__ for t in (DEFAULT_NORM_TYPES if norm_types is None else norm_types)}
+    names = _patching.class_names(DEFAULT_NORM_TYPES, norm_types, intersect=False)
     n = 0
     for mod in model.modules():
-        if not _norm_ok(mod, names, None):
-            continue
-        setattr(mod, _ORIGINAL, mod.__dict__.get("forward"))
-        mod.forward = types.MethodType(_norm_forward, mod)
-        n += 1
+        if _norm_ok(mod, names, None):
+            setattr(mod, _ORIGINAL, _patching.replace(mod, _norm_forward))
+            n += 1
     return n
-
-
-def _restore(mod, orig):
-    if orig is None:
-        mod.__dict__.pop("forward", None)
-    else:
-        mod.forward = orig
 
 
 def uninstall_fused_norm(model: torch.nn.Module) -> int:
@@ -247,9 +208,9 @@ def uninstall_fused_norm(model: torch.nn.Module) -> int:
             pre.forget()
             g = getattr(mod, "_siblings", None)
             if g is not None:   # (outputs parked on an un-normed tensor must not meet the plain forward)
-                g._x, g._parked = None, {}
-            _restore(mod, orig)
+                g.forget()
+            _patching.restore(mod, orig)
         if _ORIGINAL in mod.__dict__:
-            _restore(mod, mod.__dict__.pop(_ORIGINAL))
+            _patching.restore(mod, mod.__dict__.pop(_ORIGINAL))
             n += 1
     return n

@@ -14,12 +14,11 @@ nothing is ever written in place into the residual tensor (fused_norm keys its c
 from __future__ import annotations
 
 import inspect
-import os
-import types
 from typing import Iterable, Optional
 
 import torch
 
+from . import _patching
 from .fused_mlp import DEFAULT_MLP_TYPES
 from .fused_norm import ATTENTION_TYPES, DEFAULT_LAYER_TYPES
 
@@ -53,7 +52,7 @@ def _q_forward(self, x):
     slot, orig, _ = self.__dict__[_ARMED]
     r = slot.take(x, self.outfeatures)
     if r is None:
-        return (orig if orig is not None else types.MethodType(type(self).forward, self))(x)
+        return _patching.original(self, orig)(x)
     return self.forward_residual(x, r)          # (its fallback, residual + self(x), comes back here with the slot empty)
 
 
@@ -61,7 +60,7 @@ def _q_forward_swiglu(self, gate, up):
     slot, _, orig = self.__dict__[_ARMED]
     r = slot.take(gate, self.outfeatures)
     if r is None:
-        return (orig if orig is not None else types.MethodType(type(self).forward_swiglu, self))(gate, up)
+        return _patching.original(self, orig, "forward_swiglu")(gate, up)
     return self.forward_swiglu_residual(gate, up, r)
 
 
@@ -124,11 +123,9 @@ def install_fused_residual(model: torch.nn.Module, q_layer_types, layer_types: O
     is annotated to return torch.Tensor (the decoder-layer contract of transformers 5: tuple-returning layers of older releases are not
     guessed at).  Anything else -- tensor-parallel wrappers included: they are no q_layers -- is left alone.  Returns the number of layers
     patched; QLLM_FUSE_RESIDUAL=0 makes it a no-op that returns 0.  `uninstall_fused_residual` restores exactly what was there."""
-    if os.environ.get("QLLM_FUSE_RESIDUAL", "1") == "0":
+    if _patching.switched_off("QLLM_FUSE_RESIDUAL"):
         return 0
-    names = set(DEFAULT_LAYER_TYPES)
-    if layer_types is not None:
-        names &= {t if isinstance(t, str) else t.__name__ for t in layer_types}
+    names = _patching.class_names(DEFAULT_LAYER_TYPES, layer_types, intersect=True)
     q_types = tuple(q_layer_types)
     n = 0
     for layer in model.modules():
@@ -147,11 +144,8 @@ def install_fused_residual(model: torch.nn.Module, q_layer_types, layer_types: O
             continue
         slots = (_Slot(), _Slot())
         for q, slot in zip((o_proj, down_proj), slots):
-            setattr(q, _ARMED, (slot, q.__dict__.get("forward"), q.__dict__.get("forward_swiglu")))
-            q.forward = types.MethodType(_q_forward, q)
-            q.forward_swiglu = types.MethodType(_q_forward_swiglu, q)
-        setattr(layer, _LAYER, (layer.__dict__.get("forward"),) + slots + (params,))
-        layer.forward = types.MethodType(_layer_forward, layer)
+            setattr(q, _ARMED, (slot, _patching.replace(q, _q_forward), _patching.replace(q, _q_forward_swiglu, "forward_swiglu")))
+        setattr(layer, _LAYER, (_patching.replace(layer, _layer_forward),) + slots + (params,))
         n += 1
     return n
 
@@ -163,16 +157,9 @@ def uninstall_fused_residual(model: torch.nn.Module) -> int:
     for mod in model.modules():
         if _ARMED in mod.__dict__:
             _, orig, orig_swiglu = mod.__dict__.pop(_ARMED)
-            for name, had in (("forward", orig), ("forward_swiglu", orig_swiglu)):
-                if had is None:
-                    mod.__dict__.pop(name, None)
-                else:
-                    setattr(mod, name, had)
+            _patching.restore(mod, orig)
+            _patching.restore(mod, orig_swiglu, "forward_swiglu")
         if _LAYER in mod.__dict__:
-            orig = mod.__dict__.pop(_LAYER)[0]
-            if orig is None:
-                mod.__dict__.pop("forward", None)
-            else:
-                mod.forward = orig
+            _patching.restore(mod, mod.__dict__.pop(_LAYER)[0])
             n += 1
     return n

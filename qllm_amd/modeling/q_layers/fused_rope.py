@@ -14,36 +14,31 @@ Opt-in: `load_quantized(..., fuse_rope=True)`."""
 from __future__ import annotations
 
 import inspect
-import os
 import sys
-import types
 from typing import Iterable, Optional
 
 import torch
 
 from ... import ops
+from . import _patching
+from ._hip_forward import _act_tensors_ok
 from .fused_norm import ATTENTION_TYPES
 
 _ATTN = "_qllm_unfused_attention_forward"   # on an attention module: (the instance forward it had or None, the eager rotary function, how it finds its sliding window)
 _CORE = "_qllm_unfused_attention_core"      # fused_attention.py's record on an attention module: the same three, and its attention core
 _KNOWN = ("hidden_states", "position_embeddings", "attention_mask", "past_key_values")
-_ACT_DTYPES = (torch.float16, torch.bfloat16)
 
 
 def _kernel_applies(q, k, cos, sin, unsqueeze_dim: int = 1):
     """What `ops.rope_plan` answers when `ops.rope` computes this call -- device tensors of one activation type, nothing to differentiate,
-    a shape and layout the entry serves -- else None."""
-    ts = (q, k, cos, sin)
-    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in ts):
+    a shape and layout the entry serves -- else None.  Here: are they tensors at all (k may be None), and where; the rest is `_shape_applies`."""
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in (q, k, cos, sin)):
         return None
     return _shape_applies(q, k, cos, sin, unsqueeze_dim)
 
 
 def _shape_applies(q, k, cos, sin, unsqueeze_dim: int = 1):
-    ts = (q, k, cos, sin)
-    if q.dtype not in _ACT_DTYPES or any(t.dtype != q.dtype for t in ts):
-        return None
-    if torch.is_grad_enabled() and any(t.requires_grad for t in ts):
+    if not _act_tensors_ok(q, k, cos, sin, on_device=None):
         return None
     try:
         return ops.rope_plan(q, k, cos, sin, unsqueeze_dim)
@@ -100,23 +95,15 @@ def _patch(attn, key: str, value: tuple) -> None:
     """Record `value` under `key` (`_ATTN` or `_CORE`) on an attention module and give it the restated forward, unless the other install
     has done so already; the instance forward it had before either (or None) is kept with both records."""
     other = attn.__dict__.get(_CORE if key == _ATTN else _ATTN)
-    if other is None:
-        orig = attn.__dict__.get("forward")
-        attn.forward = types.MethodType(_attention_forward, attn)
-    else:
-        orig = other[0]
+    orig = _patching.replace(attn, _attention_forward) if other is None else other[0]
     setattr(attn, key, (orig,) + value)
 
 
 def _unpatch(mod, key: str) -> None:
     """Undo `_patch`: drop the record; when the other install's is gone too, the module gets back the forward it had."""
     orig = mod.__dict__.pop(key)[0]
-    if (_CORE if key == _ATTN else _ATTN) in mod.__dict__:
-        return
-    if orig is None:
-        mod.__dict__.pop("forward", None)
-    else:
-        mod.forward = orig
+    if (_CORE if key == _ATTN else _ATTN) not in mod.__dict__:
+        _patching.restore(mod, orig)
 
 
 def _known(attn):
@@ -151,11 +138,9 @@ def install_fused_rope(model: torch.nn.Module, attention_types: Optional[Iterabl
     names, when given) and whose forward is the one this file knows (`_known`) an instance forward with `apply_rotary` in the place of
     the family's apply_rotary_pos_emb.  No transformers global is touched.  Anything else is left alone and not counted.  Returns the
     number of modules patched; QLLM_FUSE_ROPE=0 makes it a no-op that returns 0.  `uninstall_fused_rope` restores exactly what was there."""
-    if os.environ.get("QLLM_FUSE_ROPE", "1") == "0":
+    if _patching.switched_off("QLLM_FUSE_ROPE"):
         return 0
-    names = set(ATTENTION_TYPES)
-    if attention_types is not None:
-        names &= {t if isinstance(t, str) else t.__name__ for t in attention_types}
+    names = _patching.class_names(ATTENTION_TYPES, attention_types, intersect=True)
     n = 0
     for attn in model.modules():
         if type(attn).__name__ not in names or _ATTN in attn.__dict__:

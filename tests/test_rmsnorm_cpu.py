@@ -344,6 +344,63 @@ def test_the_fused_launch_serves_one_row_and_parks_the_siblings(monkeypatch):
         assert calls["fused"] == n
 
 
+def test_uncollected_fused_launches_and_grouped_launches_count_the_same_three_misses(monkeypatch):
+    """A launch whose parked outputs nobody collects is a miss of the GROUP, whichever path launched next and found them: PreNorm.fused
+    (the wrapped forward on the un-normed tensor) or SiblingGroup.forward_for (the group's own grouped launch).  Three in a row switch
+    the group off, and the consumers go on through PreNorm.apply and their unwrapped forwards."""
+    calls = _fake_ops(monkeypatch)
+    grouped = []
+
+    def fake_grouped(descs, x2d, outs=None):
+        grouped.append(len(descs))
+        return [(x2d.float() @ d.w.float()).to(x2d.dtype) for d in descs]
+
+    monkeypatch.setattr(fused.ops, "linear_forward_grouped", fake_grouped)
+    m = _model()
+    new = lambda seed: torch.randn(1, 1, 16, generator=torch.Generator().manual_seed(seed)).half()  # noqa: E731
+    x = new(30)
+    with torch.no_grad():
+        want = m.a(x)
+        fused_norm.install_fused_norm(m, [_Q])
+        # q/k/v -- only q_proj is ever called, each time with a new tensor: fused, fused (miss 1), grouped (miss 2), fused (miss 3)
+        q, g = m.a.self_attn.q_proj, m.a.self_attn.q_proj._siblings
+        pre = q.__dict__[fused_norm._PRENORM][0]
+        q(new(31))
+        assert (pre.fused_launches, len(g._parked), g._misses) == (1, 2, 0)
+        q(new(32))
+        assert (pre.fused_launches, len(g._parked), g._misses) == (2, 2, 1)                 # counted by PreNorm.fused
+        assert g.forward_for(q, new(33)) is not None and grouped == [3]
+        assert (len(g._parked), g._misses, g.enabled) == (2, 2, True)                        # counted by forward_for: the same counter
+        n = dict(calls)
+        x4 = new(34)
+        y = q(x4)
+        assert not g.enabled and not g._parked and g._misses == 3 and pre.fused_launches == 2   # the third, by PreNorm.fused: no launch
+        assert calls == {"rmsnorm": n["rmsnorm"] + 1, "fused": n["fused"]}                   # the standalone norm and the layer's own forward
+        assert torch.equal(y, _Q.forward(q, pre.apply(x4)))
+        # gate/up -- only gate_proj: fused, grouped (miss 1), fused (miss 2), grouped (miss 3: refused, the group is off)
+        gate, g2 = m.a.mlp.gate_proj, m.a.mlp.gate_proj._siblings
+        pre2 = gate.__dict__[fused_norm._PRENORM][0]
+        gate(new(35))
+        assert g2.forward_for(gate, new(36)) is not None and (len(g2._parked), g2._misses) == (1, 1)
+        gate(new(37))
+        assert (pre2.fused_launches, len(g2._parked), g2._misses) == (2, 1, 2)
+        assert g2.forward_for(gate, new(38)) is None and not g2.enabled and not g2._parked and grouped == [3, 2]
+        # a collected output resets the count: the third group of the model, on c's MLP
+        gate3, up3, g3 = m.c.mlp.gate_proj, m.c.mlp.up_proj, m.c.mlp.gate_proj._siblings
+        gate3(new(39))
+        gate3(new(40))
+        assert g3._misses == 1
+        x5 = new(41)
+        gate3(x5)
+        assert g3._misses == 2
+        up3(x5)
+        assert g3._misses == 0 and not g3._parked and g3.enabled
+        # both groups of layer a are off: the layer computes what the unpatched layer computes, with no fused launch
+        n = dict(calls)
+        assert torch.equal(m.a(x), want)
+        assert calls == {"rmsnorm": n["rmsnorm"] + 2, "fused": n["fused"]}
+
+
 def test_prenorm_apply_hands_out_one_tensor_per_input_version(monkeypatch):
     _fake_ops(monkeypatch)
     m = _model()
