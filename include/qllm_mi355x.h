@@ -532,8 +532,8 @@ int qllm_rope(const void *q, const void *k, const void *cos, const void *sin, vo
  * a host kv_len outside 0..max_len (kv_len + 1 > max_len with an append), a mask too short.  QLLM_ERR_UNSUPPORTED: head_dim other than
  * 64 / 128, more than 8 query heads per kv head, batch * kv_heads > 4096.  QLLM_ERR_WORKSPACE: a missing, misaligned or small
  * workspace.  Every error is raised before any device work.  No host synchronisation; hipGraph-capturable.
- * Not built: chunked attention, quantized and paged caches, per-sequence lengths other than through the mask, rotary
- * inside the kernel, an fp8 cache.  A ring-buffer cache: qllm_attn_decode_ring below.  More than one query token: qllm_attn_prefill below.
+ * Not built: chunked attention, paged caches, per-sequence lengths other than through the mask, rotary
+ * inside the kernel, an fp8 cache.  A ring-buffer cache: qllm_attn_decode_ring below; a quantized cache: qllm_attn_decode_quant below.  More than one query token: qllm_attn_prefill below.
  * ABI: the symbols are ADDITIVE within ABI 7 (QLLM_ABI_VERSION is unchanged): probe for them by symbol. */
 #define QLLM_ATTN_MASK_NONE 0
 #define QLLM_ATTN_MASK_BOOL 1
@@ -585,6 +585,62 @@ size_t qllm_attn_decode_workspace_bytes(int32_t batch, int32_t q_heads, int32_t 
  * block step; chunk: positions per split, a multiple of the tile; split s owns positions s * chunk .. (s + 1) * chunk - 1), or "refused: "
  * and the refusal text.  Pure host code. */
 int qllm_attn_decode_describe(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int64_t max_len, char *buf, size_t buflen);
+
+/* ---- quantized KV cache: 8- and 4-bit decode attention -------------------------------------------------------------------------------------- */
+/* A static, full-attention KV cache whose rows are integer codes with per-group scales, read in place by a decode kernel that appends and
+ * attends in one launch (csrc/attn_decode_quant.hip), and two small kernels that move rows into and out of the format (csrc/kv_quant.hip).
+ * Format.  A cached row is the head_dim = 64 / 128 elements of one (batch entry, kv head, position), cut into groups of 32 consecutive
+ * elements; act is act_dtype, x the input widened to fp32, all arithmetic IEEE fp32.
+ *   bits = 8, symmetric:  s = act(max|x| / 127); code = clamp(rint(x / s), -127, 127) as int8, 0 where s == 0; value = s * code.
+ *   bits = 4, asymmetric: z = act(min x), s = act((max x - min x) / 15); code = clamp(rint((x - z) / s), 0, 15), 0 where s == 0;
+ *                         value = fma(code, s, z).
+ * codes: uint8 [batch, kv_heads, max_len, head_dim * bits / 8]; group g occupies bytes [4 * bits * g, 4 * bits * (g + 1)) of its row.
+ * At 8 bits byte i is element i.  At 4 bits element i sits in nibble i of the row: byte i / 2, the LOW nibble for an even i, the high
+ * one for an odd i (8 consecutive elements are one little-endian 32-bit word, element e in bits [4e, 4e + 4)).
+ * params: act_dtype [batch, kv_heads, max_len, P]; 8 bits: P = head_dim / 32 scales; 4 bits: P = head_dim / 16, all scales, then all
+ * zeros.  Last dimensions contiguous.  Strides are arguments: batch / head / position, codes in BYTES (multiples of 8), params in
+ * elements (multiples of 2), the same three for K and V; codes pointers 16-byte and params pointers 4-byte aligned.
+ * Bytes per row at head_dim 128: fp16 256; 8 bits 128 + 8 (0.53); 4 bits 64 + 16 (0.31).
+ *
+ * qllm_attn_decode_quant: qllm_attn_decode over such a cache -- the same call, length (host or device), mask, append rule, output and
+ * determinism; fp32 scores and softmax, one rounding at the store.  Codes are converted to fp32 (exact) and the group's scale is applied
+ * once per partial dot, never per element.  Append: position kv_len's rows are quantised from k_new / v_new by the formulas above, stored
+ * (plain vector stores), and the call attends over the DEQUANTISED new row -- the output is always attention over what the cache now
+ * holds; there is no full-precision residual.  With the length on the device and kv_len + 1 > max_len nothing is stored and the first
+ * max_len positions are attended.  Positions >= kv_len are never loaded.
+ * Launch shape and workspace are qllm_attn_decode's for the same (batch, q_heads, kv_heads, head_dim, max_len): a lane owns 8 elements in
+ * both kernels, so the geometry never has more splits -- the workspace is qllm_attn_decode_workspace_bytes (no bytes function of its own).
+ * Errors: qllm_attn_decode's in its order, and: only some of the four cache tensors, a NULL or misaligned codes / params pointer or a bad
+ * codes / params stride: QLLM_ERR_INVALID; bits other than 4 / 8: QLLM_ERR_UNSUPPORTED.  Every error is raised before any device work.  No
+ * host synchronisation; hipGraph-capturable.
+ * qllm_kv_quantize: act rows src [batch, kv_heads, rows, head_dim] (batch / head / row strides in elements, multiples of 8: a
+ * [B, S, H, D] view is read in place) into positions pos0 .. pos0 + rows - 1, pos0 a host integer or (pos0_dev != NULL) an int64 the
+ * kernel reads; a host pos0 outside 0 .. max_len - rows is QLLM_ERR_INVALID, with a device pos0 rows outside the cache are not written.
+ * qllm_kv_dequantize: positions 0 .. n - 1 into dst, act [batch, kv_heads, dst_len, head_dim] (strides in elements), n a host integer
+ * in 0 .. min(max_len, dst_len) or (n_dev != NULL) an int64 the kernel reads and clamps to that range; each value rounded once to act.
+ * Neither kernel writes outside its positions.
+ * Not built: a quantized ring / sliding layer, a dynamic quantized cache, per-channel K quantisation (KIVI), fp8, a prefill kernel that
+ * reads codes, a residual full-precision window.
+ * ABI: the four symbols are ADDITIVE within ABI 7 (QLLM_ABI_VERSION is unchanged): probe for them by symbol. */
+int qllm_attn_decode_quant(const void *q, const void *k_new, const void *v_new, void *k_codes, void *k_params, void *v_codes, void *v_params,
+                           const void *mask, void *out, int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t bits, int64_t kv_len,
+                           const int64_t *kv_len_dev, int64_t max_len, int64_t q_row_stride, int64_t q_head_stride, int64_t k_new_row_stride,
+                           int64_t k_new_head_stride, int64_t v_new_row_stride, int64_t v_new_head_stride, int64_t codes_batch_stride,
+                           int64_t codes_head_stride, int64_t codes_pos_stride, int64_t params_batch_stride, int64_t params_head_stride,
+                           int64_t params_pos_stride, int32_t mask_kind, int64_t mask_len, int64_t mask_batch_stride, float scaling, int32_t act_dtype,
+                           void *workspace, size_t workspace_bytes, void *stream);
+/* "attn_decode_quant bits=8 tile=64 splits=16 chunk=256 grid=16x32x1 group=1 combine=last-block", or "refused: " and the refusal text.
+ * Pure host code. */
+int qllm_attn_decode_quant_describe(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t bits, int64_t max_len, char *buf,
+                                    size_t buflen);
+int qllm_kv_quantize(const void *src, void *codes, void *params, int32_t batch, int32_t kv_heads, int32_t rows, int32_t head_dim, int32_t bits, int64_t pos0,
+                     const int64_t *pos0_dev, int64_t max_len, int64_t src_batch_stride, int64_t src_head_stride, int64_t src_row_stride,
+                     int64_t codes_batch_stride, int64_t codes_head_stride, int64_t codes_pos_stride, int64_t params_batch_stride, int64_t params_head_stride,
+                     int64_t params_pos_stride, int32_t act_dtype, void *stream);
+int qllm_kv_dequantize(const void *codes, const void *params, void *dst, int32_t batch, int32_t kv_heads, int32_t head_dim, int32_t bits, int64_t n,
+                       const int64_t *n_dev, int64_t max_len, int64_t dst_len, int64_t codes_batch_stride, int64_t codes_head_stride, int64_t codes_pos_stride,
+                       int64_t params_batch_stride, int64_t params_head_stride, int64_t params_pos_stride, int64_t dst_batch_stride, int64_t dst_head_stride,
+                       int64_t dst_pos_stride, int32_t act_dtype, void *stream);
 
 /* ---- prefill attention over the KV cache --------------------------------------------------------------------------------------------------- */
 /* out[b, i, h, :] = softmax_j(scaling * q[b, h, i, :] . K[b, h / G, j, :] + mask[b, i, j]) V[b, h / G, j, :] for q_len >= 2 query rows per

@@ -9,12 +9,16 @@ from . import _lib  # noqa: F401
 __version__ = "0.1.0"
 
 _RING = ("RingSlidingWindowLayer", "ring_static_cache", "to_ring")   # modeling/ring_cache.py, imported on first use (it imports transformers)
+_QUANT = ("QuantStaticLayer", "quant_static_cache", "to_quant")      # modeling/quant_cache.py, likewise
 
 
 def __getattr__(name: str):
     if name in _RING:
         from .modeling import ring_cache
         return getattr(ring_cache, name)
+    if name in _QUANT:
+        from .modeling import quant_cache
+        return getattr(quant_cache, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -121,6 +121,11 @@ SIGNATURES = {
                                            i32, C.c_float, i32, vp]),
     "qllm_attn_decode_ring": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i64, vp, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, i32,
                                         i64, i64, C.c_float, i32, vp, sz, vp]),
+    "qllm_attn_decode_quant": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i64, vp, i64] + [i64] * 12 + [i32, i64, i64, C.c_float, i32,
+                                                                                                                          vp, sz, vp]),
+    "qllm_attn_decode_quant_describe": (C.c_int, [i32, i32, i32, i32, i32, i64, C.c_char_p, sz]),
+    "qllm_kv_quantize": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i64, vp, i64] + [i64] * 9 + [i32, vp]),
+    "qllm_kv_dequantize": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i64, vp, i64, i64] + [i64] * 9 + [i32, vp]),
 }
 EXPORTS = tuple(SIGNATURES)
 

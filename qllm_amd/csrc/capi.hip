@@ -18,6 +18,7 @@
 #include <algorithm>
 
 #include "planner.hpp"
+#include "kv_quant.hpp"
 
 namespace qllm {
 
@@ -1219,6 +1220,149 @@ int qllm_attn_decode_ring(const void *q, const void *k_new, const void *v_new, v
   p.chunk = g.chunk, p.batch = batch, p.q_heads = q_heads, p.kv_heads = kv_heads, p.mask_kind = mask_kind, p.splits = g.splits, p.scaling = scaling;
   carve(workspace, &p.counters, &p.partials);
   return launch_attn_decode_ring(p, head_dim, act_dtype == QLLM_BF16, (hipStream_t)stream);
+}
+
+// ---- the quantized KV cache (attn_decode_quant.hip, kv_quant.hip; the format: kv_quant.hpp) ------------------------------------------------
+// what both units are built for
+static int check_kv_quant_served(const char *name, int32_t head_dim, int32_t bits) {
+  if (bits != 4 && bits != 8) return set_error(QLLM_ERR_UNSUPPORTED, "%s serves 8- and 4-bit caches (got bits=%d)", name, bits);
+  if (head_dim != 64 && head_dim != 128) return set_error(QLLM_ERR_UNSUPPORTED, "%s serves head_dim 64 and 128 (got %d)", name, head_dim);
+  return QLLM_OK;
+}
+
+// the cache tensors of a call: all of them given, codes 16-byte and params 4-byte aligned, codes strides (bytes) multiples of 8 and
+// params strides (elements) multiples of 2, none negative
+static int check_kv_quant_layout(const void *const *codes, const void *const *params, int n, const int64_t *code_strides, const int64_t *param_strides) {
+  for (int i = 0; i < n; ++i)
+    if (!codes[i] || !params[i]) return set_error(QLLM_ERR_INVALID, "the codes and the params of every cache must be given (a NULL codes / params pointer)");
+  for (int i = 0; i < n; ++i)
+    if ((uintptr_t)codes[i] % 16 || (uintptr_t)params[i] % 4) return set_error(QLLM_ERR_INVALID, "codes must be 16-byte aligned and params 4-byte aligned");
+  for (int i = 0; i < 3; ++i)
+    if (code_strides[i] < 0 || code_strides[i] % 8 != 0 || param_strides[i] < 0 || param_strides[i] % 2 != 0)
+      return set_error(QLLM_ERR_INVALID, "codes strides must be non-negative multiples of 8 bytes and params strides of 2 elements (got %lld, %lld)",
+                       (long long)code_strides[i], (long long)param_strides[i]);
+  return QLLM_OK;
+}
+
+int qllm_attn_decode_quant_describe(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t bits, int64_t max_len, char *buf,
+                                    size_t buflen) {
+  clear_error();
+  if (!buf || buflen == 0) return set_error(QLLM_ERR_INVALID, "buf must not be NULL or empty");
+  int rc = check_attn_shape(batch, q_heads, kv_heads, head_dim, nullptr, max_len);
+  if (rc == QLLM_OK) rc = check_kv_quant_served("attn_decode_quant", head_dim, bits);
+  if (rc == QLLM_OK) rc = check_attn_decode_served(batch, q_heads, kv_heads, head_dim);
+  if (rc != QLLM_OK) return describe_refusal(rc, kRefused, buf, buflen);
+  const AttnDecodeGeom g = attn_decode_geom(batch, q_heads, kv_heads, head_dim, max_len);
+  snprintf(buf, buflen, "attn_decode_quant bits=%d tile=%d splits=%d chunk=%lld grid=%dx%dx%d group=%d combine=last-block", bits, g.tile, g.splits,
+           (long long)g.chunk, g.splits, kv_heads, batch, q_heads / kv_heads);
+  return QLLM_OK;
+}
+
+// qllm_attn_decode's rules in its order, the four cache tensors in the place of its two
+int qllm_attn_decode_quant(const void *q, const void *k_new, const void *v_new, void *k_codes, void *k_params, void *v_codes, void *v_params,
+                           const void *mask, void *out, int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t bits, int64_t kv_len,
+                           const int64_t *kv_len_dev, int64_t max_len, int64_t q_row_stride, int64_t q_head_stride, int64_t k_new_row_stride,
+                           int64_t k_new_head_stride, int64_t v_new_row_stride, int64_t v_new_head_stride, int64_t codes_batch_stride,
+                           int64_t codes_head_stride, int64_t codes_pos_stride, int64_t params_batch_stride, int64_t params_head_stride,
+                           int64_t params_pos_stride, int32_t mask_kind, int64_t mask_len, int64_t mask_batch_stride, float scaling, int32_t act_dtype,
+                           void *workspace, size_t workspace_bytes, void *stream) {
+  clear_error();
+  if ((k_codes || k_params || v_codes || v_params) && !(k_codes && k_params && v_codes && v_params))
+    return set_error(QLLM_ERR_INVALID, "k_codes / k_params / v_codes / v_params must all be given (got only some of the four cache tensors)");
+  int rc = check_attn_call(q, k_codes, v_codes, out, batch, q_heads, kv_heads, head_dim, nullptr, max_len, 0, act_dtype, mask_kind, mask);
+  if (rc != QLLM_OK) return rc;
+  if ((k_new == nullptr) != (v_new == nullptr)) return set_error(QLLM_ERR_INVALID, "k_new and v_new must be given together or not at all");
+  const int64_t strides[6] = {q_row_stride, q_head_stride, k_new_row_stride, k_new_head_stride, v_new_row_stride, v_new_head_stride};  // the last four count with an append only
+  const void *const ptrs[4] = {q, k_new, v_new, out};
+  rc = check_attn_layout("q / k_new / v_new / out", ptrs, 4, kv_len_dev, mask_kind, mask, "row and head", strides, k_new ? 6 : 2);
+  if (rc != QLLM_OK) return rc;
+  const void *const codes[2] = {k_codes, v_codes}, *const params[2] = {k_params, v_params};
+  const int64_t cst[3] = {codes_batch_stride, codes_head_stride, codes_pos_stride}, pst[3] = {params_batch_stride, params_head_stride, params_pos_stride};
+  rc = check_kv_quant_layout(codes, params, 2, cst, pst);
+  if (rc != QLLM_OK) return rc;
+  const int64_t need_len = kv_len_dev ? max_len : kv_len + (k_new ? 1 : 0);  // the positions a call may reach
+  if (!kv_len_dev && (kv_len < 0 || need_len > max_len))
+    return set_error(QLLM_ERR_INVALID, "kv_len%s must lie in 0..max_len (got kv_len=%lld max_len=%lld)", k_new ? " + 1 (append)" : "", (long long)kv_len, (long long)max_len);
+  if (mask && (mask_len < need_len || mask_batch_stride < 0))
+    return set_error(QLLM_ERR_INVALID, "the mask must cover %lld positions (%s) with a non-negative batch stride (got mask_len=%lld stride=%lld)", (long long)need_len,
+                     kv_len_dev ? "max_len: the length is on the device" : "kv_len, + 1 with an append", (long long)mask_len, (long long)mask_batch_stride);
+  rc = check_kv_quant_served("attn_decode_quant", head_dim, bits);
+  if (rc != QLLM_OK) return rc;
+  rc = check_attn_decode_served(batch, q_heads, kv_heads, head_dim);
+  if (rc != QLLM_OK) return rc;
+  const AttnDecodeGeom g = attn_decode_geom(batch, q_heads, kv_heads, head_dim, max_len);
+  rc = check_workspace("qllm_attn_decode_quant", workspace, workspace_bytes, kCounterBytes + g.partial_bytes);
+  if (rc != QLLM_OK) return rc;
+
+  AttnDecodeQuantParams p;
+  p.q = q, p.k_new = k_new, p.v_new = v_new, p.k_codes = k_codes, p.k_params = k_params, p.v_codes = v_codes, p.v_params = v_params, p.mask = mask, p.out = out;
+  p.kv_len_dev = kv_len_dev, p.kv_len = kv_len, p.max_len = max_len;
+  p.q_row = q_row_stride, p.q_head = q_head_stride, p.kn_row = k_new_row_stride, p.kn_head = k_new_head_stride, p.vn_row = v_new_row_stride,
+  p.vn_head = v_new_head_stride, p.mask_batch = mask_batch_stride;
+  p.c_batch = codes_batch_stride, p.c_head = codes_head_stride, p.c_pos = codes_pos_stride;
+  p.p_batch = params_batch_stride, p.p_head = params_head_stride, p.p_pos = params_pos_stride;
+  p.chunk = g.chunk, p.batch = batch, p.q_heads = q_heads, p.kv_heads = kv_heads, p.mask_kind = mask_kind, p.splits = g.splits, p.scaling = scaling;
+  carve(workspace, &p.counters, &p.partials);
+  return launch_attn_decode_quant(p, head_dim, bits, act_dtype == QLLM_BF16, (hipStream_t)stream);
+}
+
+// what qllm_kv_quantize and qllm_kv_dequantize share: `rows` the positions of the act tensor `rows_name` names
+static int check_kv_quant_call(const char *name, const void *act, const void *codes, const void *params, int32_t batch, int32_t kv_heads, int64_t rows,
+                               const char *rows_name, int32_t head_dim, int32_t bits, const int64_t *count_dev, int64_t max_len, const int64_t *act_strides,
+                               const int64_t *code_strides, const int64_t *param_strides, int32_t act_dtype) {
+  if (!act) return set_error(QLLM_ERR_INVALID, "the act-type tensor must not be NULL");
+  if (batch <= 0 || kv_heads <= 0 || head_dim <= 0 || max_len <= 0 || rows < 0)
+    return set_error(QLLM_ERR_INVALID, "batch, kv_heads, head_dim and max_len must be >= 1 and %s >= 0 (got %d, %d, %d, %lld, %lld)", rows_name, batch, kv_heads, head_dim,
+                     (long long)max_len, (long long)rows);
+  if (act_dtype != QLLM_F16 && act_dtype != QLLM_BF16) return set_error(QLLM_ERR_INVALID, "act_dtype must be QLLM_F16 or QLLM_BF16");
+  if ((uintptr_t)act % 16 || (uintptr_t)count_dev % 8) return set_error(QLLM_ERR_INVALID, "the act-type tensor must be 16-byte aligned and a device count 8-byte aligned");
+  for (int i = 0; i < 3; ++i)
+    if (act_strides[i] < 0 || act_strides[i] % 8 != 0)
+      return set_error(QLLM_ERR_INVALID, "batch, head and row strides must be non-negative multiples of 8 elements (got %lld)", (long long)act_strides[i]);
+  int rc = check_kv_quant_layout(&codes, &params, 1, code_strides, param_strides);
+  if (rc != QLLM_OK) return rc;
+  rc = check_kv_quant_served(name, head_dim, bits);
+  if (rc != QLLM_OK) return rc;
+  if ((int64_t)batch * kv_heads > (1 << 20) || rows > ((int64_t)1 << 24) || max_len > ((int64_t)1 << 24))
+    return set_error(QLLM_ERR_UNSUPPORTED, "%s serves batch * kv_heads <= 2^20 and at most 2^24 positions", name);
+  return QLLM_OK;
+}
+
+int qllm_kv_quantize(const void *src, void *codes, void *params, int32_t batch, int32_t kv_heads, int32_t rows, int32_t head_dim, int32_t bits, int64_t pos0,
+                     const int64_t *pos0_dev, int64_t max_len, int64_t src_batch_stride, int64_t src_head_stride, int64_t src_row_stride,
+                     int64_t codes_batch_stride, int64_t codes_head_stride, int64_t codes_pos_stride, int64_t params_batch_stride, int64_t params_head_stride,
+                     int64_t params_pos_stride, int32_t act_dtype, void *stream) {
+  clear_error();
+  const int64_t sst[3] = {src_batch_stride, src_head_stride, src_row_stride}, cst[3] = {codes_batch_stride, codes_head_stride, codes_pos_stride},
+                pst[3] = {params_batch_stride, params_head_stride, params_pos_stride};
+  int rc = check_kv_quant_call("kv_quantize", src, codes, params, batch, kv_heads, rows, "rows", head_dim, bits, pos0_dev, max_len, sst, cst, pst, act_dtype);
+  if (rc != QLLM_OK) return rc;
+  if (!pos0_dev && (pos0 < 0 || pos0 + rows > max_len))
+    return set_error(QLLM_ERR_INVALID, "pos0 .. pos0 + rows must lie in 0..max_len (got pos0=%lld rows=%d max_len=%lld)", (long long)pos0, rows, (long long)max_len);
+  KvQuantParams p;
+  p.src = src, p.codes = codes, p.params = params, p.dst = nullptr, p.count_dev = pos0_dev, p.count = pos0, p.max_len = max_len;
+  p.s_batch = sst[0], p.s_head = sst[1], p.s_row = sst[2], p.c_batch = cst[0], p.c_head = cst[1], p.c_pos = cst[2], p.p_batch = pst[0], p.p_head = pst[1], p.p_pos = pst[2];
+  p.batch = batch, p.kv_heads = kv_heads, p.rows = rows;
+  return launch_kv_quantize(p, head_dim, bits, act_dtype == QLLM_BF16, (hipStream_t)stream);
+}
+
+int qllm_kv_dequantize(const void *codes, const void *params, void *dst, int32_t batch, int32_t kv_heads, int32_t head_dim, int32_t bits, int64_t n,
+                       const int64_t *n_dev, int64_t max_len, int64_t dst_len, int64_t codes_batch_stride, int64_t codes_head_stride, int64_t codes_pos_stride,
+                       int64_t params_batch_stride, int64_t params_head_stride, int64_t params_pos_stride, int64_t dst_batch_stride, int64_t dst_head_stride,
+                       int64_t dst_pos_stride, int32_t act_dtype, void *stream) {
+  clear_error();
+  const int64_t dstr[3] = {dst_batch_stride, dst_head_stride, dst_pos_stride}, cst[3] = {codes_batch_stride, codes_head_stride, codes_pos_stride},
+                pst[3] = {params_batch_stride, params_head_stride, params_pos_stride};
+  int rc = check_kv_quant_call("kv_dequantize", dst, codes, params, batch, kv_heads, dst_len, "dst_len", head_dim, bits, n_dev, max_len, dstr, cst, pst, act_dtype);
+  if (rc != QLLM_OK) return rc;
+  const int64_t reach = max_len < dst_len ? max_len : dst_len;  // a device n is clamped to what both tensors hold
+  if (!n_dev && (n < 0 || n > reach))
+    return set_error(QLLM_ERR_INVALID, "n must lie in 0..min(max_len, dst_len) (got n=%lld max_len=%lld dst_len=%lld)", (long long)n, (long long)max_len, (long long)dst_len);
+  KvQuantParams p;
+  p.src = nullptr, p.codes = (void *)codes, p.params = (void *)params, p.dst = dst, p.count_dev = n_dev, p.count = n, p.max_len = reach;
+  p.s_batch = dstr[0], p.s_head = dstr[1], p.s_row = dstr[2], p.c_batch = cst[0], p.c_head = cst[1], p.c_pos = cst[2], p.p_batch = pst[0], p.p_head = pst[1], p.p_pos = pst[2];
+  p.batch = batch, p.kv_heads = kv_heads, p.rows = 0;
+  return launch_kv_dequantize(p, head_dim, bits, act_dtype == QLLM_BF16, (hipStream_t)stream);
 }
 
 // ---- prefill attention over the KV cache (attn_prefill.hip) ------------------------------------------------------------------------------

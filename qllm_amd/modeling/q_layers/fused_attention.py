@@ -34,6 +34,12 @@ for Qwen2) EXACTLY one of the three sliding layers below -- and `ops.attn_decode
                 `layer.advance(1)`: no roll, no copy of the cache, no branch on whether the layer is full, so ONE captured step serves
                 every length.  Where its plan refuses, `update` (which returns what the static sliding layer's returns) and the
                 family's route.  At prefill it is a static sliding layer: `update`, then the same call of `ops.attn_prefill`.
+  QuantStaticLayer            (modeling/quant_cache.py; the caller builds the cache: `quant_static_cache` / `to_quant`), a full-attention
+                layer of 8- or 4-bit codes, no window: at decode NO `update` -- `ops.attn_decode_quant` over the layer's four buffers in
+                place with the length from `layer.cumulative_length` on the device, the new rows quantised and stored by the kernel, then
+                `layer.advance(1)`; no row is dequantised into memory.  Where its plan refuses, `update` (which returns the valid
+                positions dequantised into the cache's scratch pair) and the family's route.  At prefill it is a static layer over that
+                scratch pair: `update`, then the same call of `ops.attn_prefill`.
 On the full layers the calls carry no `window`.  On the sliding ones a decode call carries it, but it hides nothing there: a dynamic
 sliding layer returns at most W positions and a static one holds at most W, so the lowest visible position is 0 and the windowed kernel
 reads what the kernel without a window would.  The decode window skips keys only for direct callers of `ops.attn_decode` on a linear
@@ -42,7 +48,7 @@ length from the device), and the window itself pays at prefill, where `update` r
 QLLM_FUSE_ATTENTION_SLIDING=0 puts every call that a window reaches back on the family's route.
 
 Everything else -- a window on a full layer, a sliding layer without a window or of another window, subclasses of the sliding layers,
-quantized and offloaded caches, no cache, CPU and fp32 tensors, training, output_attentions -- runs the family's own route unchanged.
+transformers' own quantized caches, offloaded caches, no cache, CPU and fp32 tensors, training, output_attentions -- runs the family's own route unchanged.
 Composes with install_fused_rope and the other installs in any order.
 Opt-in: `load_quantized(..., fuse_attention=True)`.
 
@@ -73,8 +79,10 @@ def _layer_of(past_key_values, layer_idx, uninitialized=False, sliding=None):
     DynamicSlidingWindowLayer of that window that does not record its past ("dynamic_sliding"), or exactly a StaticSlidingWindowLayer
     (initialised, or any with `uninitialized`) that holds at most W positions ("static_sliding"), unless QLLM_FUSE_ATTENTION_SLIDING=0.
     Exactly a RingSlidingWindowLayer (modeling/ring_cache.py) under the static sliding layer's conditions: "ring_sliding".
+    Without a window, exactly a QuantStaticLayer (modeling/quant_cache.py) under the static layer's conditions: "quant_static".
     Always of a cache that does not offload; a window on a full layer, a sliding layer without one and subclasses are not served."""
     from transformers.cache_utils import DynamicLayer, DynamicSlidingWindowLayer, StaticLayer, StaticSlidingWindowLayer
+    from ..quant_cache import QuantStaticLayer
     from ..ring_cache import RingSlidingWindowLayer
     layers = getattr(past_key_values, "layers", None)
     if not isinstance(layers, list) or not isinstance(layer_idx, int) or not 0 <= layer_idx < len(layers) or getattr(past_key_values, "offloading", False):
@@ -85,6 +93,8 @@ def _layer_of(past_key_values, layer_idx, uninitialized=False, sliding=None):
             return layer, "dynamic"
         if type(layer) is StaticLayer and (layer.is_initialized or uninitialized):
             return layer, "static"
+        if type(layer) is QuantStaticLayer and (layer.is_initialized or uninitialized):
+            return layer, "quant_static"
         return None, None
     if isinstance(sliding, bool) or not isinstance(sliding, int) or sliding < 1 or os.environ.get("QLLM_FUSE_ATTENTION_SLIDING", "1") == "0":
         return None, None
@@ -101,7 +111,7 @@ def _length_after_update(layer, kind, keys):
     """The number of valid positions of what `update` returned.  A static layer: its device counter.  A static sliding layer: its device
     counter while the layer has not overflowed (it stops updating the tensor from then on: the tensor is wrong and must not be used), then
     the length of what `update` returned -- all of it is valid.  A dynamic layer of either kind: the length of what `update` returned."""
-    if kind == "static" or (kind in ("static_sliding", "ring_sliding") and layer.cumulative_length_int <= layer.max_cache_len):
+    if kind in ("static", "quant_static") or (kind in ("static_sliding", "ring_sliding") and layer.cumulative_length_int <= layer.max_cache_len):
         return layer.cumulative_length
     return keys.shape[2]
 
@@ -124,7 +134,7 @@ def _gate(self, q, k, v, attention_mask, past_key_values, kwargs, window, rows, 
     layer, kind = _layer_of(past_key_values, self.layer_idx, uninitialized=uninitialized, sliding=sliding)
     if layer is None:
         return None
-    if kind in ("static", "static_sliding", "ring_sliding") and layer.is_initialized and (layer.keys.dtype != q.dtype or layer.keys.shape[0] != q.shape[0] or layer.keys.shape[3] != q.shape[3]):
+    if kind in ("static", "quant_static", "static_sliding", "ring_sliding") and layer.is_initialized and (layer.keys.dtype != q.dtype or layer.keys.shape[0] != q.shape[0] or layer.keys.shape[3] != q.shape[3]):
         return None
     return layer, kind, sliding
 
@@ -155,6 +165,8 @@ def _fused_core(self, q, k, v, attention_mask, past_key_values, kwargs, window):
         return None, k, v, False
     if served[1] == "ring_sliding":
         return _attend_ring(self, q, k, v, attention_mask, past_key_values, served[0])
+    if served[1] == "quant_static":
+        return _attend_quant(self, q, k, v, attention_mask, past_key_values, served[0])
     return _update_and_attend(self, q, k, v, attention_mask, past_key_values, *served)
 
 
@@ -171,6 +183,26 @@ def _attend_ring(self, q, k, v, attention_mask, past_key_values, layer):
     with torch.no_grad():
         out = ops.attn_decode_ring(q, layer.keys, layer.values, layer.cumulative_length, layer.max_cache_len, k_new=k, v_new=v, mask=attention_mask,
                                    scaling=self.scaling, plan=plan)
+    layer.advance(1)
+    return out, layer.keys, layer.values, True
+
+
+def _attend_quant(self, q, k, v, attention_mask, past_key_values, layer):
+    """One token on a quantized static layer: ops.attn_decode_quant over the layer's codes and params in place -- the length from
+    `layer.cumulative_length` on the device, the new rows quantised and stored by the kernel -- then `layer.advance(1)`.  The host counter
+    bounds the length: a full layer (the kernel would store nothing) is left to `update`, which refuses it.  Where the plan refuses nothing
+    has touched the cache: `update`, once, and the family's route over the dequantised scratch pair."""
+    try:
+        if layer.cumulative_length_int >= layer.max_cache_len:
+            raise ops.QllmUnsupported(0, "the layer is full")
+        plan = ops.attn_decode_quant_plan(q, layer.k_codes, layer.k_params, layer.v_codes, layer.v_params, layer.bits, layer.cumulative_length, k, v,
+                                          attention_mask)
+    except ops.QllmUnsupported:
+        keys, values = past_key_values.update(k, v, self.layer_idx)
+        return None, keys, values, True
+    with torch.no_grad():
+        out = ops.attn_decode_quant(q, layer.k_codes, layer.k_params, layer.v_codes, layer.v_params, layer.bits, layer.cumulative_length, k_new=k, v_new=v,
+                                    mask=attention_mask, scaling=self.scaling, plan=plan)
     layer.advance(1)
     return out, layer.keys, layer.values, True
 
@@ -222,7 +254,7 @@ def _rows(bound, window):
 def _prefill_routed(kind: str, masked: bool, q_len: int, behind: bool, window: Optional[int] = None) -> bool:
     """`behind`: the host knows that the layer held tokens before this call (a dynamic layer's length and a static sliding layer's
     Python counter; a static layer's length is on the device).  `window`: the call's sliding window, for the bounds written in windows."""
-    entry = PREFILL_ROUTES.get(("static_sliding" if kind == "ring_sliding" else kind, masked), (1, 0, False))
+    entry = PREFILL_ROUTES.get(({"ring_sliding": "static_sliding", "quant_static": "static"}.get(kind, kind), masked), (1, 0, False))
     ranges = entry if isinstance(entry[0], tuple) else (entry,)
     return any(q_len >= _rows(lo, window) and (hi is None or q_len <= _rows(hi, window)) and (chunks or not behind) for lo, hi, chunks in ranges)
 
@@ -244,7 +276,7 @@ def _fused_core_prefill(self, q, k, v, attention_mask, past_key_values, kwargs, 
     if served is None:
         return no
     layer, kind, sliding = served
-    static = kind in ("static", "static_sliding", "ring_sliding")
+    static = kind in ("static", "quant_static", "static_sliding", "ring_sliding")
     held = layer.is_initialized if static else layer.get_seq_length() != 0   # (a static layer: may hold tokens; its length is on the device)
     behind = layer.is_initialized and layer.cumulative_length_int != 0 if kind in ("static_sliding", "ring_sliding") else held and not static
     if not _prefill_routed(kind, attention_mask is not None, s, behind, sliding) or (attention_mask is None and held):

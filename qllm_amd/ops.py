@@ -841,6 +841,162 @@ def attn_decode_ring(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
     return out
 
 
+# ---- the quantized KV cache (csrc/kv_quant.hpp has the format; csrc/attn_decode_quant.hip, csrc/kv_quant.hip) --------------------------------
+KV_QUANT_BITS = (8, 4)
+
+
+def kv_quant_shapes(head_dim: int, bits: int):
+    """(bytes of codes, number of params) per cached row: D * bits / 8 and D / 32 scales at 8 bits, D / 16 scales-then-zeros at 4."""
+    return head_dim * bits // 8, head_dim // 32 * (2 if bits == 4 else 1)
+
+
+def _kvq_strides(t):
+    return tuple([t.stride(i) if t.shape[i] > 1 else 0 for i in range(3)])
+
+
+def _kvq_cache(no, codes, params, bits, b: int, hkv, d: int, dtype, device):
+    """(kv heads, positions, codes strides in bytes, params strides in elements) of one cache's two tensors."""
+    if isinstance(bits, bool) or bits not in KV_QUANT_BITS:
+        raise no(f"bits must be 8 or 4 (got {bits!r})")
+    if d not in ATTN_DECODE_HEAD_DIMS:
+        raise no(f"head_dim 64 or 128 (got {d})")
+    cb, np_ = kv_quant_shapes(d, bits)
+    if codes.dtype != torch.uint8 or params.dtype != dtype or codes.device != device or params.device != device:
+        raise no(f"codes must be uint8 and params {str(dtype)[6:]}, on one device (got {str(codes.dtype)[6:]}, {str(params.dtype)[6:]})")
+    if codes.dim() != 4 or params.dim() != 4 or codes.shape[:3] != params.shape[:3] or codes.shape[0] != b or codes.shape[3] != cb or params.shape[3] != np_ \
+            or (hkv is not None and codes.shape[1] != hkv) or codes.shape[1] == 0 or codes.shape[2] == 0:
+        raise no(f"codes must be [B, Hkv, L, {cb}] and params [B, Hkv, L, {np_}] with B = {b} (got {tuple(codes.shape)}, {tuple(params.shape)})")
+    cs, ps = _kvq_strides(codes), _kvq_strides(params)
+    if codes.stride(3) != 1 or params.stride(3) != 1 or [x for x in cs if x % 8 or x < 0] or [x for x in ps if x % 2 or x < 0] or codes.data_ptr() % 16 \
+            or params.data_ptr() % 4:
+        raise no(f"codes must be 16-byte aligned with strides that are multiples of 8, params 4-byte aligned with strides that are multiples of 2 "
+                 f"(got {tuple(codes.stride())}, {tuple(params.stride())})")
+    return codes.shape[1], codes.shape[2], cs, ps
+
+
+def _kvq_count(count):
+    on_device = isinstance(count, torch.Tensor)
+    return (0, count.data_ptr()) if on_device else (int(count), None)
+
+
+def _kvq_rows(no, t: torch.Tensor, name: str):
+    """(batch, kv heads, rows, head_dim, batch / head / row stride) of act rows [B, Hkv, S, D]: any view with a contiguous D."""
+    if t.dim() != 4 or t.dtype not in (torch.float16, torch.bfloat16) or 0 in t.shape[:2] or t.shape[3] == 0:
+        raise no(f"{name} must be a float16 / bfloat16 [B, Hkv, S, D] tensor (got {tuple(t.shape)} {str(t.dtype)[6:]})")
+    st = _kvq_strides(t)
+    if (t.shape[3] > 1 and t.stride(3) != 1) or [x for x in st if x % 8 or x < 0] or t.data_ptr() % 16:
+        raise no(f"{name} must be 16-byte aligned with a contiguous last dimension and strides that are multiples of 8 (got {tuple(t.stride())})")
+    return t.shape[0], t.shape[1], t.shape[2], t.shape[3], st
+
+
+def kv_quantize(src: torch.Tensor, codes: torch.Tensor, params: torch.Tensor, bits: int, pos0=0):
+    """Quantise the act rows `src` [B, Hkv, S, D] (any strided view with a contiguous D: the transposed [B, S, H, D] projection output is
+    read in place) into positions pos0 .. pos0 + S - 1 of a quantized cache (qllm_kv_quantize, csrc/kv_quant.hip).  pos0: an int, or a 0-d
+    int64 tensor on the device that the kernel reads.  No byte outside those positions is written.  QllmUnsupported before any launch."""
+    no = _attn_refusal("kv_quantize")
+    b, hkv, rows, d, st = _kvq_rows(no, src, "src")
+    _, max_len, cs, ps = _kvq_cache(no, codes, params, bits, b, hkv, d, src.dtype, src.device)
+    on_device = _attn_length_on_device(no, pos0, src)
+    if not on_device and (int(pos0) < 0 or int(pos0) + rows > max_len):
+        raise no(f"pos0 .. pos0 + {rows} must lie in 0..{max_len} (got {int(pos0)})")
+    if not src.is_cuda:
+        raise RuntimeError("kv_quantize: the tensors must be HIP/CUDA tensors (qllm_amd has no CPU forward path)")
+    pos, pos_dev = _kvq_count(pos0)
+    with torch.cuda.device(src.device):
+        rc = _lib.load().qllm_kv_quantize(src.data_ptr(), codes.data_ptr(), params.data_ptr(), b, hkv, rows, d, bits, pos, pos_dev, max_len, *st, *cs, *ps,
+                                          _act_dtype(src), _stream_ptr())
+    _lib.check(rc)
+
+
+def kv_dequantize(codes: torch.Tensor, params: torch.Tensor, bits: int, n, out: torch.Tensor):
+    """Positions 0 .. n - 1 of a quantized cache into `out`, act [B, Hkv, L', D] (qllm_kv_dequantize): each value s * code / fma(code, s,
+    z) in fp32, rounded once.  n: an int in 0..min(L, L'), or a 0-d int64 tensor on the device (clamped to that range).  Positions of `out`
+    at or beyond n are not written.  Returns `out`."""
+    no = _attn_refusal("kv_dequantize")
+    b, hkv, dst_len, d, st = _kvq_rows(no, out, "out")
+    _, max_len, cs, ps = _kvq_cache(no, codes, params, bits, b, hkv, d, out.dtype, out.device)
+    on_device = _attn_length_on_device(no, n, out)
+    if not on_device and not 0 <= int(n) <= min(max_len, dst_len):
+        raise no(f"n must lie in 0..{min(max_len, dst_len)} (got {int(n)})")
+    if not out.is_cuda:
+        raise RuntimeError("kv_dequantize: the tensors must be HIP/CUDA tensors (qllm_amd has no CPU forward path)")
+    cnt, cnt_dev = _kvq_count(n)
+    with torch.cuda.device(out.device):
+        rc = _lib.load().qllm_kv_dequantize(codes.data_ptr(), params.data_ptr(), out.data_ptr(), b, hkv, d, bits, cnt, cnt_dev, max_len, dst_len, *cs, *ps, *st,
+                                            _act_dtype(out), _stream_ptr())
+    _lib.check(rc)
+    return out
+
+
+def attn_decode_quant_plan(q: torch.Tensor, k_codes: torch.Tensor, k_params: torch.Tensor, v_codes: torch.Tensor, v_params: torch.Tensor, bits: int, length,
+                           k_new: Optional[torch.Tensor] = None, v_new: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None):
+    """What `attn_decode_quant` hands to qllm_attn_decode_quant -- (batch, q_heads, kv_heads, head_dim, bits, max_len, q row / head stride,
+    k_new and v_new row / head strides, codes batch / head / position stride in bytes, params likewise in elements, mask_kind, mask_len,
+    mask batch stride) -- or QllmUnsupported with the reason.  q, k_new / v_new, mask and length as `attn_decode_plan` takes them; codes
+    uint8 [B, Hkv, L, D * bits / 8] and params [B, Hkv, L, P] of q's type, K and V of one shape and layout.  Pure host code, any device."""
+    no = _attn_refusal("attn_decode_quant")
+    if (k_new is None) != (v_new is None):
+        raise no("k_new and v_new must be given together or not at all")
+    _attn_one_type_and_device(no, "q and k_new / v_new", (q,) + ((k_new, v_new) if k_new is not None else ()), mask)
+    b, hq, d, q_row, q_head = _attn_heads(q, "q")
+    hkv, max_len, cs, ps = _kvq_cache(no, k_codes, k_params, bits, b, None, d, q.dtype, q.device)
+    if _kvq_cache(no, v_codes, v_params, bits, b, hkv, d, q.dtype, q.device) != (hkv, max_len, cs, ps):
+        raise no("the K and the V cache must have one shape and layout")
+    _attn_served_heads(no, hq, hkv, d)
+    if b * hkv > ATTN_DECODE_COUNTERS or b > 65535:
+        raise no(f"batch * kv_heads <= {ATTN_DECODE_COUNTERS} (got {b * hkv})")
+    new = (0, 0, 0, 0)
+    if k_new is not None:
+        kb, kh, kd, k_row, k_head = _attn_heads(k_new, "k_new")
+        vb, vh, vd, v_row, v_head = _attn_heads(v_new, "v_new")
+        if (kb, kh, kd) != (b, hkv, d) or (vb, vh, vd) != (b, hkv, d):
+            raise no(f"k_new and v_new must be one token of [{b}, {hkv}, {d}] (got {tuple(k_new.shape)}, {tuple(v_new.shape)})")
+        new = (k_row, k_head, v_row, v_head)
+    need = max_len
+    if not _attn_length_on_device(no, length, q):
+        length = int(length)
+        need = length + (1 if k_new is not None else 0)
+        if length < 0 or need > max_len:
+            raise no(f"the length{' + 1 (append)' if k_new is not None else ''} must lie in 0..{max_len} (got {length})")
+    kind, mask_len, mask_batch = _lib.ATTN_MASK_NONE, 0, 0
+    if mask is not None:
+        m2 = mask[:, 0, 0] if mask.dim() == 4 and mask.shape[1] == 1 and mask.shape[2] == 1 else mask
+        if m2.dim() != 2 or m2.shape[0] not in (1, b) or (m2.shape[1] > 1 and m2.stride(1) != 1):
+            raise no(f"the mask must be [B, 1, 1, L] or [B, L] with B = {b} or 1 and inner stride 1 (got {tuple(mask.shape)}, strides {tuple(mask.stride())})")
+        mask_len, mask_batch = m2.shape[1], (m2.stride(0) if m2.shape[0] > 1 else 0)
+        kind = _attn_mask_kind(no, mask, q, mask_len, need, mask_batch)
+    return (b, hq, hkv, d, bits, max_len, q_row, q_head) + new + cs + ps + (kind, mask_len, mask_batch)
+
+
+def attn_decode_quant_describe(batch: int, q_heads: int, kv_heads: int, head_dim: int, bits: int, max_len: int) -> str:
+    """The launch `attn_decode_quant` makes ("attn_decode_quant bits=8 tile=64 splits=16 chunk=256 grid=16x32x1 group=1 combine=last-block"),
+    or "refused: ...".  Pure host code; the geometry is `attn_decode_describe`'s for the same shapes."""
+    return _describe("qllm_attn_decode_quant_describe", 256, int(batch), int(q_heads), int(kv_heads), int(head_dim), int(bits), int(max_len))
+
+
+def attn_decode_quant(q: torch.Tensor, k_codes: torch.Tensor, k_params: torch.Tensor, v_codes: torch.Tensor, v_params: torch.Tensor, bits: int, length,
+                      k_new: Optional[torch.Tensor] = None, v_new: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
+                      scaling: Optional[float] = None, *, out=None, plan=None):
+    """`attn_decode` over a QUANTIZED cache, read in place, as ONE kernel (qllm_attn_decode_quant, csrc/attn_decode_quant.hip): 8-bit
+    symmetric or 4-bit asymmetric codes with one scale (and zero) per 32 elements (`kv_quantize` writes the format).  q, length, mask,
+    scaling and the result [B, Hq, D] are `attn_decode`'s.  k_new / v_new: the new token's rows; the kernel quantises them, stores codes
+    and params at position `length` and attends over the dequantised row -- always attention over what the cache now holds (no
+    full-precision residual).  `attn_decode_quant_plan` says what is served; everything else raises QllmUnsupported before any launch."""
+    if plan is None:
+        plan = attn_decode_quant_plan(q, k_codes, k_params, v_codes, v_params, bits, length, k_new, v_new, mask)
+    b, hq, hkv, d, bits, max_len = plan[:6]
+    out, kv_len, kv_len_dev, scaling = _attn_call("attn_decode_quant", q, k_codes, v_codes, length, scaling, out, (b, hq, d), d)
+    lib = _lib.load()
+    with torch.cuda.device(q.device):
+        nbytes = lib.qllm_attn_decode_workspace_bytes(b, hq, hkv, d, max_len)
+        ws = workspace(q.device, nbytes)
+        rc = lib.qllm_attn_decode_quant(q.data_ptr(), _ptr(k_new), _ptr(v_new), k_codes.data_ptr(), k_params.data_ptr(), v_codes.data_ptr(), v_params.data_ptr(),
+                                        _ptr(mask), out.data_ptr(), b, hq, hkv, d, bits, kv_len, kv_len_dev, max_len, *plan[6:], scaling, _act_dtype(q),
+                                        ws.data_ptr(), ws.numel(), _stream_ptr())
+    _lib.check(rc)
+    return out
+
+
 def attn_prefill_plan(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, length, mask: Optional[torch.Tensor] = None):
     """What `attn_prefill` hands to qllm_attn_prefill for these tensors -- (batch, q_heads, kv_heads, head_dim, q_len, max_len, q batch /
     head / row stride, cache batch / head / position stride, mask_kind, mask_len, mask batch / row stride) -- or QllmUnsupported with the
