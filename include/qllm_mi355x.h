@@ -687,6 +687,33 @@ int qllm_attn_prefill_window(const void *q, const void *k_cache, const void *v_c
 int qllm_attn_prefill_describe(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t q_len, int64_t max_len, char *buf,
                                size_t buflen);
 
+/* ---- attention for a few query rows behind a long cache: split over the keys ----------------------------------------------------------------- */
+/* qllm_attn_prefill's call without a window -- the same arguments with the same meaning, the same rules in the same order -- computed by
+ * another kernel (csrc/attn_chunk.hip) for the calls qllm_attn_prefill serves badly: a few query rows (the verify step of assisted
+ * generation, a continuation chunk) behind many cached tokens.  A block owns one (batch entry, kv head, split of the key positions) and
+ * ALL R = (q_heads / kv_heads) * q_len query rows of that kv head, packed token-major (row r = i * G + g: token i of query head kvh * G + g,
+ * so the causal limit is monotone in r) and padded to 32 per wave; it stages each 64-key K / V tile once for all heads of the group and
+ * computes on MFMA as qllm_attn_prefill does.  The splits -- about two blocks per compute unit over batch * kv_heads, at most 32, at
+ * most one per key tile, a function of the shapes and the CU count alone, never of kv_len -- hand (m, l, unnormalised fp32 O) per row
+ * to the workspace; the last block of a (batch entry, kv head) to arrive combines the live splits in split order, divides, rounds once,
+ * stores and re-arms its arrival counter: the same bits on every call.  A row with no visible key stores zeros.
+ * Workspace: qllm_attn_chunk_workspace_bytes() (pure; the counter page plus the partial rows; monotone in batch and max_len), 16-byte
+ * aligned, its counter page zero before the first call (qllm_workspace_init) and zero again after every call.
+ * Errors: qllm_attn_prefill's, then QLLM_ERR_UNSUPPORTED for (q_heads / kv_heads) * q_len > 128 and for batch * kv_heads > 4096 (one
+ * counter each), then QLLM_ERR_WORKSPACE.  Every error is raised before any device work.  No host synchronisation; hipGraph-capturable.
+ * Not built: a sliding window, ring / sliding / quantized caches read directly, the cache append inside the kernel, a 16-row MFMA tile
+ * for R <= 16, R > 128.  ADDITIVE within ABI 7: probe for the symbols. */
+int qllm_attn_chunk(const void *q, const void *k_cache, const void *v_cache, const void *mask, void *out, int32_t batch, int32_t q_heads,
+                    int32_t kv_heads, int32_t head_dim, int32_t q_len, int64_t kv_len, const int64_t *kv_len_dev, int64_t max_len,
+                    int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride, int64_t cache_batch_stride, int64_t cache_head_stride,
+                    int64_t cache_pos_stride, int32_t mask_kind, int64_t mask_len, int64_t mask_batch_stride, int64_t mask_row_stride, int32_t causal,
+                    float scaling, int32_t act_dtype, void *workspace, size_t workspace_bytes, void *stream);
+size_t qllm_attn_chunk_workspace_bytes(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t q_len, int64_t max_len);
+/* What a call would launch, as text: "attn_chunk rows=64 row_tiles=2 kv_tile=64 splits=32 chunk=128 grid=32x8x1", or "refused: " and the
+ * refusal text.  Pure host code. */
+int qllm_attn_chunk_describe(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t q_len, int64_t max_len, char *buf,
+                             size_t buflen);
+
 /* ---- HQQ quantizer (ABI 7) ---------------------------------------------------------------------------------------------------------- */
 /* W[N,K] (fp16 / bf16 / fp32 by w_dtype, row-major, 16-byte aligned) -> the HQQ layer buffers: qweight i32 [K*bits/32][N], scales f16
  * [K/g][N] = fp16(1/s), zeros f16 [K/g][N] = fp16(z).  The algorithm is HQQQuant.do_quantize's (qllm/quantization/hqq/quant_hqq.py:34-36,

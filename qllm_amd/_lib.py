@@ -115,6 +115,10 @@ SIGNATURES = {
     "qllm_attn_prefill": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i64, vp, i64, i64, i64, i64, i64, i64, i64, i32, i64, i64, i64, i32,
                                     C.c_float, i32, vp]),
     "qllm_attn_prefill_describe": (C.c_int, [i32, i32, i32, i32, i32, i64, C.c_char_p, sz]),
+    "qllm_attn_chunk": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i64, vp, i64, i64, i64, i64, i64, i64, i64, i32, i64, i64, i64, i32,
+                                  C.c_float, i32, vp, sz, vp]),
+    "qllm_attn_chunk_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i64]),
+    "qllm_attn_chunk_describe": (C.c_int, [i32, i32, i32, i32, i32, i64, C.c_char_p, sz]),
     "qllm_attn_decode_window": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i64, vp, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, i32,
                                           i64, i64, C.c_float, i32, vp, sz, vp]),
     "qllm_attn_prefill_window": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i64, vp, i64, i64, i64, i64, i64, i64, i64, i64, i32, i64, i64, i64,

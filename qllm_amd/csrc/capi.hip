@@ -1375,6 +1375,30 @@ static int check_attn_prefill_served(int32_t batch, int32_t q_heads, int32_t kv_
   return QLLM_OK;
 }
 
+// the rules of a call with q_len >= 2 query rows (qllm_attn_prefill_window, qllm_attn_chunk) up to what the kernel serves: the call, the
+// causal flag, the layout, the length and the mask's reach
+static int check_attn_rows_call(const void *q, const void *k_cache, const void *v_cache, const void *mask, const void *out, int32_t batch, int32_t q_heads,
+                                int32_t kv_heads, int32_t head_dim, int32_t q_len, int64_t kv_len, const int64_t *kv_len_dev, int64_t max_len, int64_t window,
+                                int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride, int64_t cache_batch_stride, int64_t cache_head_stride,
+                                int64_t cache_pos_stride, int32_t mask_kind, int64_t mask_len, int64_t mask_batch_stride, int64_t mask_row_stride,
+                                int32_t causal, int32_t act_dtype) {
+  int rc = check_attn_call(q, k_cache, v_cache, out, batch, q_heads, kv_heads, head_dim, &q_len, max_len, window, act_dtype, mask_kind, mask);
+  if (rc != QLLM_OK) return rc;
+  if (causal != 0 && causal != 1) return set_error(QLLM_ERR_INVALID, "causal must be 0 or 1 (got %d)", causal);
+  const int64_t strides[6] = {q_batch_stride, q_head_stride, q_row_stride, cache_batch_stride, cache_head_stride, cache_pos_stride};
+  const void *const ptrs[4] = {q, k_cache, v_cache, out};
+  rc = check_attn_layout("q / k_cache / v_cache / out", ptrs, 4, kv_len_dev, mask_kind, mask, "batch, head, row and position", strides, 6);
+  if (rc != QLLM_OK) return rc;
+  if (!kv_len_dev && (kv_len < q_len || kv_len > max_len))
+    return set_error(QLLM_ERR_INVALID, "kv_len must lie in q_len..max_len (got kv_len=%lld q_len=%d max_len=%lld)", (long long)kv_len, q_len, (long long)max_len);
+  const int64_t need_len = kv_len_dev ? max_len : kv_len;  // the positions a call may reach
+  if (mask && (mask_len < need_len || mask_batch_stride < 0 || mask_row_stride < 0))
+    return set_error(QLLM_ERR_INVALID, "the mask must cover %lld positions (%s) with non-negative batch and row strides (got mask_len=%lld strides=%lld, %lld)",
+                     (long long)need_len, kv_len_dev ? "max_len: the length is on the device" : "kv_len", (long long)mask_len, (long long)mask_batch_stride,
+                     (long long)mask_row_stride);
+  return QLLM_OK;
+}
+
 int qllm_attn_prefill_describe(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t q_len, int64_t max_len, char *buf,
                                size_t buflen) {
   clear_error();
@@ -1403,20 +1427,10 @@ int qllm_attn_prefill_window(const void *q, const void *k_cache, const void *v_c
                              int64_t cache_pos_stride, int32_t mask_kind, int64_t mask_len, int64_t mask_batch_stride, int64_t mask_row_stride,
                              int32_t causal, float scaling, int32_t act_dtype, void *stream) {
   clear_error();
-  int rc = check_attn_call(q, k_cache, v_cache, out, batch, q_heads, kv_heads, head_dim, &q_len, max_len, window, act_dtype, mask_kind, mask);
+  int rc = check_attn_rows_call(q, k_cache, v_cache, mask, out, batch, q_heads, kv_heads, head_dim, q_len, kv_len, kv_len_dev, max_len, window, q_batch_stride,
+                                q_head_stride, q_row_stride, cache_batch_stride, cache_head_stride, cache_pos_stride, mask_kind, mask_len, mask_batch_stride,
+                                mask_row_stride, causal, act_dtype);
   if (rc != QLLM_OK) return rc;
-  if (causal != 0 && causal != 1) return set_error(QLLM_ERR_INVALID, "causal must be 0 or 1 (got %d)", causal);
-  const int64_t strides[6] = {q_batch_stride, q_head_stride, q_row_stride, cache_batch_stride, cache_head_stride, cache_pos_stride};
-  const void *const ptrs[4] = {q, k_cache, v_cache, out};
-  rc = check_attn_layout("q / k_cache / v_cache / out", ptrs, 4, kv_len_dev, mask_kind, mask, "batch, head, row and position", strides, 6);
-  if (rc != QLLM_OK) return rc;
-  if (!kv_len_dev && (kv_len < q_len || kv_len > max_len))
-    return set_error(QLLM_ERR_INVALID, "kv_len must lie in q_len..max_len (got kv_len=%lld q_len=%d max_len=%lld)", (long long)kv_len, q_len, (long long)max_len);
-  const int64_t need_len = kv_len_dev ? max_len : kv_len;  // the positions a call may reach
-  if (mask && (mask_len < need_len || mask_batch_stride < 0 || mask_row_stride < 0))
-    return set_error(QLLM_ERR_INVALID, "the mask must cover %lld positions (%s) with non-negative batch and row strides (got mask_len=%lld strides=%lld, %lld)",
-                     (long long)need_len, kv_len_dev ? "max_len: the length is on the device" : "kv_len", (long long)mask_len, (long long)mask_batch_stride,
-                     (long long)mask_row_stride);
   rc = check_attn_prefill_served(batch, q_heads, kv_heads, head_dim);
   if (rc != QLLM_OK) return rc;
   if (window > 0 && !causal) return set_error(QLLM_ERR_UNSUPPORTED, "attn_prefill serves a sliding window on causal calls only (got window=%lld causal=0)", (long long)window);
@@ -1428,6 +1442,67 @@ int qllm_attn_prefill_window(const void *q, const void *k_cache, const void *v_c
   p.c_pos = cache_pos_stride, p.mask_batch = mask_batch_stride, p.mask_row = mask_row_stride;
   p.batch = batch, p.q_heads = q_heads, p.kv_heads = kv_heads, p.q_len = q_len, p.mask_kind = mask_kind, p.causal = causal, p.scaling = scaling;
   return launch_attn_prefill(p, head_dim, act_dtype == QLLM_BF16, (hipStream_t)stream);
+}
+
+// ---- a few query rows behind a long cache, split over the keys (attn_chunk.hip) -----------------------------------------------------------
+// what the kernel serves: the rows of one kv head in one block, a grid of (splits, kv_heads, batch), one arrival counter per (sequence,
+// kv head) in the counter page
+static int check_attn_chunk_served(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t q_len) {
+  int rc = check_attn_served("attn_chunk", q_heads, kv_heads, head_dim);
+  if (rc != QLLM_OK) return rc;
+  if ((int64_t)(q_heads / kv_heads) * q_len > kAttnChunkMaxRows)
+    return set_error(QLLM_ERR_UNSUPPORTED, "attn_chunk serves (q_heads / kv_heads) * q_len <= %d rows per kv head (got %lld)", kAttnChunkMaxRows,
+                     (long long)(q_heads / kv_heads) * q_len);
+  if (batch > 65535 || kv_heads > 65535 || (int64_t)batch * kv_heads > (int64_t)(kCounterBytes / sizeof(int)))
+    return set_error(QLLM_ERR_UNSUPPORTED, "attn_chunk serves batch * kv_heads <= %d (got %lld)", (int)(kCounterBytes / sizeof(int)), (long long)batch * kv_heads);
+  return QLLM_OK;
+}
+
+size_t qllm_attn_chunk_workspace_bytes(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t q_len, int64_t max_len) {
+  const bool refused = check_attn_shape(batch, q_heads, kv_heads, head_dim, &q_len, max_len) != QLLM_OK ||
+                       check_attn_chunk_served(batch, q_heads, kv_heads, head_dim, q_len) != QLLM_OK;
+  clear_error();
+  return refused ? kCounterBytes : kCounterBytes + attn_chunk_geom(batch, q_heads, kv_heads, head_dim, q_len, max_len).partial_bytes;
+}
+
+int qllm_attn_chunk_describe(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t q_len, int64_t max_len, char *buf,
+                             size_t buflen) {
+  clear_error();
+  if (!buf || buflen == 0) return set_error(QLLM_ERR_INVALID, "buf must not be NULL or empty");
+  int rc = check_attn_shape(batch, q_heads, kv_heads, head_dim, &q_len, max_len);
+  if (rc == QLLM_OK) rc = check_attn_chunk_served(batch, q_heads, kv_heads, head_dim, q_len);
+  if (rc != QLLM_OK) return describe_refusal(rc, kRefused, buf, buflen);
+  const AttnChunkGeom g = attn_chunk_geom(batch, q_heads, kv_heads, head_dim, q_len, max_len);
+  snprintf(buf, buflen, "attn_chunk rows=%d row_tiles=%d kv_tile=%d splits=%d chunk=%lld grid=%dx%dx%d", g.rows, g.row_tiles, kAttnChunkKvTile, g.splits,
+           (long long)g.chunk, g.splits, kv_heads, batch);
+  return QLLM_OK;
+}
+
+int qllm_attn_chunk(const void *q, const void *k_cache, const void *v_cache, const void *mask, void *out, int32_t batch, int32_t q_heads,
+                    int32_t kv_heads, int32_t head_dim, int32_t q_len, int64_t kv_len, const int64_t *kv_len_dev, int64_t max_len,
+                    int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride, int64_t cache_batch_stride, int64_t cache_head_stride,
+                    int64_t cache_pos_stride, int32_t mask_kind, int64_t mask_len, int64_t mask_batch_stride, int64_t mask_row_stride, int32_t causal,
+                    float scaling, int32_t act_dtype, void *workspace, size_t workspace_bytes, void *stream) {
+  clear_error();
+  int rc = check_attn_rows_call(q, k_cache, v_cache, mask, out, batch, q_heads, kv_heads, head_dim, q_len, kv_len, kv_len_dev, max_len, 0, q_batch_stride,
+                                q_head_stride, q_row_stride, cache_batch_stride, cache_head_stride, cache_pos_stride, mask_kind, mask_len, mask_batch_stride,
+                                mask_row_stride, causal, act_dtype);
+  if (rc != QLLM_OK) return rc;
+  rc = check_attn_chunk_served(batch, q_heads, kv_heads, head_dim, q_len);
+  if (rc != QLLM_OK) return rc;
+  const AttnChunkGeom g = attn_chunk_geom(batch, q_heads, kv_heads, head_dim, q_len, max_len);
+  rc = check_workspace("qllm_attn_chunk", workspace, workspace_bytes, kCounterBytes + g.partial_bytes);
+  if (rc != QLLM_OK) return rc;
+
+  AttnChunkParams p;
+  p.q = q, p.k_cache = k_cache, p.v_cache = v_cache, p.mask = mask, p.out = out;
+  p.kv_len_dev = kv_len_dev, p.kv_len = kv_len, p.max_len = max_len;
+  p.q_batch = q_batch_stride, p.q_head = q_head_stride, p.q_row = q_row_stride, p.c_batch = cache_batch_stride, p.c_head = cache_head_stride,
+  p.c_pos = cache_pos_stride, p.mask_batch = mask_batch_stride, p.mask_row = mask_row_stride;
+  p.chunk = g.chunk, p.batch = batch, p.q_heads = q_heads, p.kv_heads = kv_heads, p.q_len = q_len, p.mask_kind = mask_kind, p.causal = causal,
+  p.splits = g.splits, p.scaling = scaling;
+  carve(workspace, &p.counters, &p.partials);
+  return launch_attn_chunk(p, head_dim, act_dtype == QLLM_BF16, (hipStream_t)stream);
 }
 
 int qllm_dequant(const qllm_weight_t *w, void *out, int32_t out_dtype, int32_t out_transposed, void *stream) {

@@ -335,6 +335,30 @@ struct AttnPrefillParams {
 int launch_attn_prefill(const AttnPrefillParams &p, int head_dim, int act_bf16, hipStream_t stream);
 int launch_attn_prefill_window(const AttnPrefillParams &p, int head_dim, int act_bf16, hipStream_t stream);  // p.window >= 1 (attn_prefill_window.hip)
 
+// ---- attn_chunk.hip: a few query rows per sequence behind a long cache (attn_prefill's call, all rows of a kv head in one block, split over the keys)
+constexpr int kAttnChunkMaxRows = 128;  // G * q_len rows of one kv head per block: 32 per wave
+constexpr int kAttnChunkKvTile = 64;    // key positions per block step
+struct AttnChunkParams {
+  const void *q, *k_cache, *v_cache;
+  const void *mask;               // mask_kind 0: none; 1: bool bytes; 2: additive, activation type
+  void *out;                      // contiguous [batch, q_len, q_heads, head_dim]
+  const int64_t *kv_len_dev;      // NULL: kv_len
+  int64_t kv_len, max_len;
+  int64_t q_batch, q_head, q_row, c_batch, c_head, c_pos, mask_batch, mask_row;  // strides in elements
+  int64_t chunk;                  // positions per split
+  int batch, q_heads, kv_heads, q_len, mask_kind, causal, splits;
+  float scaling;
+  float *partials;                // [batch * kv_heads][splits][G * q_len][4 + head_dim] fp32: m, l, two pads, O
+  int *counters;                  // one arrival counter per (batch entry, kv head) (zero before and after the launch)
+};
+struct AttnChunkGeom {
+  int rows, row_tiles, splits;
+  int64_t chunk;
+  size_t partial_bytes;
+};
+AttnChunkGeom attn_chunk_geom(int batch, int q_heads, int kv_heads, int head_dim, int q_len, int64_t max_len);
+int launch_attn_chunk(const AttnChunkParams &p, int head_dim, int act_bf16, hipStream_t stream);
+
 // ---- native.hip (reference layouts <-> the strip-major native layout) -------------------------------------------------------
 int launch_repack_native(const qllm_weight_t &src, int zero_kind, void *qweight_out, void *scales_out, void *qzeros_out, hipStream_t stream);
 int launch_unpack_native(const qllm_weight_t &src, int dst_layout, void *qweight_out, void *scales_out, void *qzeros_out, hipStream_t stream);

@@ -154,7 +154,9 @@ def load_quantized(model_dir: str, device: Optional[str] = "cuda", torch_dtype: 
     cache -- as one kernel that reads only the valid keys (q_layers/fused_attention.py); model.fused_attentions counts the modules.
     `fuse_attention_prefill` (opt-in; implies the attention install): also the attention core of calls with two or more query tokens --
     prompts, continuation chunks, padded batches -- as one flash-attention kernel where q_layers/fused_attention.py routes them to it;
-    model.fused_attention_prefills counts the modules (0 with QLLM_FUSE_ATTENTION_PREFILL=0)."""
+    model.fused_attention_prefills counts the modules (0 with QLLM_FUSE_ATTENTION_PREFILL=0).  The value "split" is True with one route in
+    front: masked calls of a few query tokens behind cached ones (assisted generation's verify step) go to the kernel that splits the keys
+    over the device (ops.attn_chunk)."""
     import transformers
 
     hf_cfg = transformers.AutoConfig.from_pretrained(model_dir)

@@ -55,7 +55,9 @@ Opt-in: `load_quantized(..., fuse_attention=True)`.
 Prefill (q_len >= 2) runs the family's route unless the install is made with `prefill=True` (`load_quantized(...,
 fuse_attention_prefill=True)`): then `_fused_core_prefill` hands prompts, continuation chunks and padded batches to `ops.attn_prefill`
 (qllm_attn_prefill, csrc/attn_prefill.hip) under the conditions in its docstring, for the (cache layer kind, mask or none, q_len)
-combinations of `PREFILL_ROUTES`.  With the flag off nothing changes."""
+combinations of `PREFILL_ROUTES`.  With the flag off nothing changes.  `prefill="split"` is `prefill=True` with one route in front of it:
+masked calls of a few query tokens behind cached ones (`SPLIT_MAX_ROWS`, `SPLIT_KINDS`) go to `ops.attn_chunk` (qllm_attn_chunk,
+csrc/attn_chunk.hip), which holds all query rows of a kv head in one block and splits the keys over the device."""
 from __future__ import annotations
 
 import os
@@ -284,21 +286,63 @@ def _fused_core_prefill(self, q, k, v, attention_mask, past_key_values, kwargs, 
     return _update_and_attend(self, q, k, v, attention_mask, past_key_values, layer, kind, sliding)
 
 
+# What `_fused_core_split` hands to ops.attn_chunk before `_fused_core_prefill`'s routing: masked calls of 2 .. SPLIT_MAX_ROWS query tokens on
+# the layer kinds of SPLIT_KINDS (not on a layer the host knows to be empty -- a dynamic layer of length 0, a static one not yet initialised:
+# a first prompt has no long cache behind it).  The bound is set
+# from profiles/attn_chunk.md, "Module routing" (tools/attn_chunk_bench.py): a (kind, rows) region where the kernel does not beat BOTH
+# sdpa and ops.attn_prefill by more than the measured spread stays on its present route.  0: nothing is routed (the op stays opt-in).
+SPLIT_MAX_ROWS = 16
+SPLIT_KINDS = ("dynamic", "static", "quant_static")
+
+
+def _fused_core_split(self, q, k, v, attention_mask, past_key_values, kwargs, window):
+    """`_fused_core_prefill`, and in front of its routing: a call that passes its gate with 2 <= q_len <= SPLIT_MAX_ROWS, a mask and a
+    cache layer of SPLIT_KINDS that the host does not know to be empty goes to ops.attn_chunk over what `update` returned,
+    where that op's plan serves it.  Where the plan refuses, the call ends where `_fused_core_prefill` would have taken it: ops.attn_prefill
+    if PREFILL_ROUTES routes it and its plan serves it, else the family's route over the updated states.  Everything else IS
+    `_fused_core_prefill`."""
+    s = q.shape[2]
+    served = None
+    if 2 <= s <= SPLIT_MAX_ROWS and attention_mask is not None and getattr(self, "is_causal", False):
+        served = _gate(self, q, k, v, attention_mask, past_key_values, kwargs, window, s, uninitialized=True)
+    # a layer the host knows to be empty -- a dynamic layer of length 0, a static one not yet initialised -- takes a first prompt
+    if served is None or served[1] not in SPLIT_KINDS or (served[0].get_seq_length() == 0 if served[1] == "dynamic" else not served[0].is_initialized):
+        return _fused_core_prefill(self, q, k, v, attention_mask, past_key_values, kwargs, window)
+    layer, kind, _ = served
+    routed = _prefill_routed(kind, True, s, kind == "dynamic")   # `_fused_core_prefill`'s decision, taken before the cache is touched
+    keys, values = past_key_values.update(k, v, self.layer_idx)
+    length = _length_after_update(layer, kind, keys)
+    for plan_of, op in ((ops.attn_chunk_plan, ops.attn_chunk),) + (((ops.attn_prefill_plan, ops.attn_prefill),) if routed else ()):
+        try:
+            plan = plan_of(q, keys, values, length, mask=attention_mask)
+        except ops.QllmUnsupported:
+            continue
+        with torch.no_grad():
+            return op(q, keys, values, length, mask=attention_mask, causal=True, scaling=self.scaling, plan=plan), keys, values, True
+    return None, keys, values, True
+
+
 def count_fused_attention_prefill(model: torch.nn.Module) -> int:
-    """How many attention modules of `model` carry the prefill core."""
-    return sum(1 for mod in model.modules() if _CORE in mod.__dict__ and mod.__dict__[_CORE][3] is _fused_core_prefill)
+    """How many attention modules of `model` carry a prefill core (`prefill=True` or `prefill="split"`)."""
+    return sum(1 for mod in model.modules() if _CORE in mod.__dict__ and mod.__dict__[_CORE][3] in (_fused_core_prefill, _fused_core_split))
 
 
-def install_fused_attention(model: torch.nn.Module, attention_types: Optional[Iterable] = None, prefill: bool = False) -> int:
+def install_fused_attention(model: torch.nn.Module, attention_types: Optional[Iterable] = None, prefill=False) -> int:
     """Give every attention module of `model` whose class name is in fused_norm.ATTENTION_TYPES (and in `attention_types`, classes or
     names, when given) and whose forward is the one fused_rope.py restates (`_known`) that restated forward with `_fused_core` in it.  No
     transformers global is touched.  Anything else is left alone and not counted.  Returns the number of modules patched;
     QLLM_FUSE_ATTENTION=0 makes it a no-op that returns 0.  `uninstall_fused_attention` restores exactly what was there, in any order with
     `uninstall_fused_rope`.  `prefill` (opt-in, off by default): the modules get `_fused_core_prefill`, which also serves calls with two
-    or more query tokens; QLLM_FUSE_ATTENTION_PREFILL=0 turns the flag into a no-op (the decode core alone is installed)."""
+    or more query tokens; QLLM_FUSE_ATTENTION_PREFILL=0 turns the flag into a no-op (the decode core alone is installed).
+    `prefill="split"`: `prefill=True`, and in front of its routing the masked calls of a few query tokens behind cached ones go to
+    ops.attn_chunk (`_fused_core_split`: the verify step of assisted generation, a short continuation chunk)."""
     if _patching.switched_off("QLLM_FUSE_ATTENTION"):
         return 0
-    core = _fused_core_prefill if prefill and not _patching.switched_off("QLLM_FUSE_ATTENTION_PREFILL") else _fused_core
+    if not isinstance(prefill, bool) and prefill != "split":
+        raise ValueError(f"install_fused_attention: prefill must be False, True or \"split\" (got {prefill!r})")
+    core = _fused_core
+    if prefill and not _patching.switched_off("QLLM_FUSE_ATTENTION_PREFILL"):
+        core = _fused_core_split if prefill == "split" else _fused_core_prefill
     names = _patching.class_names(ATTENTION_TYPES, attention_types, intersect=True)
     n = 0
     for attn in model.modules():

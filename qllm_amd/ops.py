@@ -1005,7 +1005,16 @@ def attn_prefill_plan(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
     strides, already holding the S new rows; Hkv divides Hq, at most 8 query heads per kv head; D 64 or 128; mask None, [B, 1, S, L'] or
     [B, S, L'] (B or 1 batch rows, expanded views included), bool or of the activation type, inner stride 1; `length` an int (S..L; the mask
     covers it) or a 0-d int64 tensor on the device (the mask then covers L).  Pure host code, any device."""
-    no = _attn_refusal("attn_prefill")
+    def grid(no, b, hq, hkv, s, d):
+        if b > 65535 or hq > 65535:
+            raise no(f"batch <= 65535 and q_heads <= 65535 (got {b}, {hq})")
+    return _attn_rows_plan("attn_prefill", grid, q, k_cache, v_cache, length, mask)
+
+
+def _attn_rows_plan(name: str, served, q, k_cache, v_cache, length, mask):
+    """The plan tuple attn_prefill_plan and attn_chunk_plan share, with the refusals under `name`; `served(no, b, hq, hkv, s, d)` raises what
+    only that kernel refuses, in the place of the grid's bound."""
+    no = _attn_refusal(name)
     _attn_one_type_and_device(no, "q and the caches", (q, k_cache, v_cache), mask)
     if q.dim() != 4 or 0 in q.shape:
         raise no(f"q must be a non-empty [B, Hq, S, D] tensor or view (got {tuple(q.shape)})")
@@ -1019,8 +1028,7 @@ def attn_prefill_plan(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
         raise no(f"q must be 16-byte aligned with strides that are non-negative multiples of 8 (got {tuple(q.stride())})")
     hkv, max_len = _attn_cache_shape(no, k_cache, v_cache, b, d)
     _attn_served_heads(no, hq, hkv, d)
-    if b > 65535 or hq > 65535:
-        raise no(f"batch <= 65535 and q_heads <= 65535 (got {b}, {hq})")
+    served(no, b, hq, hkv, s, d)
     if s > max_len:
         raise no(f"the caches must hold the {s} query rows (got {max_len} positions)")
     cs = _attn_cache_strides(no, k_cache, v_cache)
@@ -1068,6 +1076,54 @@ def attn_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, 
     with torch.cuda.device(q.device):
         rc = _lib.load().qllm_attn_prefill_window(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), _ptr(mask), out.data_ptr(), b, hq, hkv, d, s,
                                                   kv_len, kv_len_dev, max_len, window, *plan[6:16], 1 if causal else 0, scaling, _act_dtype(q), _stream_ptr())
+    _lib.check(rc)
+    return out
+
+
+ATTN_CHUNK_MAX_ROWS = 128   # kAttnChunkMaxRows of csrc/kernels.hpp: the query rows of one kv head, (Hq / Hkv) * S, that a block holds
+
+
+def attn_chunk_plan(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, length, mask: Optional[torch.Tensor] = None):
+    """What `attn_chunk` hands to qllm_attn_chunk for these tensors: `attn_prefill_plan`'s tuple under its rules, or QllmUnsupported with
+    the reason.  In the place of attn_prefill's bound on the grid: (Hq / Hkv) * S <= 128 rows per kv head, batch * kv_heads <= 4096 (one
+    arrival counter each); and, last, a workspace (qllm_attn_chunk_workspace_bytes) within ops.WORKSPACE_BYTES.  Pure host code, any
+    device."""
+    def served(no, b, hq, hkv, s, d):
+        if hq // hkv * s > ATTN_CHUNK_MAX_ROWS:
+            raise no(f"at most {ATTN_CHUNK_MAX_ROWS} query rows per kv head, (Hq / Hkv) * S (got {hq // hkv * s})")
+        if b * hkv > ATTN_DECODE_COUNTERS or b > 65535:
+            raise no(f"batch * kv_heads <= {ATTN_DECODE_COUNTERS} (got {b * hkv})")
+    plan = _attn_rows_plan("attn_chunk", served, q, k_cache, v_cache, length, mask)
+    nbytes = _lib.load().qllm_attn_chunk_workspace_bytes(*plan[:6])
+    if nbytes > WORKSPACE_BYTES:
+        raise _attn_refusal("attn_chunk")(f"a workspace of at most {WORKSPACE_BYTES} bytes (these shapes need {nbytes})")
+    return plan
+
+
+def attn_chunk_describe(batch: int, q_heads: int, kv_heads: int, head_dim: int, q_len: int, max_len: int) -> str:
+    """The launch `attn_chunk` makes for these shapes ("attn_chunk rows=64 row_tiles=2 kv_tile=64 splits=32 chunk=128 grid=32x8x1"), or
+    "refused: ...".  Pure host code: a function of the shapes and the device's CU count, never of the length."""
+    return _describe("qllm_attn_chunk_describe", 256, int(batch), int(q_heads), int(kv_heads), int(head_dim), int(q_len), int(max_len))
+
+
+def attn_chunk(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, length, mask: Optional[torch.Tensor] = None, causal: bool = True,
+               scaling: Optional[float] = None, *, out=None, plan=None):
+    """`attn_prefill` without a window -- the same arguments, the same [B, S, Hq, D] output -- for a FEW query rows behind a long cache (the
+    verify step of assisted generation, a continuation chunk), as ONE kernel (qllm_attn_chunk, csrc/attn_chunk.hip): a block holds all
+    (Hq / Hkv) * S <= 128 query rows of one kv head, so a K / V tile is staged once for the whole group, and the key positions are split
+    over about two blocks per compute unit, combined by the last block to arrive in split order (the same bits on every call).  The
+    launch follows the shapes alone: with `length` a 0-d int64 tensor on the device a captured call serves every length.
+    `attn_chunk_plan` says what is served; everything else raises QllmUnsupported before anything is launched.  plan: what it returned for
+    these very arguments.  The workspace is ops.workspace's, one per (device, stream)."""
+    if plan is None:
+        plan = attn_chunk_plan(q, k_cache, v_cache, length, mask)
+    b, hq, hkv, d, s, max_len = plan[:6]
+    out, kv_len, kv_len_dev, scaling = _attn_call("attn_chunk", q, k_cache, v_cache, length, scaling, out, (b, s, hq, d), d)
+    lib = _lib.load()
+    with torch.cuda.device(q.device):
+        ws = workspace(q.device, lib.qllm_attn_chunk_workspace_bytes(b, hq, hkv, d, s, max_len))
+        rc = lib.qllm_attn_chunk(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), _ptr(mask), out.data_ptr(), b, hq, hkv, d, s, kv_len, kv_len_dev,
+                                 max_len, *plan[6:16], 1 if causal else 0, scaling, _act_dtype(q), ws.data_ptr(), ws.numel(), _stream_ptr())
     _lib.check(rc)
     return out
 
