@@ -714,6 +714,28 @@ size_t qllm_attn_chunk_workspace_bytes(int32_t batch, int32_t q_heads, int32_t k
 int qllm_attn_chunk_describe(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t q_len, int64_t max_len, char *buf,
                              size_t buflen);
 
+/* qllm_attn_chunk over a QUANTIZED cache (the format above qllm_attn_decode_quant), read in place and never written
+ * (csrc/attn_chunk_quant.hip): the same kernel text with another tile staging -- codes and params travel to registers and are dequantised,
+ * by qllm_kv_dequantize's arithmetic, on their way into LDS.  The result is, bit for bit, qllm_attn_chunk over what qllm_kv_dequantize
+ * writes for the same codes; no dequantised row reaches memory.  The caller has already stored the q_len new rows (qllm_kv_quantize) and
+ * kv_len counts them.  Arguments: qllm_attn_chunk's with the four cache tensors in the place of its two, `bits` (8 or 4), the codes'
+ * batch / head / position strides in BYTES (multiples of 8, codes 16-byte aligned) and the params' in ELEMENTS (multiples of 2, params
+ * 4-byte aligned), K and V alike.  Grid, workspace (qllm_attn_chunk_workspace_bytes) and counter page: qllm_attn_chunk's for the same
+ * shapes.  Errors: qllm_attn_chunk's in its order, the cache layout's and QLLM_ERR_UNSUPPORTED for other bits behind the mask's reach.
+ * No host synchronisation; hipGraph-capturable.  Not built: the append in this kernel, more than 128 rows per kv head, quantized ring /
+ * sliding layers.  ADDITIVE within ABI 7: probe for the symbols. */
+int qllm_attn_chunk_quant(const void *q, const void *k_codes, const void *k_params, const void *v_codes, const void *v_params, const void *mask, void *out,
+                          int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t bits, int32_t q_len, int64_t kv_len,
+                          const int64_t *kv_len_dev, int64_t max_len, int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride,
+                          int64_t codes_batch_stride, int64_t codes_head_stride, int64_t codes_pos_stride, int64_t params_batch_stride,
+                          int64_t params_head_stride, int64_t params_pos_stride, int32_t mask_kind, int64_t mask_len, int64_t mask_batch_stride,
+                          int64_t mask_row_stride, int32_t causal, float scaling, int32_t act_dtype, void *workspace, size_t workspace_bytes,
+                          void *stream);
+/* "attn_chunk_quant bits=8 rows=64 row_tiles=2 kv_tile=64 splits=32 chunk=128 grid=32x8x1" (qllm_attn_chunk_describe's line with the bits in
+ * front), or "refused: " and the refusal text.  Pure host code. */
+int qllm_attn_chunk_quant_describe(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t bits, int32_t q_len, int64_t max_len,
+                                   char *buf, size_t buflen);
+
 /* ---- HQQ quantizer (ABI 7) ---------------------------------------------------------------------------------------------------------- */
 /* W[N,K] (fp16 / bf16 / fp32 by w_dtype, row-major, 16-byte aligned) -> the HQQ layer buffers: qweight i32 [K*bits/32][N], scales f16
  * [K/g][N] = fp16(1/s), zeros f16 [K/g][N] = fp16(z).  The algorithm is HQQQuant.do_quantize's (qllm/quantization/hqq/quant_hqq.py:34-36,

@@ -36,7 +36,7 @@
 //
 // Keys hidden only by the mask or by causality ARE loaded (their weight is exactly 0): their K and V rows are assumed finite.
 //
-// Not built: a sliding window; ring, sliding and quantized caches read directly; the cache append inside the kernel; a 16-row MFMA tile
+// Not built: a sliding window; ring and sliding caches read directly (a quantized one: attn_chunk_quant.hip); the cache append inside the kernel; a 16-row MFMA tile
 // for R <= 16 (a 32-row tile is then at least half padding); R > 128; waves over key sub-ranges when NT = 1 (three of the four waves
 // then only stage); skipping, in the combine, the splits above a row's diagonal.
 #include "attn_chunk_kernel.hpp"

@@ -1505,6 +1505,61 @@ int qllm_attn_chunk(const void *q, const void *k_cache, const void *v_cache, con
   return launch_attn_chunk(p, head_dim, act_dtype == QLLM_BF16, (hipStream_t)stream);
 }
 
+// ---- the same call over a quantized cache (attn_chunk_quant.hip) ---------------------------------------------------------------------------
+int qllm_attn_chunk_quant_describe(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t bits, int32_t q_len, int64_t max_len,
+                                   char *buf, size_t buflen) {
+  clear_error();
+  if (!buf || buflen == 0) return set_error(QLLM_ERR_INVALID, "buf must not be NULL or empty");
+  int rc = check_attn_shape(batch, q_heads, kv_heads, head_dim, &q_len, max_len);
+  if (rc == QLLM_OK) rc = check_kv_quant_served("attn_chunk_quant", head_dim, bits);
+  if (rc == QLLM_OK) rc = check_attn_chunk_served(batch, q_heads, kv_heads, head_dim, q_len);
+  if (rc != QLLM_OK) return describe_refusal(rc, kRefused, buf, buflen);
+  const AttnChunkGeom g = attn_chunk_geom(batch, q_heads, kv_heads, head_dim, q_len, max_len);
+  snprintf(buf, buflen, "attn_chunk_quant bits=%d rows=%d row_tiles=%d kv_tile=%d splits=%d chunk=%lld grid=%dx%dx%d", bits, g.rows, g.row_tiles,
+           kAttnChunkKvTile, g.splits, (long long)g.chunk, g.splits, kv_heads, batch);
+  return QLLM_OK;
+}
+
+// qllm_attn_chunk's rules in its order: the rows call's with the codes in the place of the caches (16-byte aligned tensors and strides
+// that are non-negative multiples of 8 -- of bytes here -- are what check_attn_rows_call asks of a cache and what the codes need), then
+// the quantized cache's own (qllm_attn_decode_quant's), then what the two kernels serve, geometry and workspace
+int qllm_attn_chunk_quant(const void *q, const void *k_codes, const void *k_params, const void *v_codes, const void *v_params, const void *mask, void *out,
+                          int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t bits, int32_t q_len, int64_t kv_len,
+                          const int64_t *kv_len_dev, int64_t max_len, int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride,
+                          int64_t codes_batch_stride, int64_t codes_head_stride, int64_t codes_pos_stride, int64_t params_batch_stride,
+                          int64_t params_head_stride, int64_t params_pos_stride, int32_t mask_kind, int64_t mask_len, int64_t mask_batch_stride,
+                          int64_t mask_row_stride, int32_t causal, float scaling, int32_t act_dtype, void *workspace, size_t workspace_bytes,
+                          void *stream) {
+  clear_error();
+  if ((k_codes || k_params || v_codes || v_params) && !(k_codes && k_params && v_codes && v_params))
+    return set_error(QLLM_ERR_INVALID, "k_codes / k_params / v_codes / v_params must all be given (got only some of the four cache tensors)");
+  int rc = check_attn_rows_call(q, k_codes, v_codes, mask, out, batch, q_heads, kv_heads, head_dim, q_len, kv_len, kv_len_dev, max_len, 0, q_batch_stride,
+                                q_head_stride, q_row_stride, codes_batch_stride, codes_head_stride, codes_pos_stride, mask_kind, mask_len, mask_batch_stride,
+                                mask_row_stride, causal, act_dtype);
+  if (rc != QLLM_OK) return rc;
+  const void *const codes[2] = {k_codes, v_codes}, *const params[2] = {k_params, v_params};
+  const int64_t cst[3] = {codes_batch_stride, codes_head_stride, codes_pos_stride}, pst[3] = {params_batch_stride, params_head_stride, params_pos_stride};
+  rc = check_kv_quant_layout(codes, params, 2, cst, pst);
+  if (rc != QLLM_OK) return rc;
+  rc = check_kv_quant_served("attn_chunk_quant", head_dim, bits);
+  if (rc != QLLM_OK) return rc;
+  rc = check_attn_chunk_served(batch, q_heads, kv_heads, head_dim, q_len);
+  if (rc != QLLM_OK) return rc;
+  const AttnChunkGeom g = attn_chunk_geom(batch, q_heads, kv_heads, head_dim, q_len, max_len);
+  rc = check_workspace("qllm_attn_chunk_quant", workspace, workspace_bytes, kCounterBytes + g.partial_bytes);
+  if (rc != QLLM_OK) return rc;
+
+  AttnChunkQuantParams p;
+  p.q = q, p.k_cache = k_codes, p.v_cache = v_codes, p.k_params = k_params, p.v_params = v_params, p.mask = mask, p.out = out;
+  p.kv_len_dev = kv_len_dev, p.kv_len = kv_len, p.max_len = max_len;
+  p.q_batch = q_batch_stride, p.q_head = q_head_stride, p.q_row = q_row_stride, p.c_batch = cst[0], p.c_head = cst[1], p.c_pos = cst[2],
+  p.p_batch = pst[0], p.p_head = pst[1], p.p_pos = pst[2], p.mask_batch = mask_batch_stride, p.mask_row = mask_row_stride;
+  p.chunk = g.chunk, p.batch = batch, p.q_heads = q_heads, p.kv_heads = kv_heads, p.q_len = q_len, p.mask_kind = mask_kind, p.causal = causal,
+  p.splits = g.splits, p.scaling = scaling;
+  carve(workspace, &p.counters, &p.partials);
+  return launch_attn_chunk_quant(p, head_dim, bits, act_dtype == QLLM_BF16, (hipStream_t)stream);
+}
+
 int qllm_dequant(const qllm_weight_t *w, void *out, int32_t out_dtype, int32_t out_transposed, void *stream) {
   clear_error();
   int rc = validate_weight(w);

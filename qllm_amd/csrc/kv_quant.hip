@@ -60,16 +60,7 @@ __global__ __launch_bounds__(256) void kv_dequantize_kernel(const KvQuantParams 
   } else {
     codes[0] = *(const uint32_t *)crow;
   }
-  const float s = kvq_f32<BF16>(prow[0]), z = BITS == 4 ? kvq_f32<BF16>(prow[D / 32]) : 0.f;
-  float c[8];
-  kvq_codes_f32<BITS>(codes, c);
-  uint32_t w[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float lo = BITS == 4 ? __builtin_fmaf(c[2 * i], s, z) : s * c[2 * i], hi = BITS == 4 ? __builtin_fmaf(c[2 * i + 1], s, z) : s * c[2 * i + 1];
-    w[i] = kvq_act<BF16>(lo) | (kvq_act<BF16>(hi) << 16);
-  }
-  *((uint4_t *)p.dst + (b * p.s_batch + h * p.s_head + pos * p.s_row) / 8 + sub) = uint4_t{w[0], w[1], w[2], w[3]};
+  *((uint4_t *)p.dst + (b * p.s_batch + h * p.s_head + pos * p.s_row) / 8 + sub) = kvq_decode<BF16, BITS>(codes, prow[0], BITS == 4 ? prow[D / 32] : 0u);
 }
 
 template <bool QUANT, bool BF16, int D>

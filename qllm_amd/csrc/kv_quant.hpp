@@ -38,6 +38,14 @@ struct AttnDecodeQuantParams {
 // grid and workspace are attn_decode_geom's (a lane owns 8 elements here as there: the same tile, the same splits)
 int launch_attn_decode_quant(const AttnDecodeQuantParams &p, int head_dim, int bits, int act_bf16, hipStream_t stream);
 
+// attn_chunk_quant.hip: attn_chunk.hip's launch over codes.  k_cache / v_cache are the CODES and c_batch / c_head / c_pos count BYTES;
+// everything else of AttnChunkParams means what it means there (grid and workspace: attn_chunk_geom's)
+struct AttnChunkQuantParams : AttnChunkParams {
+  const void *k_params, *v_params;
+  int64_t p_batch, p_head, p_pos;  // params, in elements (K and V alike)
+};
+int launch_attn_chunk_quant(const AttnChunkQuantParams &p, int head_dim, int bits, int act_bf16, hipStream_t stream);
+
 struct KvQuantParams {
   const void *src;                // quantize: act rows [B, Hkv, rows, D]
   void *codes, *params;
@@ -128,6 +136,22 @@ __device__ __forceinline__ void kvq_codes_f32(const uint32_t (&codes)[BITS / 4],
     if constexpr (BITS == 8) c[e] = (float)(int)(int8_t)(codes[e / 4] >> (8 * (e % 4)));
     else c[e] = (float)((codes[0] >> (4 * e)) & 15u);
   }
+}
+
+// the lane's 8 codes with their group's scale and zero (act bits) -> its 8 values, each rounded once to act: what kv_dequantize writes and
+// what attn_chunk_quant.hip puts into LDS, one arithmetic for both
+template <bool BF16, int BITS>
+__device__ __forceinline__ uint4_t kvq_decode(const uint32_t (&codes)[BITS / 4], uint32_t s_raw, uint32_t z_raw) {
+  const float s = kvq_f32<BF16>(s_raw), z = BITS == 4 ? kvq_f32<BF16>(z_raw) : 0.f;
+  float c[8];
+  kvq_codes_f32<BITS>(codes, c);
+  uint32_t w[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float lo = BITS == 4 ? __builtin_fmaf(c[2 * i], s, z) : s * c[2 * i], hi = BITS == 4 ? __builtin_fmaf(c[2 * i + 1], s, z) : s * c[2 * i + 1];
+    w[i] = kvq_act<BF16>(lo) | (kvq_act<BF16>(hi) << 16);
+  }
+  return uint4_t{w[0], w[1], w[2], w[3]};
 }
 
 }  // namespace

@@ -156,7 +156,8 @@ def load_quantized(model_dir: str, device: Optional[str] = "cuda", torch_dtype: 
     prompts, continuation chunks, padded batches -- as one flash-attention kernel where q_layers/fused_attention.py routes them to it;
     model.fused_attention_prefills counts the modules (0 with QLLM_FUSE_ATTENTION_PREFILL=0).  The value "split" is True with one route in
     front: masked calls of a few query tokens behind cached ones (assisted generation's verify step) go to the kernel that splits the keys
-    over the device (ops.attn_chunk)."""
+    over the device (ops.attn_chunk).  The value "codes" is "split" with one more route in front: on a quantized static cache
+    (modeling/quant_cache.py) those calls read the codes in place (ops.attn_chunk_quant) and dequantise no row into memory."""
     import transformers
 
     hf_cfg = transformers.AutoConfig.from_pretrained(model_dir)

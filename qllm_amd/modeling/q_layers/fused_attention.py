@@ -57,7 +57,11 @@ fuse_attention_prefill=True)`): then `_fused_core_prefill` hands prompts, contin
 (qllm_attn_prefill, csrc/attn_prefill.hip) under the conditions in its docstring, for the (cache layer kind, mask or none, q_len)
 combinations of `PREFILL_ROUTES`.  With the flag off nothing changes.  `prefill="split"` is `prefill=True` with one route in front of it:
 masked calls of a few query tokens behind cached ones (`SPLIT_MAX_ROWS`, `SPLIT_KINDS`) go to `ops.attn_chunk` (qllm_attn_chunk,
-csrc/attn_chunk.hip), which holds all query rows of a kv head in one block and splits the keys over the device."""
+csrc/attn_chunk.hip), which holds all query rows of a kv head in one block and splits the keys over the device.  `prefill="codes"` is
+`prefill="split"` with one more route in front: on an initialised QuantStaticLayer those calls go to `ops.attn_chunk_quant`
+(qllm_attn_chunk_quant, csrc/attn_chunk_quant.hip) over the codes in place -- `ops.kv_quantize` of the new rows, `advance`, one attention
+kernel, no `kv_dequantize` and no write of the scratch pair (`_fused_core_codes`).  Prompts of more than SPLIT_MAX_ROWS rows on such a
+layer still go through `update`."""
 from __future__ import annotations
 
 import os
@@ -322,9 +326,42 @@ def _fused_core_split(self, q, k, v, attention_mask, past_key_values, kwargs, wi
     return None, keys, values, True
 
 
+def _fused_core_codes(self, q, k, v, attention_mask, past_key_values, kwargs, window):
+    """`_fused_core_split`, and in front of it: a call that passes its gate with 2 <= q_len <= SPLIT_MAX_ROWS and a mask on an INITIALISED
+    QuantStaticLayer that still has room for the new rows (the host counter) reads the codes in place where `ops.attn_chunk_quant_plan`
+    serves it -- the plan is taken before the cache is touched, with the length read from `layer.cumulative_length` on the device:
+    `ops.kv_quantize` of k and of v at the device counter, `layer.advance(q_len)`, then `ops.attn_chunk_quant` over the layer's four
+    buffers.  No `kv_dequantize`, and the scratch pair is not written; it is returned, as `_attend_quant` returns it.  Any refusal leaves
+    the call exactly where `_fused_core_split` takes it.  The row bound is SPLIT_MAX_ROWS: the same kernel frame, and the route replaced
+    pays two whole-cache dequantise launches besides."""
+    from ..quant_cache import _readable
+    s = q.shape[2]
+    served = None
+    if 2 <= s <= SPLIT_MAX_ROWS and attention_mask is not None and getattr(self, "is_causal", False):
+        served = _gate(self, q, k, v, attention_mask, past_key_values, kwargs, window, s)
+    if served is not None and served[1] == "quant_static" and served[0].cumulative_length_int + s <= served[0].max_cache_len:
+        layer = served[0]
+        caches = (layer.k_codes, layer.k_params, layer.v_codes, layer.v_params, layer.bits, layer.cumulative_length)
+        try:
+            plan = ops.attn_chunk_quant_plan(q, *caches, attention_mask)
+        except ops.QllmUnsupported:
+            plan = None
+        if plan is not None:
+            with torch.no_grad():
+                ops.kv_quantize(_readable(k), layer.k_codes, layer.k_params, layer.bits, layer.cumulative_length)
+                ops.kv_quantize(_readable(v), layer.v_codes, layer.v_params, layer.bits, layer.cumulative_length)
+                layer.advance(s)
+                out = ops.attn_chunk_quant(q, *caches, mask=attention_mask, causal=True, scaling=self.scaling, plan=plan)
+            return out, layer.keys, layer.values, True
+    return _fused_core_split(self, q, k, v, attention_mask, past_key_values, kwargs, window)
+
+
+_PREFILL_CORES = {True: _fused_core_prefill, "split": _fused_core_split, "codes": _fused_core_codes}
+
+
 def count_fused_attention_prefill(model: torch.nn.Module) -> int:
-    """How many attention modules of `model` carry a prefill core (`prefill=True` or `prefill="split"`)."""
-    return sum(1 for mod in model.modules() if _CORE in mod.__dict__ and mod.__dict__[_CORE][3] in (_fused_core_prefill, _fused_core_split))
+    """How many attention modules of `model` carry a prefill core (`prefill=True`, `prefill="split"` or `prefill="codes"`)."""
+    return sum(1 for mod in model.modules() if _CORE in mod.__dict__ and mod.__dict__[_CORE][3] in _PREFILL_CORES.values())
 
 
 def install_fused_attention(model: torch.nn.Module, attention_types: Optional[Iterable] = None, prefill=False) -> int:
@@ -335,14 +372,16 @@ def install_fused_attention(model: torch.nn.Module, attention_types: Optional[It
     `uninstall_fused_rope`.  `prefill` (opt-in, off by default): the modules get `_fused_core_prefill`, which also serves calls with two
     or more query tokens; QLLM_FUSE_ATTENTION_PREFILL=0 turns the flag into a no-op (the decode core alone is installed).
     `prefill="split"`: `prefill=True`, and in front of its routing the masked calls of a few query tokens behind cached ones go to
-    ops.attn_chunk (`_fused_core_split`: the verify step of assisted generation, a short continuation chunk)."""
+    ops.attn_chunk (`_fused_core_split`: the verify step of assisted generation, a short continuation chunk).  `prefill="codes"`:
+    `prefill="split"`, and in front of it those calls on a quantized static layer go to ops.attn_chunk_quant, which reads the codes in
+    place (`_fused_core_codes`)."""
     if _patching.switched_off("QLLM_FUSE_ATTENTION"):
         return 0
-    if not isinstance(prefill, bool) and prefill != "split":
-        raise ValueError(f"install_fused_attention: prefill must be False, True or \"split\" (got {prefill!r})")
+    if not isinstance(prefill, bool) and (not isinstance(prefill, str) or prefill not in _PREFILL_CORES):
+        raise ValueError(f"install_fused_attention: prefill must be False, True, \"split\" or \"codes\" (got {prefill!r})")
     core = _fused_core
     if prefill and not _patching.switched_off("QLLM_FUSE_ATTENTION_PREFILL"):
-        core = _fused_core_split if prefill == "split" else _fused_core_prefill
+        core = _PREFILL_CORES[prefill]
     names = _patching.class_names(ATTENTION_TYPES, attention_types, intersect=True)
     n = 0
     for attn in model.modules():

@@ -1011,11 +1011,13 @@ def attn_prefill_plan(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
     return _attn_rows_plan("attn_prefill", grid, q, k_cache, v_cache, length, mask)
 
 
-def _attn_rows_plan(name: str, served, q, k_cache, v_cache, length, mask):
+def _attn_rows_plan(name: str, served, q, k_cache, v_cache, length, mask, quant=None):
     """The plan tuple attn_prefill_plan and attn_chunk_plan share, with the refusals under `name`; `served(no, b, hq, hkv, s, d)` raises what
-    only that kernel refuses, in the place of the grid's bound."""
+    only that kernel refuses, in the place of the grid's bound.  `quant`: None, or (k_params, v_params, bits) of a quantized cache whose
+    codes k_cache / v_cache are -- `_kvq_cache`'s rules on both in the place of the act caches' shape and strides, and the codes' strides
+    (bytes) followed by the params' (elements) in the place of the cache strides."""
     no = _attn_refusal(name)
-    _attn_one_type_and_device(no, "q and the caches", (q, k_cache, v_cache), mask)
+    _attn_one_type_and_device(no, "q and the caches", (q, k_cache, v_cache) if quant is None else (q,), mask)
     if q.dim() != 4 or 0 in q.shape:
         raise no(f"q must be a non-empty [B, Hq, S, D] tensor or view (got {tuple(q.shape)})")
     b, hq, s, d = q.shape
@@ -1026,12 +1028,17 @@ def _attn_rows_plan(name: str, served, q, k_cache, v_cache, length, mask):
     qs = tuple(q.stride(i) if q.shape[i] > 1 else 0 for i in range(3))
     if any(x % 8 or x < 0 for x in qs) or q.data_ptr() % 16:
         raise no(f"q must be 16-byte aligned with strides that are non-negative multiples of 8 (got {tuple(q.stride())})")
-    hkv, max_len = _attn_cache_shape(no, k_cache, v_cache, b, d)
+    if quant is None:
+        hkv, max_len = _attn_cache_shape(no, k_cache, v_cache, b, d)
+    else:
+        hkv, max_len, cs, ps = _kvq_cache(no, k_cache, quant[0], quant[2], b, None, d, q.dtype, q.device)
+        if _kvq_cache(no, v_cache, quant[1], quant[2], b, hkv, d, q.dtype, q.device) != (hkv, max_len, cs, ps):
+            raise no("the K and the V cache must have one shape and layout")
     _attn_served_heads(no, hq, hkv, d)
     served(no, b, hq, hkv, s, d)
     if s > max_len:
         raise no(f"the caches must hold the {s} query rows (got {max_len} positions)")
-    cs = _attn_cache_strides(no, k_cache, v_cache)
+    cs = _attn_cache_strides(no, k_cache, v_cache) if quant is None else cs + ps
     need = max_len
     if not _attn_length_on_device(no, length, q):
         need = int(length)
@@ -1088,15 +1095,20 @@ def attn_chunk_plan(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tenso
     the reason.  In the place of attn_prefill's bound on the grid: (Hq / Hkv) * S <= 128 rows per kv head, batch * kv_heads <= 4096 (one
     arrival counter each); and, last, a workspace (qllm_attn_chunk_workspace_bytes) within ops.WORKSPACE_BYTES.  Pure host code, any
     device."""
+    return _attn_chunk_plan("attn_chunk", q, k_cache, v_cache, length, mask)
+
+
+def _attn_chunk_plan(name: str, q, k_cache, v_cache, length, mask, quant=None):
+    """attn_chunk_plan's rules under `name`, over act caches or (`quant`, `_attn_rows_plan`'s) over a quantized one."""
     def served(no, b, hq, hkv, s, d):
         if hq // hkv * s > ATTN_CHUNK_MAX_ROWS:
             raise no(f"at most {ATTN_CHUNK_MAX_ROWS} query rows per kv head, (Hq / Hkv) * S (got {hq // hkv * s})")
         if b * hkv > ATTN_DECODE_COUNTERS or b > 65535:
             raise no(f"batch * kv_heads <= {ATTN_DECODE_COUNTERS} (got {b * hkv})")
-    plan = _attn_rows_plan("attn_chunk", served, q, k_cache, v_cache, length, mask)
+    plan = _attn_rows_plan(name, served, q, k_cache, v_cache, length, mask, quant)
     nbytes = _lib.load().qllm_attn_chunk_workspace_bytes(*plan[:6])
     if nbytes > WORKSPACE_BYTES:
-        raise _attn_refusal("attn_chunk")(f"a workspace of at most {WORKSPACE_BYTES} bytes (these shapes need {nbytes})")
+        raise _attn_refusal(name)(f"a workspace of at most {WORKSPACE_BYTES} bytes (these shapes need {nbytes})")
     return plan
 
 
@@ -1124,6 +1136,44 @@ def attn_chunk(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, le
         ws = workspace(q.device, lib.qllm_attn_chunk_workspace_bytes(b, hq, hkv, d, s, max_len))
         rc = lib.qllm_attn_chunk(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), _ptr(mask), out.data_ptr(), b, hq, hkv, d, s, kv_len, kv_len_dev,
                                  max_len, *plan[6:16], 1 if causal else 0, scaling, _act_dtype(q), ws.data_ptr(), ws.numel(), _stream_ptr())
+    _lib.check(rc)
+    return out
+
+
+def attn_chunk_quant_plan(q: torch.Tensor, k_codes: torch.Tensor, k_params: torch.Tensor, v_codes: torch.Tensor, v_params: torch.Tensor, bits: int, length,
+                          mask: Optional[torch.Tensor] = None):
+    """What `attn_chunk_quant` hands to qllm_attn_chunk_quant -- (batch, q_heads, kv_heads, head_dim, bits, q_len, max_len, q batch / head /
+    row stride, codes batch / head / position stride in bytes, params likewise in elements, mask_kind, mask_len, mask batch / row stride)
+    -- or QllmUnsupported with the reason: `attn_chunk_plan`'s rules on q, length and mask, `attn_decode_quant_plan`'s on the two caches
+    (codes uint8 [B, Hkv, L, D * bits / 8] and params [B, Hkv, L, P] of q's type, K and V of one shape and layout).  Pure host code, any
+    device."""
+    plan = _attn_chunk_plan("attn_chunk_quant", q, k_codes, v_codes, length, mask, (k_params, v_params, bits))
+    return plan[:4] + (bits,) + plan[4:]
+
+
+def attn_chunk_quant_describe(batch: int, q_heads: int, kv_heads: int, head_dim: int, bits: int, q_len: int, max_len: int) -> str:
+    """The launch `attn_chunk_quant` makes ("attn_chunk_quant bits=8 rows=64 row_tiles=2 kv_tile=64 splits=32 chunk=128 grid=32x8x1"), or
+    "refused: ...".  Pure host code; the geometry is `attn_chunk_describe`'s for the same shapes."""
+    return _describe("qllm_attn_chunk_quant_describe", 256, int(batch), int(q_heads), int(kv_heads), int(head_dim), int(bits), int(q_len), int(max_len))
+
+
+def attn_chunk_quant(q: torch.Tensor, k_codes: torch.Tensor, k_params: torch.Tensor, v_codes: torch.Tensor, v_params: torch.Tensor, bits: int, length,
+                     mask: Optional[torch.Tensor] = None, causal: bool = True, scaling: Optional[float] = None, *, out=None, plan=None):
+    """`attn_chunk` over a QUANTIZED cache, read in place and never written, as ONE kernel (qllm_attn_chunk_quant,
+    csrc/attn_chunk_quant.hip): codes and params go to registers and are dequantised, by `kv_dequantize`'s arithmetic, on their way into
+    LDS -- the bits of `attn_chunk` over what `kv_dequantize` writes, with no dequantised row in memory.  The caller has already put the S
+    new rows in with `kv_quantize`, and `length` counts them.  q, length, mask, causal, scaling and the [B, S, Hq, D] result are
+    `attn_chunk`'s.  `attn_chunk_quant_plan` says what is served; everything else raises QllmUnsupported before anything is launched."""
+    if plan is None:
+        plan = attn_chunk_quant_plan(q, k_codes, k_params, v_codes, v_params, bits, length, mask)
+    b, hq, hkv, d, bits, s, max_len = plan[:7]
+    out, kv_len, kv_len_dev, scaling = _attn_call("attn_chunk_quant", q, k_codes, v_codes, length, scaling, out, (b, s, hq, d), d)
+    lib = _lib.load()
+    with torch.cuda.device(q.device):
+        ws = workspace(q.device, lib.qllm_attn_chunk_workspace_bytes(b, hq, hkv, d, s, max_len))
+        rc = lib.qllm_attn_chunk_quant(q.data_ptr(), k_codes.data_ptr(), k_params.data_ptr(), v_codes.data_ptr(), v_params.data_ptr(), _ptr(mask),
+                                       out.data_ptr(), b, hq, hkv, d, bits, s, kv_len, kv_len_dev, max_len, *plan[7:], 1 if causal else 0, scaling,
+                                       _act_dtype(q), ws.data_ptr(), ws.numel(), _stream_ptr())
     _lib.check(rc)
     return out
 
@@ -1459,4 +1509,4 @@ def unpack_native(w: QllmWeight, keep, layout: str):
 
 __all__ = ["make_weight", "linear_forward", "linear_forward_grouped", "linear_forward_permuted", "linear_forward_bitpanel", "bitpanel_describe", "linear_forward_bitgemm", "bitgemm_describe", "bitgemm_min_m", "linear_forward_bitgroup", "bitgroup_describe", "linear_forward_swiglu", "swiglu_describe", "linear_forward_residual", "linear_forward_swiglu_residual", "residual_describe", "rmsnorm", "linear_forward_rmsnorm", "rmsnorm_describe", "linear_forward_shared", "dequant", "gather_columns", "gather_describe", "unpack_qweight", "pack_qweight",
            "workspace", "QllmUnsupported", "LAYOUTS", "plan_describe", "repack_native", "unpack_native", "hqq_quantize", "gptq_quantize",
-           "gptq_quantize_static", "awq_quantize", "awq_clip_search"]
+           "gptq_quantize_static", "awq_quantize", "awq_clip_search", "attn_chunk_quant", "attn_chunk_quant_plan", "attn_chunk_quant_describe"]
