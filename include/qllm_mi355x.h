@@ -722,8 +722,8 @@ int qllm_attn_chunk_describe(int32_t batch, int32_t q_heads, int32_t kv_heads, i
  * batch / head / position strides in BYTES (multiples of 8, codes 16-byte aligned) and the params' in ELEMENTS (multiples of 2, params
  * 4-byte aligned), K and V alike.  Grid, workspace (qllm_attn_chunk_workspace_bytes) and counter page: qllm_attn_chunk's for the same
  * shapes.  Errors: qllm_attn_chunk's in its order, the cache layout's and QLLM_ERR_UNSUPPORTED for other bits behind the mask's reach.
- * No host synchronisation; hipGraph-capturable.  Not built: the append in this kernel, more than 128 rows per kv head, quantized ring /
- * sliding layers.  ADDITIVE within ABI 7: probe for the symbols. */
+ * No host synchronisation; hipGraph-capturable.  More than 128 rows per kv head: qllm_attn_prefill_quant.  Not built: the append in this
+ * kernel, quantized ring / sliding layers, fp8, int8 MFMA on the codes.  ADDITIVE within ABI 7: probe for the symbols. */
 int qllm_attn_chunk_quant(const void *q, const void *k_codes, const void *k_params, const void *v_codes, const void *v_params, const void *mask, void *out,
                           int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t bits, int32_t q_len, int64_t kv_len,
                           const int64_t *kv_len_dev, int64_t max_len, int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride,
@@ -735,6 +735,30 @@ int qllm_attn_chunk_quant(const void *q, const void *k_codes, const void *k_para
  * front), or "refused: " and the refusal text.  Pure host code. */
 int qllm_attn_chunk_quant_describe(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t bits, int32_t q_len, int64_t max_len,
                                    char *buf, size_t buflen);
+
+/* qllm_attn_prefill over a QUANTIZED cache, read in place and never written (csrc/attn_prefill_quant.hip): any q_len >= 2 -- the prompt
+ * itself, every chunk of a chunked prefill -- without dequantising a row into memory.  A kernel with its own work split: the R =
+ * (q_heads / kv_heads) * q_len query rows of a kv head are packed token-major (row r = i * G + g, as qllm_attn_chunk packs them; no bound
+ * on R) and a block of four waves owns 128 consecutive packed rows of one (batch entry, kv head), so a 64-key tile of codes, loaded and
+ * dequantised (qllm_kv_dequantize's arithmetic, one rounding, on the way into LDS), serves all query heads of the group in a block.
+ * Grid (ceil(R / 128), kv_heads, batch), a function of the shapes alone; no split over the keys, no workspace.  The arithmetic
+ * is qllm_attn_prefill's: MFMA, fp32 scores, fp32 online softmax in the log2 domain, P rounded once, one rounding at the store into the
+ * contiguous [batch, q_len, q_heads, head_dim] output; a row with no visible key stores zeros.  causal as qllm_attn_prefill: key tiles
+ * above a block's last row's diagonal are never read.  The caller has already stored the q_len new rows (qllm_kv_quantize) and kv_len
+ * counts them.  Arguments: qllm_attn_prefill's with the four cache tensors, their strides and `bits` in the caches' place, as
+ * qllm_attn_chunk_quant takes them.  Errors: qllm_attn_prefill's shared rules in its order, the cache layout's, QLLM_ERR_UNSUPPORTED for
+ * other bits or head_dim, more than 8 query heads per kv head, batch or kv_heads above 65535, R above 2^30; all before any device work.
+ * No host synchronisation; hipGraph-capturable.  Not built: the append in this kernel, a sliding window, quantized ring / sliding layers,
+ * fp8, int8 MFMA on the codes.  ADDITIVE within ABI 7: probe for the symbols. */
+int qllm_attn_prefill_quant(const void *q, const void *k_codes, const void *k_params, const void *v_codes, const void *v_params, const void *mask, void *out,
+                            int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t bits, int32_t q_len, int64_t kv_len,
+                            const int64_t *kv_len_dev, int64_t max_len, int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride,
+                            int64_t codes_batch_stride, int64_t codes_head_stride, int64_t codes_pos_stride, int64_t params_batch_stride,
+                            int64_t params_head_stride, int64_t params_pos_stride, int32_t mask_kind, int64_t mask_len, int64_t mask_batch_stride,
+                            int64_t mask_row_stride, int32_t causal, float scaling, int32_t act_dtype, void *stream);
+/* "attn_prefill_quant bits=8 tile=64 grid=4x8x1 group=4", or "refused: " and the refusal text.  Pure host code. */
+int qllm_attn_prefill_quant_describe(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t bits, int32_t q_len, int64_t max_len,
+                                     char *buf, size_t buflen);
 
 /* ---- HQQ quantizer (ABI 7) ---------------------------------------------------------------------------------------------------------- */
 /* W[N,K] (fp16 / bf16 / fp32 by w_dtype, row-major, 16-byte aligned) -> the HQQ layer buffers: qweight i32 [K*bits/32][N], scales f16

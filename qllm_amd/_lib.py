@@ -132,6 +132,8 @@ SIGNATURES = {
     "qllm_kv_dequantize": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i64, vp, i64, i64] + [i64] * 9 + [i32, vp]),
     "qllm_attn_chunk_quant": (C.c_int, [vp] * 7 + [i32] * 6 + [i64, vp, i64] + [i64] * 9 + [i32, i64, i64, i64, i32, C.c_float, i32, vp, sz, vp]),
     "qllm_attn_chunk_quant_describe": (C.c_int, [i32, i32, i32, i32, i32, i32, i64, C.c_char_p, sz]),
+    "qllm_attn_prefill_quant": (C.c_int, [vp] * 7 + [i32] * 6 + [i64, vp, i64] + [i64] * 9 + [i32, i64, i64, i64, i32, C.c_float, i32, vp]),
+    "qllm_attn_prefill_quant_describe": (C.c_int, [i32, i32, i32, i32, i32, i32, i64, C.c_char_p, sz]),
 }
 EXPORTS = tuple(SIGNATURES)
 

@@ -27,7 +27,7 @@
 // it has just formed: the DEQUANTISED new row, what every later step will see at that position.  With the length on the device and
 // kv_len + 1 > L_max nothing is stored and the first L_max positions are attended.
 //
-// Not built: a quantized ring / sliding layer, per-channel K quantisation, fp8, a prefill kernel over codes for more than 128 rows per kv head (attn_chunk_quant.hip serves the chunk shapes), a full-precision residual
+// Not built: a quantized ring / sliding layer, per-channel K quantisation, fp8, int8 MFMA on the codes (two or more query rows over codes: attn_chunk_quant.hip, attn_prefill_quant.hip), a full-precision residual
 // window, head_dim other than 64 / 128.
 #include "attn_decode_kernel.hpp"
 #include "kv_quant.hpp"

@@ -1560,6 +1560,65 @@ int qllm_attn_chunk_quant(const void *q, const void *k_codes, const void *k_para
   return launch_attn_chunk_quant(p, head_dim, bits, act_dtype == QLLM_BF16, (hipStream_t)stream);
 }
 
+// ---- prefill attention over a quantized cache, any number of rows (attn_prefill_quant.hip) -------------------------------------------------
+// what the kernel serves: the packed rows of a kv head in tiles of 128, a grid of (row tiles, kv_heads, batch)
+static int check_attn_prefill_quant_served(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t q_len) {
+  if (q_len < 2) return set_error(QLLM_ERR_UNSUPPORTED, "attn_prefill_quant serves q_len >= 2 (got %d); one token is qllm_attn_decode_quant's", q_len);
+  int rc = check_attn_served("attn_prefill_quant", q_heads, kv_heads, head_dim);
+  if (rc != QLLM_OK) return rc;
+  if (batch > 65535 || kv_heads > 65535 || (int64_t)(q_heads / kv_heads) * q_len > ((int64_t)1 << 30))
+    return set_error(QLLM_ERR_UNSUPPORTED, "attn_prefill_quant serves batch <= 65535, kv_heads <= 65535 and (q_heads / kv_heads) * q_len <= 2^30 (got %d, %d, %lld)",
+                     batch, kv_heads, (long long)(q_heads / kv_heads) * q_len);
+  return QLLM_OK;
+}
+
+int qllm_attn_prefill_quant_describe(int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t bits, int32_t q_len, int64_t max_len,
+                                     char *buf, size_t buflen) {
+  clear_error();
+  if (!buf || buflen == 0) return set_error(QLLM_ERR_INVALID, "buf must not be NULL or empty");
+  int rc = check_attn_shape(batch, q_heads, kv_heads, head_dim, &q_len, max_len);
+  if (rc == QLLM_OK) rc = check_kv_quant_served("attn_prefill_quant", head_dim, bits);
+  if (rc == QLLM_OK) rc = check_attn_prefill_quant_served(batch, q_heads, kv_heads, head_dim, q_len);
+  if (rc != QLLM_OK) return describe_refusal(rc, kRefused, buf, buflen);
+  const int group = q_heads / kv_heads;
+  snprintf(buf, buflen, "attn_prefill_quant bits=%d tile=%d grid=%dx%dx%d group=%d", bits, kAttnPrefillKvTile,
+           (int)(((int64_t)group * q_len + kAttnPrefillQTile - 1) / kAttnPrefillQTile), kv_heads, batch, group);
+  return QLLM_OK;
+}
+
+// qllm_attn_prefill's rules in its order with the codes in the place of the caches (as qllm_attn_chunk_quant takes them), then the
+// quantized cache's own, then what the kernel serves
+int qllm_attn_prefill_quant(const void *q, const void *k_codes, const void *k_params, const void *v_codes, const void *v_params, const void *mask, void *out,
+                            int32_t batch, int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t bits, int32_t q_len, int64_t kv_len,
+                            const int64_t *kv_len_dev, int64_t max_len, int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride,
+                            int64_t codes_batch_stride, int64_t codes_head_stride, int64_t codes_pos_stride, int64_t params_batch_stride,
+                            int64_t params_head_stride, int64_t params_pos_stride, int32_t mask_kind, int64_t mask_len, int64_t mask_batch_stride,
+                            int64_t mask_row_stride, int32_t causal, float scaling, int32_t act_dtype, void *stream) {
+  clear_error();
+  if ((k_codes || k_params || v_codes || v_params) && !(k_codes && k_params && v_codes && v_params))
+    return set_error(QLLM_ERR_INVALID, "k_codes / k_params / v_codes / v_params must all be given (got only some of the four cache tensors)");
+  int rc = check_attn_rows_call(q, k_codes, v_codes, mask, out, batch, q_heads, kv_heads, head_dim, q_len, kv_len, kv_len_dev, max_len, 0, q_batch_stride,
+                                q_head_stride, q_row_stride, codes_batch_stride, codes_head_stride, codes_pos_stride, mask_kind, mask_len, mask_batch_stride,
+                                mask_row_stride, causal, act_dtype);
+  if (rc != QLLM_OK) return rc;
+  const void *const codes[2] = {k_codes, v_codes}, *const params[2] = {k_params, v_params};
+  const int64_t cst[3] = {codes_batch_stride, codes_head_stride, codes_pos_stride}, pst[3] = {params_batch_stride, params_head_stride, params_pos_stride};
+  rc = check_kv_quant_layout(codes, params, 2, cst, pst);
+  if (rc != QLLM_OK) return rc;
+  rc = check_kv_quant_served("attn_prefill_quant", head_dim, bits);
+  if (rc != QLLM_OK) return rc;
+  rc = check_attn_prefill_quant_served(batch, q_heads, kv_heads, head_dim, q_len);
+  if (rc != QLLM_OK) return rc;
+
+  AttnPrefillQuantParams p;
+  p.q = q, p.k_cache = k_codes, p.v_cache = v_codes, p.k_params = k_params, p.v_params = v_params, p.mask = mask, p.out = out;
+  p.kv_len_dev = kv_len_dev, p.kv_len = kv_len, p.max_len = max_len, p.window = 0;
+  p.q_batch = q_batch_stride, p.q_head = q_head_stride, p.q_row = q_row_stride, p.c_batch = cst[0], p.c_head = cst[1], p.c_pos = cst[2],
+  p.p_batch = pst[0], p.p_head = pst[1], p.p_pos = pst[2], p.mask_batch = mask_batch_stride, p.mask_row = mask_row_stride;
+  p.batch = batch, p.q_heads = q_heads, p.kv_heads = kv_heads, p.q_len = q_len, p.mask_kind = mask_kind, p.causal = causal, p.scaling = scaling;
+  return launch_attn_prefill_quant(p, head_dim, bits, act_dtype == QLLM_BF16, (hipStream_t)stream);
+}
+
 int qllm_dequant(const qllm_weight_t *w, void *out, int32_t out_dtype, int32_t out_transposed, void *stream) {
   clear_error();
   int rc = validate_weight(w);

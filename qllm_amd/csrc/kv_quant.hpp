@@ -46,6 +46,14 @@ struct AttnChunkQuantParams : AttnChunkParams {
 };
 int launch_attn_chunk_quant(const AttnChunkQuantParams &p, int head_dim, int bits, int act_bf16, hipStream_t stream);
 
+// attn_prefill_quant.hip: attn_prefill.hip's call without a window over codes, by a kernel of its own.  k_cache / v_cache are the CODES
+// and c_batch / c_head / c_pos count BYTES; `window` is not read.  Grid: (ceil(G * q_len / kAttnPrefillQTile), kv_heads, batch)
+struct AttnPrefillQuantParams : AttnPrefillParams {
+  const void *k_params, *v_params;
+  int64_t p_batch, p_head, p_pos;  // params, in elements (K and V alike)
+};
+int launch_attn_prefill_quant(const AttnPrefillQuantParams &p, int head_dim, int bits, int act_bf16, hipStream_t stream);
+
 struct KvQuantParams {
   const void *src;                // quantize: act rows [B, Hkv, rows, D]
   void *codes, *params;
@@ -139,7 +147,7 @@ __device__ __forceinline__ void kvq_codes_f32(const uint32_t (&codes)[BITS / 4],
 }
 
 // the lane's 8 codes with their group's scale and zero (act bits) -> its 8 values, each rounded once to act: what kv_dequantize writes and
-// what attn_chunk_quant.hip puts into LDS, one arithmetic for both
+// what attn_quant_tile.hpp puts into LDS (attn_chunk_quant.hip, attn_prefill_quant.hip), one arithmetic for all
 template <bool BF16, int BITS>
 __device__ __forceinline__ uint4_t kvq_decode(const uint32_t (&codes)[BITS / 4], uint32_t s_raw, uint32_t z_raw) {
   const float s = kvq_f32<BF16>(s_raw), z = BITS == 4 ? kvq_f32<BF16>(z_raw) : 0.f;

@@ -157,7 +157,9 @@ def load_quantized(model_dir: str, device: Optional[str] = "cuda", torch_dtype: 
     model.fused_attention_prefills counts the modules (0 with QLLM_FUSE_ATTENTION_PREFILL=0).  The value "split" is True with one route in
     front: masked calls of a few query tokens behind cached ones (assisted generation's verify step) go to the kernel that splits the keys
     over the device (ops.attn_chunk).  The value "codes" is "split" with one more route in front: on a quantized static cache
-    (modeling/quant_cache.py) those calls read the codes in place (ops.attn_chunk_quant) and dequantise no row into memory."""
+    (modeling/quant_cache.py) those calls read the codes in place (ops.attn_chunk_quant) and dequantise no row into memory.  The value "codes_all" is "codes" with one more route behind that one: every
+    other call with two or more query tokens on such a cache -- the prompt, chunks of any size -- reads the codes in place too
+    (ops.attn_prefill_quant)."""
     import transformers
 
     hf_cfg = transformers.AutoConfig.from_pretrained(model_dir)

@@ -61,7 +61,9 @@ csrc/attn_chunk.hip), which holds all query rows of a kv head in one block and s
 `prefill="split"` with one more route in front: on an initialised QuantStaticLayer those calls go to `ops.attn_chunk_quant`
 (qllm_attn_chunk_quant, csrc/attn_chunk_quant.hip) over the codes in place -- `ops.kv_quantize` of the new rows, `advance`, one attention
 kernel, no `kv_dequantize` and no write of the scratch pair (`_fused_core_codes`).  Prompts of more than SPLIT_MAX_ROWS rows on such a
-layer still go through `update`."""
+layer still go through `update` there.  `prefill="codes_all"` is `prefill="codes"` with one more route behind that one: every other call
+with q_len >= 2 on a QuantStaticLayer -- the prompt, chunks of any size -- goes to `ops.attn_prefill_quant` (qllm_attn_prefill_quant,
+csrc/attn_prefill_quant.hip) over the codes in place, in the same way (`_fused_core_codes_all`)."""
 from __future__ import annotations
 
 import os
@@ -334,33 +336,72 @@ def _fused_core_codes(self, q, k, v, attention_mask, past_key_values, kwargs, wi
     buffers.  No `kv_dequantize`, and the scratch pair is not written; it is returned, as `_attend_quant` returns it.  Any refusal leaves
     the call exactly where `_fused_core_split` takes it.  The row bound is SPLIT_MAX_ROWS: the same kernel frame, and the route replaced
     pays two whole-cache dequantise launches besides."""
-    from ..quant_cache import _readable
+    return _codes_chunk(self, q, k, v, attention_mask, past_key_values, kwargs, window) or \
+        _fused_core_split(self, q, k, v, attention_mask, past_key_values, kwargs, window)
+
+
+def _codes_chunk(self, q, k, v, attention_mask, past_key_values, kwargs, window):
+    """`_fused_core_codes`'s own route: the core's tuple, or None (the cache untouched) where it does not take the call."""
     s = q.shape[2]
     served = None
     if 2 <= s <= SPLIT_MAX_ROWS and attention_mask is not None and getattr(self, "is_causal", False):
         served = _gate(self, q, k, v, attention_mask, past_key_values, kwargs, window, s)
     if served is not None and served[1] == "quant_static" and served[0].cumulative_length_int + s <= served[0].max_cache_len:
-        layer = served[0]
-        caches = (layer.k_codes, layer.k_params, layer.v_codes, layer.v_params, layer.bits, layer.cumulative_length)
-        try:
-            plan = ops.attn_chunk_quant_plan(q, *caches, attention_mask)
-        except ops.QllmUnsupported:
-            plan = None
-        if plan is not None:
-            with torch.no_grad():
-                ops.kv_quantize(_readable(k), layer.k_codes, layer.k_params, layer.bits, layer.cumulative_length)
-                ops.kv_quantize(_readable(v), layer.v_codes, layer.v_params, layer.bits, layer.cumulative_length)
-                layer.advance(s)
-                out = ops.attn_chunk_quant(q, *caches, mask=attention_mask, causal=True, scaling=self.scaling, plan=plan)
-            return out, layer.keys, layer.values, True
-    return _fused_core_split(self, q, k, v, attention_mask, past_key_values, kwargs, window)
+        return _attend_codes(self, q, k, v, attention_mask, served[0], ops.attn_chunk_quant_plan, ops.attn_chunk_quant)
+    return None
 
 
-_PREFILL_CORES = {True: _fused_core_prefill, "split": _fused_core_split, "codes": _fused_core_codes}
+def _attend_codes(self, q, k, v, attention_mask, layer, plan_of, op):
+    """On an initialised QuantStaticLayer with room for the rows: `plan_of` over the layer's four buffers before the cache is touched (None
+    where it refuses), then `ops.kv_quantize` of k and of v at the device counter, `layer.advance(q_len)` and `op` with the length on the
+    device; the scratch pair is returned unwritten."""
+    from ..quant_cache import _readable
+    caches = (layer.k_codes, layer.k_params, layer.v_codes, layer.v_params, layer.bits, layer.cumulative_length)
+    try:
+        plan = plan_of(q, *caches, attention_mask)
+    except ops.QllmUnsupported:
+        return None
+    with torch.no_grad():
+        ops.kv_quantize(_readable(k), layer.k_codes, layer.k_params, layer.bits, layer.cumulative_length)
+        ops.kv_quantize(_readable(v), layer.v_codes, layer.v_params, layer.bits, layer.cumulative_length)
+        layer.advance(q.shape[2])
+        out = op(q, *caches, mask=attention_mask, causal=True, scaling=self.scaling, plan=plan)
+    return out, layer.keys, layer.values, True
+
+
+def _fused_core_codes_all(self, q, k, v, attention_mask, past_key_values, kwargs, window):
+    """`_fused_core_codes` with one more route behind its chunk route and in front of `_fused_core_split`: EVERY call with q_len >= 2 on a
+    QuantStaticLayer -- the prompt itself, every chunk of a chunked prefill -- reads the codes in place through `ops.attn_prefill_quant`
+    (qllm_attn_prefill_quant, csrc/attn_prefill_quant.hip) instead of dequantising every valid position into the scratch pair through
+    `update`.  The route takes a call that passes `_gate` on a causal module, on a quantized static layer (initialised or not) with room
+    for the rows by the host counter, that carries a mask or meets an empty layer (sdpa's own rule for a mask-less causal call), where
+    `ops.attn_prefill_quant_plan` serves it.  An uninitialised layer is initialised by its own `lazy_initialization` first (what `update`
+    would do; no counter moves; where the plan then refuses, the layer is marked uninitialised again); the plan is taken before the cache
+    is touched.  PREFILL_ROUTES is not consulted: its bounds were measured
+    for the fp16 kernel against sdpa, and the route replaced here pays two whole-cache launches besides.  Any refusal leaves the call
+    exactly where `_fused_core_codes` takes it."""
+    took = _codes_chunk(self, q, k, v, attention_mask, past_key_values, kwargs, window)
+    s = q.shape[2]
+    if took is None and s >= 2 and getattr(self, "is_causal", False):
+        served = _gate(self, q, k, v, attention_mask, past_key_values, kwargs, window, s, uninitialized=True)
+        if served is not None and served[1] == "quant_static":
+            layer = served[0]
+            if layer.cumulative_length_int + s <= layer.max_cache_len and (attention_mask is not None or layer.cumulative_length_int == 0):
+                fresh = not layer.is_initialized
+                if fresh:
+                    layer.lazy_initialization(k, v)
+                took = _attend_codes(self, q, k, v, attention_mask, layer, ops.attn_prefill_quant_plan, ops.attn_prefill_quant)
+                if took is None and fresh:   # a refusal meets the layer as "codes" would: not initialised (`update` does it again)
+                    layer.is_initialized = False
+    return took or _fused_core_split(self, q, k, v, attention_mask, past_key_values, kwargs, window)
+
+
+_PREFILL_CORES = {True: _fused_core_prefill, "split": _fused_core_split, "codes": _fused_core_codes, "codes_all": _fused_core_codes_all}
 
 
 def count_fused_attention_prefill(model: torch.nn.Module) -> int:
-    """How many attention modules of `model` carry a prefill core (`prefill=True`, `prefill="split"` or `prefill="codes"`)."""
+    """How many attention modules of `model` carry a prefill core (`prefill=True`, `prefill="split"`, `prefill="codes"` or
+    `prefill="codes_all"`)."""
     return sum(1 for mod in model.modules() if _CORE in mod.__dict__ and mod.__dict__[_CORE][3] in _PREFILL_CORES.values())
 
 
@@ -374,11 +415,13 @@ def install_fused_attention(model: torch.nn.Module, attention_types: Optional[It
     `prefill="split"`: `prefill=True`, and in front of its routing the masked calls of a few query tokens behind cached ones go to
     ops.attn_chunk (`_fused_core_split`: the verify step of assisted generation, a short continuation chunk).  `prefill="codes"`:
     `prefill="split"`, and in front of it those calls on a quantized static layer go to ops.attn_chunk_quant, which reads the codes in
-    place (`_fused_core_codes`)."""
+    place (`_fused_core_codes`).  `prefill="codes_all"`: `prefill="codes"`, and behind its chunk route every other call with two or more
+    query tokens on a quantized static layer -- prompts, chunks of any size -- goes to ops.attn_prefill_quant over the codes in place
+    (`_fused_core_codes_all`)."""
     if _patching.switched_off("QLLM_FUSE_ATTENTION"):
         return 0
     if not isinstance(prefill, bool) and (not isinstance(prefill, str) or prefill not in _PREFILL_CORES):
-        raise ValueError(f"install_fused_attention: prefill must be False, True, \"split\" or \"codes\" (got {prefill!r})")
+        raise ValueError(f"install_fused_attention: prefill must be False, True, \"split\", \"codes\" or \"codes_all\" (got {prefill!r})")
     core = _fused_core
     if prefill and not _patching.switched_off("QLLM_FUSE_ATTENTION_PREFILL"):
         core = _PREFILL_CORES[prefill]

@@ -17,8 +17,8 @@ dequantised (`ops.kv_dequantize`); states that kernel cannot read in place (misa
 is the correctness route, not the fast path.  On CPU tensors both steps are a few lines of
 torch with the same formulas.
 
-Not built: a quantized ring / sliding layer, a dynamic quantized cache, per-channel K quantisation (KIVI), fp8, a prefill kernel that reads codes for prompts of
-more than 128 rows per kv head (the chunk shapes read them in place: csrc/attn_chunk_quant.hip; longer prompts still go through `update`), a residual full-precision window, torch.compile of the layer (it is not compileable: `update` launches ctypes kernels)."""
+Not built: a quantized ring / sliding layer, a dynamic quantized cache, per-channel K quantisation (KIVI), fp8 (prompts and chunks
+read the codes in place where the install asks for it: csrc/attn_chunk_quant.hip, csrc/attn_prefill_quant.hip; otherwise they go through `update`), a residual full-precision window, torch.compile of the layer (it is not compileable: `update` launches ctypes kernels)."""
 from __future__ import annotations
 
 import torch

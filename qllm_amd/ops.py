@@ -1178,6 +1178,45 @@ def attn_chunk_quant(q: torch.Tensor, k_codes: torch.Tensor, k_params: torch.Ten
     return out
 
 
+def attn_prefill_quant_plan(q: torch.Tensor, k_codes: torch.Tensor, k_params: torch.Tensor, v_codes: torch.Tensor, v_params: torch.Tensor, bits: int, length,
+                            mask: Optional[torch.Tensor] = None):
+    """What `attn_prefill_quant` hands to qllm_attn_prefill_quant -- `attn_chunk_quant_plan`'s tuple -- or QllmUnsupported with the reason:
+    `attn_prefill_plan`'s rules on q, length and mask, `attn_decode_quant_plan`'s on the two caches.  In the place of attn_prefill's bound
+    on the grid: batch and kv_heads <= 65535, (Hq / Hkv) * S <= 2^30.  No bound on the rows per kv head, no workspace.  Pure host code,
+    any device."""
+    def grid(no, b, hq, hkv, s, d):
+        if b > 65535 or hkv > 65535 or hq // hkv * s > 1 << 30:
+            raise no(f"batch <= 65535, kv_heads <= 65535 and (Hq / Hkv) * S <= 2^30 (got {b}, {hkv}, {hq // hkv * s})")
+    plan = _attn_rows_plan("attn_prefill_quant", grid, q, k_codes, v_codes, length, mask, (k_params, v_params, bits))
+    return plan[:4] + (bits,) + plan[4:]
+
+
+def attn_prefill_quant_describe(batch: int, q_heads: int, kv_heads: int, head_dim: int, bits: int, q_len: int, max_len: int) -> str:
+    """The launch `attn_prefill_quant` makes ("attn_prefill_quant bits=8 tile=64 grid=4x8x1 group=4": row tiles of 128 packed rows x kv
+    heads x batch), or "refused: ...".  Pure host code: a function of the shapes alone, never of the length."""
+    return _describe("qllm_attn_prefill_quant_describe", 256, int(batch), int(q_heads), int(kv_heads), int(head_dim), int(bits), int(q_len), int(max_len))
+
+
+def attn_prefill_quant(q: torch.Tensor, k_codes: torch.Tensor, k_params: torch.Tensor, v_codes: torch.Tensor, v_params: torch.Tensor, bits: int, length,
+                       mask: Optional[torch.Tensor] = None, causal: bool = True, scaling: Optional[float] = None, *, out=None, plan=None):
+    """`attn_prefill` without a window over a QUANTIZED cache, read in place and never written, as ONE kernel (qllm_attn_prefill_quant,
+    csrc/attn_prefill_quant.hip) for any S >= 2: the query rows of a kv head are packed token-major and cut into tiles of 128, so a K / V
+    tile of codes, dequantised by `kv_dequantize`'s arithmetic on its way into LDS, serves all heads of a group in a block; no dequantised
+    row reaches memory.  The caller has already put the S new rows in with `kv_quantize`, and `length` counts them.  q, length, mask,
+    causal, scaling and the [B, S, Hq, D] result are `attn_prefill`'s.  `attn_prefill_quant_plan` says what is served; everything else
+    raises QllmUnsupported before anything is launched."""
+    if plan is None:
+        plan = attn_prefill_quant_plan(q, k_codes, k_params, v_codes, v_params, bits, length, mask)
+    b, hq, hkv, d, bits, s, max_len = plan[:7]
+    out, kv_len, kv_len_dev, scaling = _attn_call("attn_prefill_quant", q, k_codes, v_codes, length, scaling, out, (b, s, hq, d), d)
+    with torch.cuda.device(q.device):
+        rc = _lib.load().qllm_attn_prefill_quant(q.data_ptr(), k_codes.data_ptr(), k_params.data_ptr(), v_codes.data_ptr(), v_params.data_ptr(), _ptr(mask),
+                                                 out.data_ptr(), b, hq, hkv, d, bits, s, kv_len, kv_len_dev, max_len, *plan[7:], 1 if causal else 0, scaling,
+                                                 _act_dtype(q), _stream_ptr())
+    _lib.check(rc)
+    return out
+
+
 def dequant(w: QllmWeight, device: torch.device, dtype=torch.float16, transposed: bool = False) -> torch.Tensor:
     """W[K,N] (or [N,K]) bit-identical to the reference's DequantizeLinearBlockWise / unpack()."""
     lib = _lib.load()
@@ -1509,4 +1548,5 @@ def unpack_native(w: QllmWeight, keep, layout: str):
 
 __all__ = ["make_weight", "linear_forward", "linear_forward_grouped", "linear_forward_permuted", "linear_forward_bitpanel", "bitpanel_describe", "linear_forward_bitgemm", "bitgemm_describe", "bitgemm_min_m", "linear_forward_bitgroup", "bitgroup_describe", "linear_forward_swiglu", "swiglu_describe", "linear_forward_residual", "linear_forward_swiglu_residual", "residual_describe", "rmsnorm", "linear_forward_rmsnorm", "rmsnorm_describe", "linear_forward_shared", "dequant", "gather_columns", "gather_describe", "unpack_qweight", "pack_qweight",
            "workspace", "QllmUnsupported", "LAYOUTS", "plan_describe", "repack_native", "unpack_native", "hqq_quantize", "gptq_quantize",
-           "gptq_quantize_static", "awq_quantize", "awq_clip_search", "attn_chunk_quant", "attn_chunk_quant_plan", "attn_chunk_quant_describe"]
+           "gptq_quantize_static", "awq_quantize", "awq_clip_search", "attn_chunk_quant", "attn_chunk_quant_plan", "attn_chunk_quant_describe",
+           "attn_prefill_quant", "attn_prefill_quant_plan", "attn_prefill_quant_describe"]
