@@ -505,6 +505,25 @@ int qllm_rope(const void *q, const void *k, const void *cos, const void *sin, vo
               int32_t k_heads, int32_t head_dim, int64_t q_row_stride, int64_t q_head_stride, int64_t k_row_stride, int64_t k_head_stride,
               int32_t cos_rows, int32_t act_dtype, void *stream);
 
+/* ---- per-head RMSNorm of q and k, then their rotary embedding (Qwen3) --------------------------------------------------------------------- */
+/* q_out = rope(norm(q; q_weight)) and k_out = rope(norm(k; k_weight)) in ONE launch (csrc/rope_qknorm.hip): Qwen3's attention puts an
+ * RMSNorm over head_dim between the q / k projection and the rotary embedding.  Per (row, head) over its head_dim elements:
+ *   rstd = rsqrt(mean(x^2) + eps) in fp32,  h = round(x * rstd),  y = round(weight * h),
+ *   out = round(round(y * cos) + round(rotate_half(y) * sin)),
+ * every rounding to act_dtype -- bit for bit qllm_rmsnorm on the heads of q and of k (M = rows * heads, K = head_dim) followed by
+ * qllm_rope, the sum of squares taken in qllm_rmsnorm's order.  Everything but q_weight, k_weight and eps is qllm_rope's argument of that
+ * name with qllm_rope's meaning: rows, strides in elements (a slice of a wider fused buffer is served), contiguous outputs, cos / sin
+ * [cos_rows, head_dim], an output that may be its input when the strides agree, k == NULL with k_heads == 0 for q alone (k_weight is
+ * then not looked at).  q_weight / k_weight: contiguous [head_dim] of act_dtype.
+ * QLLM_ERR_INVALID: whatever qllm_rope calls invalid, a NULL q_weight (k_weight with k), a weight that is not 16-byte aligned, an eps
+ * that is not finite and > 0.  QLLM_ERR_UNSUPPORTED: head_dim other than 64 / 128.  Every error is raised before any device work.  No
+ * workspace, no LDS, no host synchronisation; hipGraph-capturable.  Not built: Gemma's 1 + w norm, a norm over the whole q / k width
+ * (OLMo2), partial rotary, the norm folded into the q/k/v launch or into the attention kernels.
+ * ABI: the symbol is ADDITIVE within ABI 7 (QLLM_ABI_VERSION is unchanged): probe for it by symbol. */
+int qllm_rope_qknorm(const void *q, const void *k, const void *cos, const void *sin, void *q_out, void *k_out, const void *q_weight,
+                     const void *k_weight, float eps, int32_t rows, int32_t q_heads, int32_t k_heads, int32_t head_dim, int64_t q_row_stride,
+                     int64_t q_head_stride, int64_t k_row_stride, int64_t k_head_stride, int32_t cos_rows, int32_t act_dtype, void *stream);
+
 /* ---- single-token attention over the KV cache -------------------------------------------------------------------------------------------- */
 /* out = softmax(scaling * q K^T + mask) V for ONE query token per sequence against caches [batch, kv_heads, max_len, head_dim] of which
  * the first kv_len positions count, in ONE launch (csrc/attn_decode.hip, flash-decoding): a block owns one (batch entry, kv head, split of

@@ -108,6 +108,7 @@ SIGNATURES = {
     "qllm_linear_forward_residual": (C.c_int, [wp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "qllm_residual_describe": (C.c_int, [wp, i32, i32, C.c_char_p, sz]),
     "qllm_rope": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i64, i64, i64, i64, i32, i32, vp]),
+    "qllm_rope_qknorm": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_float, i32, i32, i32, i32, i64, i64, i64, i64, i32, i32, vp]),
     "qllm_attn_decode": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i64, vp, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, i32, i64, i64,
                                    C.c_float, i32, vp, sz, vp]),
     "qllm_attn_decode_workspace_bytes": (sz, [i32, i32, i32, i32, i64]),

@@ -1020,11 +1020,10 @@ int qllm_rmsnorm_describe(const qllm_weight_t *w, int32_t n_weights, int32_t M, 
   return describe_fused("rmsnorm", d, w, n_weights, M, buf, buflen);
 }
 
-// q_out = q * cos + rotate_half(q) * sin, k_out likewise: the rotary embedding of q and k in one launch (rope.hip)
-int qllm_rope(const void *q, const void *k, const void *cos, const void *sin, void *q_out, void *k_out, int32_t rows, int32_t q_heads, int32_t k_heads,
-              int32_t head_dim, int64_t q_row_stride, int64_t q_head_stride, int64_t k_row_stride, int64_t k_head_stride, int32_t cos_rows,
-              int32_t act_dtype, void *stream) {
-  clear_error();
+// The host rules of the rotary entries (qllm_rope, qllm_rope_qknorm), written once: the call, the layout, then what rope.hip serves.
+static int check_rope(const void *q, const void *k, const void *cos, const void *sin, void *q_out, void *k_out, int32_t rows, int32_t q_heads, int32_t k_heads,
+                      int32_t head_dim, int64_t q_row_stride, int64_t q_head_stride, int64_t k_row_stride, int64_t k_head_stride, int32_t cos_rows,
+                      int32_t act_dtype) {
   if (!q || !cos || !sin || !q_out) return set_error(QLLM_ERR_INVALID, "q / cos / sin / q_out must not be NULL");
   if (k_heads < 0 || (k_heads == 0) != (k == nullptr) || (k_heads == 0) != (k_out == nullptr))
     return set_error(QLLM_ERR_INVALID, "k and k_out must not be NULL with k_heads >= 1, and both NULL with k_heads == 0 (got k_heads=%d)", k_heads);
@@ -1044,8 +1043,36 @@ int qllm_rope(const void *q, const void *k, const void *cos, const void *sin, vo
     return set_error(QLLM_ERR_INVALID, "an output may be its input only with contiguous strides (head_stride == head_dim, row_stride == heads * head_dim)");
   if (head_dim % 16 != 0 || head_dim < 16 || head_dim > kRopeMaxHeadDim)
     return set_error(QLLM_ERR_UNSUPPORTED, "rope serves head_dim %% 16 == 0, 16 <= head_dim <= %d (got %d)", kRopeMaxHeadDim, head_dim);
+  return QLLM_OK;
+}
+
+// q_out = q * cos + rotate_half(q) * sin, k_out likewise: the rotary embedding of q and k in one launch (rope.hip)
+int qllm_rope(const void *q, const void *k, const void *cos, const void *sin, void *q_out, void *k_out, int32_t rows, int32_t q_heads, int32_t k_heads,
+              int32_t head_dim, int64_t q_row_stride, int64_t q_head_stride, int64_t k_row_stride, int64_t k_head_stride, int32_t cos_rows,
+              int32_t act_dtype, void *stream) {
+  clear_error();
+  if (int rc = check_rope(q, k, cos, sin, q_out, k_out, rows, q_heads, k_heads, head_dim, q_row_stride, q_head_stride, k_row_stride, k_head_stride, cos_rows,
+                          act_dtype))
+    return rc;
   return launch_rope(q, k, cos, sin, q_out, k_out, rows, q_heads, k_heads, head_dim, q_row_stride, q_head_stride, k_row_stride, k_head_stride, cos_rows,
                      act_dtype == QLLM_BF16, (hipStream_t)stream);
+}
+
+// q_out = rope(RMSNorm_head(q; q_weight)), k_out = rope(RMSNorm_head(k; k_weight)): Qwen3's q_norm / k_norm and the rotary embedding in one
+// launch (rope_qknorm.hip).  qllm_rope's rules, then its own: a weight per tensor, an epsilon the norm can divide by, the two head sizes.
+int qllm_rope_qknorm(const void *q, const void *k, const void *cos, const void *sin, void *q_out, void *k_out, const void *q_weight, const void *k_weight,
+                     float eps, int32_t rows, int32_t q_heads, int32_t k_heads, int32_t head_dim, int64_t q_row_stride, int64_t q_head_stride,
+                     int64_t k_row_stride, int64_t k_head_stride, int32_t cos_rows, int32_t act_dtype, void *stream) {
+  clear_error();
+  if (int rc = check_rope(q, k, cos, sin, q_out, k_out, rows, q_heads, k_heads, head_dim, q_row_stride, q_head_stride, k_row_stride, k_head_stride, cos_rows,
+                          act_dtype))
+    return rc;
+  if (!q_weight || (k && !k_weight)) return set_error(QLLM_ERR_INVALID, "q_weight, and k_weight with k, must not be NULL");
+  if ((uintptr_t)q_weight % 16 || (uintptr_t)k_weight % 16) return set_error(QLLM_ERR_INVALID, "q_weight / k_weight must be 16-byte aligned");
+  if (!(eps > 0.f) || !__builtin_isfinite(eps)) return set_error(QLLM_ERR_INVALID, "eps must be finite and > 0");
+  if (!rope_qknorm_head_dim(head_dim)) return set_error(QLLM_ERR_UNSUPPORTED, "rope_qknorm serves head_dim 64 and 128 (got %d)", head_dim);
+  return launch_rope_qknorm(q, k, cos, sin, q_out, k_out, q_weight, k_weight, eps, rows, q_heads, k_heads, head_dim, q_row_stride, q_head_stride, k_row_stride,
+                            k_head_stride, cos_rows, act_dtype == QLLM_BF16, (hipStream_t)stream);
 }
 
 // ---- attention over the KV cache: the host rules of the decode and the prefill entries, each written once -----------------------------------

@@ -288,6 +288,12 @@ constexpr int kRopeMaxHeadDim = 256;
 int launch_rope(const void *q, const void *k, const void *cos, const void *sin, void *q_out, void *k_out, int rows, int q_heads, int k_heads, int head_dim,
                 int64_t q_row_stride, int64_t q_head_stride, int64_t k_row_stride, int64_t k_head_stride, int cos_rows, int act_bf16, hipStream_t stream);
 
+// ---- rope_qknorm.hip: the per-head RMSNorm of q and of k (Qwen3's q_norm / k_norm) and their rotary embedding in one launch ----------------
+constexpr bool rope_qknorm_head_dim(int head_dim) { return head_dim == 64 || head_dim == 128; }   // what the unit instantiates
+int launch_rope_qknorm(const void *q, const void *k, const void *cos, const void *sin, void *q_out, void *k_out, const void *q_weight, const void *k_weight,
+                       float eps, int rows, int q_heads, int k_heads, int head_dim, int64_t q_row_stride, int64_t q_head_stride, int64_t k_row_stride,
+                       int64_t k_head_stride, int cos_rows, int act_bf16, hipStream_t stream);
+
 // ---- attn_decode.hip: one query token per sequence against the first kv_len positions of a KV cache (flash-decoding) ---------------------
 constexpr int kAttnDecodeMaxGroup = 8;    // query heads per kv head
 constexpr int kAttnDecodeMaxSplits = 32;  // blocks per (batch entry, kv head)

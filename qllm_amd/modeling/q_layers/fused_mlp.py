@@ -16,7 +16,7 @@ import torch
 
 from . import _patching
 
-DEFAULT_MLP_TYPES = ("LlamaMLP", "MistralMLP", "Qwen2MLP")
+DEFAULT_MLP_TYPES = ("LlamaMLP", "MistralMLP", "Qwen2MLP", "Qwen3MLP")
 _ORIGINAL = "_qllm_unfused_forward"
 
 
@@ -46,7 +46,7 @@ def _eligible(mod: torch.nn.Module, names: set, q_types: tuple) -> bool:
 
 
 def install_fused_mlp(model: torch.nn.Module, q_layer_types, mlp_types: Optional[Iterable] = None) -> int:
-    """Patch every SwiGLU MLP of `model` whose class (or class name) is in `mlp_types` -- default LlamaMLP, MistralMLP, Qwen2MLP --
+    """Patch every SwiGLU MLP of `model` whose class (or class name) is in `mlp_types` -- default LlamaMLP, MistralMLP, Qwen2MLP, Qwen3MLP --
     and whose gate_proj / up_proj / down_proj are all q_layers with a SiLU act_fn (torch.nn.SiLU, torch.nn.functional.silu, or transformers' SiLUActivation).  Returns the number of modules patched;
     QLLM_FUSE_MLP=0 makes it a no-op that returns 0.  `uninstall_fused_mlp` restores the original forwards."""
     if _patching.switched_off("QLLM_FUSE_MLP"):

@@ -29,9 +29,12 @@ from . import _patching
 from ._hip_forward import _act_tensors_ok, tensor_version
 from .fused_mlp import DEFAULT_MLP_TYPES
 
-DEFAULT_LAYER_TYPES = ("LlamaDecoderLayer", "MistralDecoderLayer", "Qwen2DecoderLayer")
-DEFAULT_NORM_TYPES = ("LlamaRMSNorm", "MistralRMSNorm", "Qwen2RMSNorm")
-ATTENTION_TYPES = tuple(f"{fam}{kind}" for fam in ("Llama", "Mistral", "Qwen2") for kind in ("Attention", "SdpaAttention", "FlashAttention2", "FlashAttention"))
+DEFAULT_LAYER_TYPES = ("LlamaDecoderLayer", "MistralDecoderLayer", "Qwen2DecoderLayer", "Qwen3DecoderLayer")
+DEFAULT_NORM_TYPES = ("LlamaRMSNorm", "MistralRMSNorm", "Qwen2RMSNorm", "Qwen3RMSNorm")
+# (a Qwen3 attention also holds q_norm / k_norm, Qwen3RMSNorms of width head_dim over [B, S, H, D]: no decoder-layer norm, so
+# install_fused_norm leaves them alone; make_quant_norm gives them ops.rmsnorm's forward, which takes any leading dimensions, and
+# fused_rope.py's restated forward reads their weight and variance_epsilon, which no install touches)
+ATTENTION_TYPES = tuple(f"{fam}{kind}" for fam in ("Llama", "Mistral", "Qwen2", "Qwen3") for kind in ("Attention", "SdpaAttention", "FlashAttention2", "FlashAttention"))
 _ORIGINAL = "_qllm_unfused_norm_forward"   # on a norm module: the instance forward it had (None: the class's)
 _PRENORM = "_qllm_prenorm"                 # on a consumer: (PreNorm, the instance forward it had or None)
 
@@ -153,7 +156,7 @@ def _pair(norm, consumers, norm_names: set, q_types: tuple):
 
 def install_fused_norm(model: torch.nn.Module, q_layer_types, layer_types: Optional[Iterable] = None) -> int:
     """Patch the decoder layers of `model` whose class (or class name) is in `layer_types` -- default LlamaDecoderLayer,
-    MistralDecoderLayer, Qwen2DecoderLayer -- and whose structure is the one this module knows: input_layernorm feeds
+    MistralDecoderLayer, Qwen2DecoderLayer, Qwen3DecoderLayer -- and whose structure is the one this module knows: input_layernorm feeds
     self_attn.{q,k,v}_proj (an attention class of those families), post_attention_layernorm feeds mlp.{gate,up}_proj (an MLP class of
     fused_mlp.DEFAULT_MLP_TYPES), every consumer a q_layer of the norm's width, the norm a module with a 1-D `weight` and a float
     `variance_epsilon`.  Anything else is not guessed at (Gemma's 1 + w norm: not on the list).  Returns the number of norms folded;

@@ -10,6 +10,10 @@ attention interface only -- with `apply_rotary` in the place of the module's fun
 (device tensors of one fp16 / bf16 type, no autograd graph being recorded, what `ops.rope_plan` serves) and the eager function of the
 attention's own module everywhere else: fp32 cos / sin, partial rotary, odd head sizes, CPU tensors, training.  The q/k/v and o_proj
 modules are called as modules, so `install_fused_norm`, `install_fused_mlp` and `install_fused_residual` compose in any order.
+Qwen3's attention is Qwen2's with an RMSNorm over head_dim (`q_norm`, `k_norm`) between the q / k projections and the rotary embedding: some
+sixteen more elementwise kernels.  There the restated forward hands the projections' outputs, the two norm weights and the epsilon to
+`ops.rope_qknorm` (qllm_rope_qknorm, csrc/rope_qknorm.hip) -- norms and embedding of q and k as ONE kernel, with every rounding of the eager
+modules -- under the same conditions, and calls the modules' own norms in front of `apply_rotary` everywhere else.
 Opt-in: `load_quantized(..., fuse_rope=True)`."""
 from __future__ import annotations
 
@@ -55,20 +59,69 @@ def apply_rotary(eager, q, k, cos, sin, unsqueeze_dim: int = 1):
         return ops.rope(q, k, cos, sin, unsqueeze_dim, plan=plan)
 
 
+def _has_qk_norm(attn) -> bool:
+    """The class puts `q_norm` / `k_norm`, RMSNorms over head_dim, between the q / k projections and the rotary embedding: Qwen3's."""
+    return type(attn).__name__.startswith("Qwen3")
+
+
+def _qk_norm_ok(attn) -> bool:
+    """q_norm and k_norm are what `_attention_forward` reads: modules with a 1-D weight of head_dim elements and a float epsilon."""
+    for n in ("q_norm", "k_norm"):
+        norm = getattr(attn, n, None)
+        w = getattr(norm, "weight", None)
+        if not (isinstance(norm, torch.nn.Module) and isinstance(w, torch.Tensor) and w.dim() == 1 and w.shape[0] == attn.head_dim
+                and isinstance(getattr(norm, "variance_epsilon", None), float)):
+            return False
+    return True
+
+
+def _qknorm_applies(attn, q, k, cos, sin):
+    """What `ops.rope_qknorm_plan` answers when `ops.rope_qknorm` computes q_norm, k_norm and the rotary embedding of this call -- device
+    tensors of one activation type, the norms' weights among them, nothing to differentiate, one epsilon, a shape and layout the entry
+    serves -- else None.  q, k: [B, H, S, D] views of the projections' outputs."""
+    wq, wk = attn.q_norm.weight, attn.k_norm.weight
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in (q, k, cos, sin, wq, wk)):
+        return None
+    return _qknorm_shape_applies(attn, q, k, cos, sin)
+
+
+def _qknorm_shape_applies(attn, q, k, cos, sin):
+    wq, wk = attn.q_norm.weight, attn.k_norm.weight
+    eps = attn.q_norm.variance_epsilon
+    if eps != attn.k_norm.variance_epsilon or not _act_tensors_ok(q, k, cos, sin, wq, wk, on_device=None):
+        return None
+    try:
+        return ops.rope_qknorm_plan(q, k, wq, wk, eps, cos, sin)
+    except ops.QllmUnsupported:
+        return None
+
+
 def _attention_forward(self, hidden_states, position_embeddings=None, attention_mask=None, past_key_values=None, **kwargs):
-    """LlamaAttention.forward / MistralAttention.forward / Qwen2Attention.forward of transformers 5 -- the ONE restatement, shared with
-    fused_attention.py -- with `apply_rotary` where install_fused_rope put it (`_ATTN`) and the fused attention core where
-    install_fused_attention put it (`_CORE`); either may be there without the other."""
+    """LlamaAttention.forward / MistralAttention.forward / Qwen2Attention.forward / Qwen3Attention.forward of transformers 5 -- the ONE
+    restatement, shared with fused_attention.py -- with `apply_rotary` where install_fused_rope put it (`_ATTN`) and the fused attention
+    core where install_fused_attention put it (`_CORE`); either may be there without the other.  Qwen3's q and k go through q_norm and
+    k_norm before the rotary embedding: with install_fused_rope, norms and embedding are ONE kernel (`ops.rope_qknorm`) where it applies,
+    and the modules' own norms followed by `apply_rotary` everywhere else."""
     rope, core = self.__dict__.get(_ATTN), self.__dict__.get(_CORE)
     _, eager_rotary, window = (rope or core)[:3]
     family = sys.modules[type(self).__module__]
     input_shape = hidden_states.shape[:-1]
     hidden_shape = (*input_shape, -1, self.head_dim)
-    query_states = self.q_proj(hidden_states).view(hidden_shape).transpose(1, 2)
-    key_states = self.k_proj(hidden_states).view(hidden_shape).transpose(1, 2)
+    query_states = self.q_proj(hidden_states).view(hidden_shape)
+    key_states = self.k_proj(hidden_states).view(hidden_shape)
     value_states = self.v_proj(hidden_states).view(hidden_shape).transpose(1, 2)
     cos, sin = position_embeddings
-    if rope is not None:
+    plan = None
+    if _has_qk_norm(self):      # Qwen3
+        plan = _qknorm_applies(self, query_states.transpose(1, 2), key_states.transpose(1, 2), cos, sin) if rope is not None else None
+        if plan is None:
+            query_states, key_states = self.q_norm(query_states), self.k_norm(key_states)
+    query_states, key_states = query_states.transpose(1, 2), key_states.transpose(1, 2)
+    if plan is not None:
+        with torch.no_grad():
+            query_states, key_states = ops.rope_qknorm(query_states, key_states, self.q_norm.weight.detach(), self.k_norm.weight.detach(),
+                                                       self.q_norm.variance_epsilon, cos, sin, plan=plan)
+    elif rope is not None:
         query_states, key_states = apply_rotary(eager_rotary, query_states, key_states, cos, sin)
     else:
         query_states, key_states = eager_rotary(query_states, key_states, cos, sin)
@@ -109,7 +162,8 @@ def _unpatch(mod, key: str) -> None:
 def _known(attn):
     """(the eager rotary function, where the sliding window comes from) of an attention module this file can restate, else None: a class of
     fused_norm.ATTENTION_TYPES whose forward has the known parameters -- hidden_states, position_embeddings, attention_mask,
-    past_key_values, **kwargs -- and nothing else, whose module holds the three globals the forward uses, and which has the attributes."""
+    past_key_values, **kwargs -- and nothing else, whose module holds the three globals the forward uses, and which has the attributes;
+    a Qwen3 class also its q_norm and k_norm (`_qk_norm_ok`)."""
     name = type(attn).__name__
     if name not in ATTENTION_TYPES:
         return None
@@ -127,8 +181,10 @@ def _known(attn):
         return None
     if not all(hasattr(attn, n) for n in ("head_dim", "layer_idx", "config", "scaling", "attention_dropout")):
         return None
-    window = "config" if name.startswith("Mistral") else "self" if name.startswith("Qwen2") else None
+    window = "config" if name.startswith("Mistral") else "self" if name.startswith(("Qwen2", "Qwen3")) else None
     if window == "self" and not hasattr(attn, "sliding_window"):
+        return None
+    if _has_qk_norm(attn) and not _qk_norm_ok(attn):
         return None
     return eager, window
 

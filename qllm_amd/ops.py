@@ -6,6 +6,7 @@ PyTorch is plumbing here (device memory, streams); all compute is in libqllm_mi3
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Optional, Sequence
 
@@ -554,6 +555,26 @@ def rope_plan(q: torch.Tensor, k: Optional[torch.Tensor], cos: torch.Tensor, sin
     return (b * s, hq, hk, d) + strides + (cos.shape[0] * s,)
 
 
+def _rope_outputs(op: str, q, k, cos, sin, unsqueeze_dim: int, out):
+    """(q_out, k_out) of `rope` / `rope_qknorm` for inputs their plan serves: new tensors as the eager call would return them, or the
+    caller's `out`, checked.  Device tensors only."""
+    for t in (q, cos, sin) + ((k,) if k is not None else ()):
+        if not t.is_cuda:
+            raise RuntimeError(f"{op}: q, k, cos and sin must be HIP/CUDA tensors (qllm_amd has no CPU forward path)")
+    if out is None:
+        q_out, k_out = torch.empty_like(q), torch.empty_like(k) if k is not None else None
+        if not all(o is None or _rope_tokens(o, unsqueeze_dim).is_contiguous() for o in (q_out, k_out)):
+            raise QllmUnsupported(_lib.QLLM_ERR_UNSUPPORTED, f"{op}: the eager result of these inputs is not token-major in memory")
+        return q_out, k_out
+    q_out, k_out = out
+    for name, o, t in (("q_out", q_out, q), ("k_out", k_out, k)):
+        if (o is None) != (t is None):
+            raise RuntimeError(f"{op}: {name} must be given exactly when its input is")
+        if t is not None and (o.shape != t.shape or o.dtype != t.dtype or o.device != t.device or not _rope_tokens(o, unsqueeze_dim).is_contiguous()):
+            raise RuntimeError(f"{op}: {name} must be a {tuple(t.shape)} {t.dtype} tensor on {t.device} that is dense and token-major in memory")
+    return q_out, k_out
+
+
 def rope(q: torch.Tensor, k: Optional[torch.Tensor], cos: torch.Tensor, sin: torch.Tensor, unsqueeze_dim: int = 1, *, out=None, plan=None):
     """(q * cos + rotate_half(q) * sin, k * cos + rotate_half(k) * sin) with cos / sin unsqueezed at `unsqueeze_dim`: transformers'
     apply_rotary_pos_emb (Llama, Mistral, Qwen2) for both tensors in ONE kernel (qllm_rope, csrc/rope.hip), bit for bit, returning tensors
@@ -563,23 +584,56 @@ def rope(q: torch.Tensor, k: Optional[torch.Tensor], cos: torch.Tensor, sin: tor
     the result would be (token-major, dense); an output may be its input when that one is laid out so.  plan: what `rope_plan` returned
     for these very arguments, for a caller that has asked already."""
     rows, hq, hk, d, q_row, q_head, k_row, k_head, cos_rows = plan if plan is not None else rope_plan(q, k, cos, sin, unsqueeze_dim)
-    for t in (q, cos, sin) + ((k,) if k is not None else ()):
-        if not t.is_cuda:
-            raise RuntimeError("rope: q, k, cos and sin must be HIP/CUDA tensors (qllm_amd has no CPU forward path)")
-    if out is None:
-        q_out, k_out = torch.empty_like(q), torch.empty_like(k) if k is not None else None
-        if not all(o is None or _rope_tokens(o, unsqueeze_dim).is_contiguous() for o in (q_out, k_out)):
-            raise QllmUnsupported(_lib.QLLM_ERR_UNSUPPORTED, "rope: the eager result of these inputs is not token-major in memory")
-    else:
-        q_out, k_out = out
-        for name, o, t in (("q_out", q_out, q), ("k_out", k_out, k)):
-            if (o is None) != (t is None):
-                raise RuntimeError(f"rope: {name} must be given exactly when its input is")
-            if t is not None and (o.shape != t.shape or o.dtype != t.dtype or o.device != t.device or not _rope_tokens(o, unsqueeze_dim).is_contiguous()):
-                raise RuntimeError(f"rope: {name} must be a {tuple(t.shape)} {t.dtype} tensor on {t.device} that is dense and token-major in memory")
+    q_out, k_out = _rope_outputs("rope", q, k, cos, sin, unsqueeze_dim, out)
     with torch.cuda.device(q.device):
         rc = _lib.load().qllm_rope(q.data_ptr(), _ptr(k), cos.data_ptr(), sin.data_ptr(), q_out.data_ptr(), _ptr(k_out), rows, hq, hk, d,
                                    q_row, q_head, k_row, k_head, cos_rows, _act_dtype(q), _stream_ptr())
+    _lib.check(rc)
+    return q_out, k_out
+
+
+ROPE_QKNORM_HEAD_DIMS = (64, 128)   # what csrc/rope_qknorm.hip is built for (rope_qknorm_head_dim of csrc/kernels.hpp)
+
+
+def rope_qknorm_plan(q: torch.Tensor, k: Optional[torch.Tensor], q_weight: torch.Tensor, k_weight: Optional[torch.Tensor], eps: float, cos: torch.Tensor,
+                     sin: torch.Tensor, unsqueeze_dim: int = 1):
+    """What `rope_qknorm` hands to qllm_rope_qknorm for these tensors -- `rope_plan`'s answer, by `rope_plan`'s rules -- or QllmUnsupported
+    with the reason; on top of those rules: head_dim 64 or 128, each weight a contiguous, 16-byte aligned [head_dim] tensor of q's type on
+    q's device (k_weight exactly when k is given), eps finite and > 0.  Pure host code, any device."""
+    plan = rope_plan(q, k, cos, sin, unsqueeze_dim)
+    d = plan[3]
+
+    def no(why):
+        return QllmUnsupported(_lib.QLLM_ERR_UNSUPPORTED, "rope_qknorm: " + why)
+    if d not in ROPE_QKNORM_HEAD_DIMS:
+        raise no(f"head_dim must be 64 or 128 (got {d})")
+    if (k is None) != (k_weight is None):
+        raise no("k_weight must be given exactly when k is")
+    for name, w in (("q_weight", q_weight),) + ((("k_weight", k_weight),) if k is not None else ()):
+        if not isinstance(w, torch.Tensor) or w.dim() != 1 or w.shape[0] != d:
+            raise no(f"{name} must be a [{d}] tensor (got {tuple(w.shape) if isinstance(w, torch.Tensor) else type(w).__name__})")
+        if w.dtype != q.dtype or w.device != q.device:
+            raise no(f"{name} must be of q's type and device, {q.dtype} on {q.device} (got {w.dtype} on {w.device})")
+        if not w.is_contiguous() or w.data_ptr() % 16:
+            raise no(f"{name} must be contiguous and 16-byte aligned")
+    if not (eps > 0 and math.isfinite(eps)):
+        raise no(f"eps must be finite and > 0 (got {eps})")
+    return plan
+
+
+def rope_qknorm(q: torch.Tensor, k: Optional[torch.Tensor], q_weight: torch.Tensor, k_weight: Optional[torch.Tensor], eps: float, cos: torch.Tensor,
+                sin: torch.Tensor, unsqueeze_dim: int = 1, *, out=None, plan=None):
+    """`rope(norm(q, q_weight), norm(k, k_weight), cos, sin, unsqueeze_dim)` with norm the RMSNorm over head_dim of every (token, head) --
+    what Qwen3's attention computes between its q / k projections and the attention core (q_norm, k_norm, apply_rotary_pos_emb) -- in
+    ONE kernel (qllm_rope_qknorm, csrc/rope_qknorm.hip).  Bit for bit `rope(rmsnorm(q_c, q_weight, eps), rmsnorm(k_c, k_weight, eps), ...)`
+    on contiguous [B, S, H, D] copies, with every rounding of the eager modules.  Shapes, strides, `out` and `plan` are `rope`'s:
+    `rope_qknorm_plan` says what is served, everything else raises QllmUnsupported before anything is launched."""
+    rows, hq, hk, d, q_row, q_head, k_row, k_head, cos_rows = plan if plan is not None else rope_qknorm_plan(q, k, q_weight, k_weight, eps, cos, sin,
+                                                                                                             unsqueeze_dim)
+    q_out, k_out = _rope_outputs("rope_qknorm", q, k, cos, sin, unsqueeze_dim, out)
+    with torch.cuda.device(q.device):
+        rc = _lib.load().qllm_rope_qknorm(q.data_ptr(), _ptr(k), cos.data_ptr(), sin.data_ptr(), q_out.data_ptr(), _ptr(k_out), q_weight.data_ptr(),
+                                          _ptr(k_weight), float(eps), rows, hq, hk, d, q_row, q_head, k_row, k_head, cos_rows, _act_dtype(q), _stream_ptr())
     _lib.check(rc)
     return q_out, k_out
 
@@ -1549,4 +1603,4 @@ def unpack_native(w: QllmWeight, keep, layout: str):
 __all__ = ["make_weight", "linear_forward", "linear_forward_grouped", "linear_forward_permuted", "linear_forward_bitpanel", "bitpanel_describe", "linear_forward_bitgemm", "bitgemm_describe", "bitgemm_min_m", "linear_forward_bitgroup", "bitgroup_describe", "linear_forward_swiglu", "swiglu_describe", "linear_forward_residual", "linear_forward_swiglu_residual", "residual_describe", "rmsnorm", "linear_forward_rmsnorm", "rmsnorm_describe", "linear_forward_shared", "dequant", "gather_columns", "gather_describe", "unpack_qweight", "pack_qweight",
            "workspace", "QllmUnsupported", "LAYOUTS", "plan_describe", "repack_native", "unpack_native", "hqq_quantize", "gptq_quantize",
            "gptq_quantize_static", "awq_quantize", "awq_clip_search", "attn_chunk_quant", "attn_chunk_quant_plan", "attn_chunk_quant_describe",
-           "attn_prefill_quant", "attn_prefill_quant_plan", "attn_prefill_quant_describe"]
+           "attn_prefill_quant", "attn_prefill_quant_plan", "attn_prefill_quant_describe", "rope_qknorm", "rope_qknorm_plan"]
