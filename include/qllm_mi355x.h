@@ -524,6 +524,33 @@ int qllm_rope_qknorm(const void *q, const void *k, const void *cos, const void *
                      const void *k_weight, float eps, int32_t rows, int32_t q_heads, int32_t k_heads, int32_t head_dim, int64_t q_row_stride,
                      int64_t q_head_stride, int64_t k_row_stride, int64_t k_head_stride, int32_t cos_rows, int32_t act_dtype, void *stream);
 
+/* ---- routed experts of a sparse mixture-of-experts block at decode (Mixtral, Qwen3-MoE) --------------------------------------------------- */
+/* The experts of a sparse MoE block for T = 1..4 tokens as TWO launches (csrc/moe_decode.hip), whatever the routing, with no host
+ * synchronisation: slot = t * top_k + j, e = ids[slot],
+ *   qllm_moe_gate_up:  h[slot] = round(silu(round(x[t] . Wgate[e])) as the eager act_fn(g) * u rounds it) -- [T * top_k, I]
+ *   qllm_moe_down:     y[t] = sum_j round(round(h[slot] . Wdown[e]) * weights[slot]), added in ASCENDING expert id, one rounding to act_dtype
+ *                      per add -- the order and the roundings of transformers' index_add_ loop; one store per output, no atomics.
+ * Layers: 4 bits, 128-wide groups, in the native strip-major layout (QLLM_LAYOUT_NATIVE) and STACKED per expert: expert e of a [K -> N]
+ * kind lies at qweight + e * N * K / 8 words, scales + e * N * K / 128 halves, qzeros + e * N * K / 1024 words; qzeros NULL: the
+ * symmetric grid (zero point 8).  gate / up: [H -> I]; down: [I -> H].  W is s (q - z) unrounded, sums in fp32.
+ * ids: int64 [T, top_k] ON THE DEVICE, as torch.topk leaves them; a slot whose id is outside [0, E) reads nothing and adds nothing (E is
+ * transformers' masked-expert sentinel).  weights: [T, top_k] of weights_dtype, QLLM_F32 or act_dtype.  x, y: contiguous [T, H] of
+ * act_dtype (QLLM_F16 / QLLM_BF16); h: contiguous [T * top_k, I], rows of unserved slots are neither written nor read.
+ * QLLM_ERR_INVALID: a NULL pointer (qzeros excepted), gate_qzeros given without up_qzeros or the reverse, a pointer that is not aligned (16
+ * bytes; ids 8; weights their element), T / top_k / E / H / I < 1, add_zero_bias other than 0 / 1, a bad dtype code.
+ * QLLM_ERR_UNSUPPORTED: T > 4, top_k > 8, E > 2^24, H % 128 != 0, I % 128 != 0, H > 16384.  Every error is raised before any device
+ * work.  No workspace; hipGraph-capturable, and a captured pair serves every later content of ids and weights.
+ * qllm_moe_describe: the launch shapes of the pair for (T, top_k, E, H, I) as text, or "refused: ..." (QLLM_OK) -- pure host code.
+ * Not built: the router, more than 4 tokens, other bit widths or group sizes, shared experts, expert parallelism.
+ * ABI: the symbols are ADDITIVE within ABI 7 (QLLM_ABI_VERSION is unchanged): probe for them by symbol. */
+int qllm_moe_gate_up(const void *x, const void *ids, const void *gate_qweight, const void *gate_scales, const void *gate_qzeros,
+                     const void *up_qweight, const void *up_scales, const void *up_qzeros, void *h, int32_t T, int32_t top_k, int32_t E, int32_t H,
+                     int32_t I, int32_t add_zero_bias, int32_t act_dtype, void *stream);
+int qllm_moe_down(const void *h, const void *ids, const void *weights, const void *down_qweight, const void *down_scales, const void *down_qzeros,
+                  void *y, int32_t T, int32_t top_k, int32_t E, int32_t H, int32_t I, int32_t add_zero_bias, int32_t weights_dtype, int32_t act_dtype,
+                  void *stream);
+int qllm_moe_describe(int32_t T, int32_t top_k, int32_t E, int32_t H, int32_t I, char *buf, size_t buflen);
+
 /* ---- single-token attention over the KV cache -------------------------------------------------------------------------------------------- */
 /* out = softmax(scaling * q K^T + mask) V for ONE query token per sequence against caches [batch, kv_heads, max_len, head_dim] of which
  * the first kv_len positions count, in ONE launch (csrc/attn_decode.hip, flash-decoding): a block owns one (batch entry, kv head, split of

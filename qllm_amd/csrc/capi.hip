@@ -1075,6 +1075,73 @@ int qllm_rope_qknorm(const void *q, const void *k, const void *cos, const void *
                             k_head_stride, cos_rows, act_dtype == QLLM_BF16, (hipStream_t)stream);
 }
 
+// ---- the routed experts of a sparse MoE block at decode (moe_decode.hip) ---------------------------------------------------------------------
+// The host rules the three entries share: the sizes first (qllm_moe_describe has nothing else), then what the kernels serve.
+static int check_moe_shape(int32_t T, int32_t top_k, int32_t E, int32_t H, int32_t I) {
+  if (T <= 0 || top_k <= 0 || E <= 0 || H <= 0 || I <= 0)
+    return set_error(QLLM_ERR_INVALID, "T, top_k, E, H and I must be >= 1 (got T=%d top_k=%d E=%d H=%d I=%d)", T, top_k, E, H, I);
+  if (T > kMoeMaxTokens) return set_error(QLLM_ERR_UNSUPPORTED, "moe_decode serves 1..%d tokens (got %d)", kMoeMaxTokens, T);
+  if (top_k > kMoeMaxTopK) return set_error(QLLM_ERR_UNSUPPORTED, "moe_decode serves top_k 1..%d (got %d)", kMoeMaxTopK, top_k);
+  if (E > (1 << 24)) return set_error(QLLM_ERR_UNSUPPORTED, "moe_decode serves up to 2^24 experts (got %d)", E);
+  if (H % 128 != 0 || I % 128 != 0)
+    return set_error(QLLM_ERR_UNSUPPORTED, "moe_decode serves 128-wide groups: H %% 128 == 0 and I %% 128 == 0 (got H=%d I=%d)", H, I);
+  if (H > kMoeMaxH) return set_error(QLLM_ERR_UNSUPPORTED, "moe_decode serves H <= %d (got %d)", kMoeMaxH, H);
+  return QLLM_OK;
+}
+// one stack of layers: packed words and scales, zero points or NULL (symmetric), 16-byte aligned
+static int check_moe_stack(const char *name, const void *qweight, const void *scales, const void *qzeros) {
+  if (!qweight || !scales) return set_error(QLLM_ERR_INVALID, "%s_qweight / %s_scales must not be NULL", name, name);
+  if ((uintptr_t)qweight % 16 || (uintptr_t)scales % 16 || (uintptr_t)qzeros % 16)
+    return set_error(QLLM_ERR_INVALID, "%s_qweight / %s_scales / %s_qzeros must be 16-byte aligned", name, name, name);
+  return QLLM_OK;
+}
+static int check_moe_call(int32_t add_zero_bias, int32_t act_dtype) {
+  if (add_zero_bias != 0 && add_zero_bias != 1) return set_error(QLLM_ERR_INVALID, "add_zero_bias must be 0 or 1 (got %d)", add_zero_bias);
+  if (act_dtype != QLLM_F16 && act_dtype != QLLM_BF16) return set_error(QLLM_ERR_INVALID, "act_dtype must be QLLM_F16 or QLLM_BF16");
+  return QLLM_OK;
+}
+
+int qllm_moe_gate_up(const void *x, const void *ids, const void *gate_qweight, const void *gate_scales, const void *gate_qzeros, const void *up_qweight,
+                     const void *up_scales, const void *up_qzeros, void *h, int32_t T, int32_t top_k, int32_t E, int32_t H, int32_t I, int32_t add_zero_bias,
+                     int32_t act_dtype, void *stream) {
+  clear_error();
+  if (!x || !ids || !h) return set_error(QLLM_ERR_INVALID, "x / ids / h must not be NULL");
+  if (int rc = check_moe_stack("gate", gate_qweight, gate_scales, gate_qzeros)) return rc;
+  if (int rc = check_moe_stack("up", up_qweight, up_scales, up_qzeros)) return rc;
+  if ((gate_qzeros == nullptr) != (up_qzeros == nullptr)) return set_error(QLLM_ERR_INVALID, "gate_qzeros and up_qzeros must both be given or both be NULL");
+  if ((uintptr_t)x % 16 || (uintptr_t)ids % 8 || (uintptr_t)h % 16) return set_error(QLLM_ERR_INVALID, "x / h must be 16-byte and ids 8-byte aligned");
+  if (int rc = check_moe_call(add_zero_bias, act_dtype)) return rc;
+  if (int rc = check_moe_shape(T, top_k, E, H, I)) return rc;
+  const MoeGateUpParams p{x, (const int64_t *)ids, (const uint32_t *)gate_qweight, (const uint32_t *)up_qweight, (const half_t *)gate_scales,
+                          (const half_t *)up_scales, (const uint32_t *)gate_qzeros, (const uint32_t *)up_qzeros, h, top_k, E, H, I, add_zero_bias};
+  return launch_moe_gate_up(p, T, act_dtype == QLLM_BF16, (hipStream_t)stream);
+}
+
+int qllm_moe_down(const void *h, const void *ids, const void *weights, const void *down_qweight, const void *down_scales, const void *down_qzeros, void *y,
+                  int32_t T, int32_t top_k, int32_t E, int32_t H, int32_t I, int32_t add_zero_bias, int32_t weights_dtype, int32_t act_dtype, void *stream) {
+  clear_error();
+  if (!h || !ids || !weights || !y) return set_error(QLLM_ERR_INVALID, "h / ids / weights / y must not be NULL");
+  if (int rc = check_moe_stack("down", down_qweight, down_scales, down_qzeros)) return rc;
+  if (int rc = check_moe_call(add_zero_bias, act_dtype)) return rc;
+  if (weights_dtype != QLLM_F32 && weights_dtype != act_dtype) return set_error(QLLM_ERR_INVALID, "weights_dtype must be QLLM_F32 or act_dtype");
+  if ((uintptr_t)h % 16 || (uintptr_t)ids % 8 || (uintptr_t)y % 16 || (uintptr_t)weights % (weights_dtype == QLLM_F32 ? 4 : 2))
+    return set_error(QLLM_ERR_INVALID, "h / y must be 16-byte aligned, ids 8-byte, weights to their element");
+  if (int rc = check_moe_shape(T, top_k, E, H, I)) return rc;
+  const MoeDownParams p{h, (const int64_t *)ids, weights, (const uint32_t *)down_qweight, (const half_t *)down_scales, (const uint32_t *)down_qzeros, y,
+                        top_k, E, H, I, add_zero_bias, weights_dtype == QLLM_F32};
+  return launch_moe_down(p, T, act_dtype == QLLM_BF16, (hipStream_t)stream);
+}
+
+int qllm_moe_describe(int32_t T, int32_t top_k, int32_t E, int32_t H, int32_t I, char *buf, size_t buflen) {
+  clear_error();
+  if (!buf || buflen == 0) return set_error(QLLM_ERR_INVALID, "buf must not be NULL");
+  if (int rc = check_moe_shape(T, top_k, E, H, I)) return describe_refusal(rc, kRefused, buf, buflen);
+  const int ga = H / 128, gb = top_k * (I / 128);
+  snprintf(buf, buflen, "moe_decode gate_up grid=%dx%d waves=%d groups_per_wave=%d lds=%d | down grid=%dx%d waves=%d groups_per_wave=%d", I / 16, T * top_k,
+           kMoeWavesA, (ga + kMoeWavesA - 1) / kMoeWavesA, H * 2 + kMoeWavesA * 128, H / 16, T, kMoeWavesB, (gb + kMoeWavesB - 1) / kMoeWavesB);
+  return QLLM_OK;
+}
+
 // ---- attention over the KV cache: the host rules of the decode and the prefill entries, each written once -----------------------------------
 // What differs between the two kernels is an argument: the name in the "%s serves ..." texts, the pointers and strides an entry has and
 // the words its texts call them by.  The entries call these in one order -- the call,

@@ -294,6 +294,39 @@ int launch_rope_qknorm(const void *q, const void *k, const void *cos, const void
                        float eps, int rows, int q_heads, int k_heads, int head_dim, int64_t q_row_stride, int64_t q_head_stride, int64_t k_row_stride,
                        int64_t k_head_stride, int cos_rows, int act_bf16, hipStream_t stream);
 
+// ---- moe_decode.hip: the routed experts of a sparse MoE block at T <= 4 tokens as two launches (moe_decode_kernel.hpp has the format) -----
+constexpr int kMoeMaxTokens = 4;     // T: decode and the verify step of assisted generation; above it the modules loop
+constexpr int kMoeMaxTopK = 8;
+constexpr int kMoeMaxH = 16384;      // gate / up: x[t] is staged through LDS by at most kMoeXChunks 16-byte loads per thread
+constexpr int kMoeWavesA = 8, kMoeThreadsA = kMoeWavesA * 64;
+constexpr int kMoeWavesB = 16, kMoeThreadsB = kMoeWavesB * 64;
+constexpr int kMoeRound = 4;         // groups a wave has in flight per matrix before its first wait
+constexpr int kMoeXChunks = kMoeMaxH / 8 / kMoeThreadsA;
+
+struct MoeGateUpParams {
+  const void *x;                      // [T, H]
+  const int64_t *ids;                 // [T * top_k]
+  const uint32_t *gq, *uq;            // gate / up stacks
+  const half_t *gs, *us;
+  const uint32_t *gz, *uz;            // NULL: symmetric
+  void *h;                            // [T * top_k, I]
+  int top_k, E, H, I, add_zero_bias;
+};
+
+struct MoeDownParams {
+  const void *h;                      // [T * top_k, I]
+  const int64_t *ids;                 // [T * top_k]
+  const void *weights;                // [T * top_k] float32 or the activation type
+  const uint32_t *dq;
+  const half_t *ds;
+  const uint32_t *dz;
+  void *y;                            // [T, H]
+  int top_k, E, H, I, add_zero_bias, weights_f32;
+};
+
+int launch_moe_gate_up(const MoeGateUpParams &p, int T, int act_bf16, hipStream_t stream);
+int launch_moe_down(const MoeDownParams &p, int T, int act_bf16, hipStream_t stream);
+
 // ---- attn_decode.hip: one query token per sequence against the first kv_len positions of a KV cache (flash-decoding) ---------------------
 constexpr int kAttnDecodeMaxGroup = 8;    // query heads per kv head
 constexpr int kAttnDecodeMaxSplits = 32;  // blocks per (batch entry, kv head)

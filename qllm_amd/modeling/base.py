@@ -159,7 +159,10 @@ def load_quantized(model_dir: str, device: Optional[str] = "cuda", torch_dtype: 
     over the device (ops.attn_chunk).  The value "codes" is "split" with one more route in front: on a quantized static cache
     (modeling/quant_cache.py) those calls read the codes in place (ops.attn_chunk_quant) and dequantise no row into memory.  The value "codes_all" is "codes" with one more route behind that one: every
     other call with two or more query tokens on such a cache -- the prompt, chunks of any size -- reads the codes in place too
-    (ops.attn_prefill_quant)."""
+    (ops.attn_prefill_quant).
+    Always: a sparse MoE block (Mixtral, Qwen3-MoE) whose checkpoint holds per-expert `.qweight` tensors gets a `QuantExperts`
+    (q_layers/quant_experts.py) for its experts; model.quant_experts counts the blocks, and load_report["quantized_layers"] includes
+    their layers."""
     import transformers
 
     hf_cfg = transformers.AutoConfig.from_pretrained(model_dir)
@@ -184,9 +187,23 @@ def load_quantized(model_dir: str, device: Optional[str] = "cuda", torch_dtype: 
         sd = _load_file(f)
         keys.update(sd.keys())
         shards.append(sd)
+    # Mixtral checkpoints call the sparse block `block_sparse_moe`; transformers 5.x builds it as `mlp` (and renames on from_pretrained)
+    old, new = ".block_sparse_moe.", ".mlp."
+    if any(old in k for k in keys) and not any(old in n + "." for n, _ in model.named_modules()):
+        shards = [{k.replace(old, new): v for k, v in sd.items()} for sd in shards]
+        keys = {k.replace(old, new) for k in keys}
     linears = modelutils.find_layers(model, [torch.nn.Linear])
     quantized = [n for n in linears if n + ".qweight" in keys]
     target = swap_quantized_linears(model, quantized, cfg)
+    # the experts of a sparse MoE block are 3-D parameters, not nn.Linears: per-expert q_layers under the checkpoint's names (quant_experts.py)
+    from .q_layers import install_quant_experts
+    expert_layers = []
+
+    def expert_layer(k, n, name):
+        info = cfg.by_layer.get(name, {"wbits": cfg.bits, "groupsize": cfg.group_size})
+        expert_layers.append(name)
+        return target(info["wbits"], info["groupsize"], k, n, name + ".bias" in keys, dtype=dtype)
+    model.quant_experts = install_quant_experts(model, keys, expert_layer)
     model.tie_weights()
     missing, unexpected = [], []
     for sd in shards:
@@ -199,7 +216,7 @@ def load_quantized(model_dir: str, device: Optional[str] = "cuda", torch_dtype: 
         for _, layer in modelutils.find_layers(model, [target]).items():
             layer.handle_qzeros_for_autogptq()
         cfg.compatible_with_autogptq = False  # zeros are now stored plainly (base.py:314-319)
-    model.load_report = dict(quantized_layers=len(quantized), unexpected_keys=unexpected)
+    model.load_report = dict(quantized_layers=len(quantized) + len(expert_layers), unexpected_keys=unexpected)
     if device is not None:
         model = model.to(device)
     if release_reference and os.environ.get("QLLM_RELEASE_REFERENCE", "1") != "0":

@@ -9,3 +9,4 @@ from .fused_norm import install_fused_norm, make_quant_norm, uninstall_fused_nor
 from .fused_residual import install_fused_residual, uninstall_fused_residual  # noqa: F401
 from .fused_rope import install_fused_rope, uninstall_fused_rope  # noqa: F401
 from .fused_attention import install_fused_attention, uninstall_fused_attention  # noqa: F401
+from .quant_experts import QuantExperts, install_quant_experts  # noqa: F401

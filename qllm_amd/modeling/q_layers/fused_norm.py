@@ -29,12 +29,13 @@ from . import _patching
 from ._hip_forward import _act_tensors_ok, tensor_version
 from .fused_mlp import DEFAULT_MLP_TYPES
 
-DEFAULT_LAYER_TYPES = ("LlamaDecoderLayer", "MistralDecoderLayer", "Qwen2DecoderLayer", "Qwen3DecoderLayer")
-DEFAULT_NORM_TYPES = ("LlamaRMSNorm", "MistralRMSNorm", "Qwen2RMSNorm", "Qwen3RMSNorm")
+# (Mixtral, Qwen3-MoE: the attention side and the norms; a layer whose mlp is a sparse block keeps its own forward -- quant_experts.py)
+DEFAULT_LAYER_TYPES = ("LlamaDecoderLayer", "MistralDecoderLayer", "Qwen2DecoderLayer", "Qwen3DecoderLayer", "MixtralDecoderLayer", "Qwen3MoeDecoderLayer")
+DEFAULT_NORM_TYPES = ("LlamaRMSNorm", "MistralRMSNorm", "Qwen2RMSNorm", "Qwen3RMSNorm", "MixtralRMSNorm", "Qwen3MoeRMSNorm")
 # (a Qwen3 attention also holds q_norm / k_norm, Qwen3RMSNorms of width head_dim over [B, S, H, D]: no decoder-layer norm, so
 # install_fused_norm leaves them alone; make_quant_norm gives them ops.rmsnorm's forward, which takes any leading dimensions, and
 # fused_rope.py's restated forward reads their weight and variance_epsilon, which no install touches)
-ATTENTION_TYPES = tuple(f"{fam}{kind}" for fam in ("Llama", "Mistral", "Qwen2", "Qwen3") for kind in ("Attention", "SdpaAttention", "FlashAttention2", "FlashAttention"))
+ATTENTION_TYPES = tuple(f"{fam}{kind}" for fam in ("Llama", "Mistral", "Qwen2", "Qwen3", "Mixtral", "Qwen3Moe") for kind in ("Attention", "SdpaAttention", "FlashAttention2", "FlashAttention"))
 _ORIGINAL = "_qllm_unfused_norm_forward"   # on a norm module: the instance forward it had (None: the class's)
 _PRENORM = "_qllm_prenorm"                 # on a consumer: (PreNorm, the instance forward it had or None)
 

@@ -181,7 +181,7 @@ def _known(attn):
         return None
     if not all(hasattr(attn, n) for n in ("head_dim", "layer_idx", "config", "scaling", "attention_dropout")):
         return None
-    window = "config" if name.startswith("Mistral") else "self" if name.startswith(("Qwen2", "Qwen3")) else None
+    window = "config" if name.startswith(("Mistral", "Mixtral")) else "self" if name.startswith(("Qwen2", "Qwen3")) else None
     if window == "self" and not hasattr(attn, "sliding_window"):
         return None
     if _has_qk_norm(attn) and not _qk_norm_ok(attn):

@@ -638,6 +638,142 @@ def rope_qknorm(q: torch.Tensor, k: Optional[torch.Tensor], q_weight: torch.Tens
     return q_out, k_out
 
 
+MOE_MAX_TOKENS, MOE_MAX_TOP_K, MOE_MAX_H = 4, 8, 16384   # kMoeMaxTokens, kMoeMaxTopK, kMoeMaxH of csrc/kernels.hpp
+
+
+def _moe_no(why):
+    return QllmUnsupported(_lib.QLLM_ERR_UNSUPPORTED, "moe_decode: " + why)
+
+
+def _moe_stack(name: str, stack, device):
+    """(E, K, N) of one stack of expert layers -- (qweight int32 [E, N/16, K/8, 16], scales float16 [E, N/16, K/128, 16], qzeros int32
+    [E, N/16, K/128, 2] or None): the native strip-major layout of 4-bit, 128-wide-group layers, expert after expert -- or QllmUnsupported."""
+    if not isinstance(stack, (tuple, list)) or len(stack) != 3 or not all(isinstance(t, torch.Tensor) for t in stack[:2]):
+        raise _moe_no(f"{name} must be (qweight, scales, qzeros or None) tensors")
+    qw, sc, qz = stack
+    if qw.dim() != 4 or qw.shape[3] != 16 or qw.dtype != torch.int32:
+        raise _moe_no(f"{name} qweight must be int32 [E, N/16, K/8, 16] (got {qw.dtype} {tuple(qw.shape)})")
+    e, ns, k8 = qw.shape[:3]
+    if k8 % 16 or e == 0 or ns == 0 or k8 == 0:
+        raise _moe_no(f"{name}: K must be a positive multiple of 128 (4 bits, 128-wide groups; got K={8 * k8})")
+    if sc.dtype != torch.float16 or tuple(sc.shape) != (e, ns, k8 // 16, 16):
+        raise _moe_no(f"{name} scales must be float16 {(e, ns, k8 // 16, 16)} (got {sc.dtype} {tuple(sc.shape)})")
+    if qz is not None and (not isinstance(qz, torch.Tensor) or qz.dtype != torch.int32 or tuple(qz.shape) != (e, ns, k8 // 16, 2)):
+        raise _moe_no(f"{name} qzeros must be None or int32 {(e, ns, k8 // 16, 2)}")
+    for t in (qw, sc) + ((qz,) if qz is not None else ()):
+        if t.device != device or not t.is_contiguous() or t.data_ptr() % 16:
+            raise _moe_no(f"{name}: the stack must be contiguous, 16-byte aligned and on {device}")
+    return e, 8 * k8, 16 * ns
+
+
+def _moe_routing(ids, weights, t: int, act_dtype, device):
+    """top_k of ids [T, top_k] (int64, as torch.topk leaves them) and, when given, weights [T, top_k] (float32 or the activation type)."""
+    if not isinstance(ids, torch.Tensor) or ids.dim() != 2 or ids.shape[0] != t or ids.dtype != torch.int64 or not ids.is_contiguous() or ids.device != device:
+        raise _moe_no(f"ids must be a contiguous int64 [{t}, top_k] tensor on {device}")
+    top_k = ids.shape[1]
+    if not 1 <= top_k <= MOE_MAX_TOP_K:
+        raise _moe_no(f"top_k 1..{MOE_MAX_TOP_K} (got {top_k})")
+    if weights is not None and (not isinstance(weights, torch.Tensor) or weights.shape != ids.shape or weights.dtype not in (torch.float32, act_dtype)
+                                or not weights.is_contiguous() or weights.device != device):
+        raise _moe_no(f"weights must be a contiguous float32 or {act_dtype} {tuple(ids.shape)} tensor on {device}")
+    return top_k
+
+
+def _moe_act(name: str, x, rows, cols):
+    if (not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype not in (torch.float16, torch.bfloat16) or not x.is_contiguous() or x.data_ptr() % 16
+            or (rows is not None and x.shape[0] != rows) or (cols is not None and x.shape[1] != cols)):
+        raise _moe_no(f"{name} must be a contiguous, 16-byte aligned float16 / bfloat16 [{rows if rows is not None else 'T'}, {cols if cols is not None else 'H'}] tensor")
+    return x.shape
+
+
+def _moe_sizes(t: int, h: int, i: int):
+    if not 1 <= t <= MOE_MAX_TOKENS:
+        raise _moe_no(f"1..{MOE_MAX_TOKENS} tokens (got {t}): more rows are the modules' loop")
+    if h % 128 or i % 128 or h > MOE_MAX_H:
+        raise _moe_no(f"H % 128 == 0, I % 128 == 0 and H <= {MOE_MAX_H} (got H={h} I={i})")
+
+
+def moe_plan(x: torch.Tensor, ids: torch.Tensor, weights: torch.Tensor, gate, up, down):
+    """What `moe_gate_up` and `moe_down` are launched with for these tensors -- (T, top_k, E, H, I) -- or QllmUnsupported with the reason:
+    the ONE place that says whether a routed-experts call is served.  x [T, H] float16 / bfloat16, contiguous, T = 1..4; ids int64
+    [T, top_k], top_k = 1..8; weights [T, top_k] float32 or x's type; gate / up / down: stacks of E experts (`_moe_stack`) of shapes
+    [H -> I], [H -> I], [I -> H] with H % 128 == 0, I % 128 == 0, H <= 16384, packed zero points in all three or in none; everything on
+    one device; and, measured, one token or 2 * T * top_k <= E (below that many experts the tokens share them, and the loop, which
+    reads a shared expert once, wins).  The two launchers themselves take every T <= 4.  Pure host code, any device."""
+    t, h = _moe_act("x", x, None, None)
+    top_k = _moe_routing(ids, weights, t, x.dtype, x.device)
+    if weights is None:
+        raise _moe_no("weights must be given")
+    (e, kg, ng), (eu, ku, nu), (ed, kd, nd) = (_moe_stack(n, s, x.device) for n, s in (("gate", gate), ("up", up), ("down", down)))
+    if (eu, ku, nu) != (e, kg, ng) or (ed, kd, nd) != (e, ng, kg) or kg != h:
+        raise _moe_no(f"gate and up must be [{h} -> I] and down [I -> {h}] stacks of one expert count (got {(e, kg, ng)}, {(eu, ku, nu)}, {(ed, kd, nd)})")
+    if len({s[2] is None for s in (gate, up, down)}) != 1:
+        raise _moe_no("the three stacks must all have packed zero points or all be symmetric")
+    _moe_sizes(t, h, ng)
+    if t > 1 and 2 * t * top_k > e:
+        # measured (profiles/moe_decode.md): the launches read one expert per SLOT, the loop each hit expert once for all its tokens; at
+        # Mixtral's E = 8, top_k = 2 the pair wins at 2 tokens (x1.30), ties at 3 and loses at 4 (x0.85); at Qwen3-30B-A3B's E = 128 it wins 14-16-fold
+        raise _moe_no(f"with {t} tokens x top_k {top_k} slots over {e} experts the loop reads each hit expert once and is faster (served: T == 1 or 2 * T * top_k <= E)")
+    return t, top_k, e, h, ng
+
+
+def moe_describe(t: int, top_k: int, e: int, h: int, i: int) -> str:
+    """The launch shapes of the pair ("moe_decode gate_up grid=896x2 waves=8 ... | down grid=256x1 waves=16 ..."), or "refused: ...".
+    Pure host code."""
+    return _describe("qllm_moe_describe", 256, int(t), int(top_k), int(e), int(h), int(i))
+
+
+def _moe_out(name: str, out, shape, like: torch.Tensor):
+    if out is None:
+        return torch.empty(shape, dtype=like.dtype, device=like.device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != like.dtype or out.device != like.device or not out.is_contiguous() or out.data_ptr() % 16:
+        raise RuntimeError(f"{name} must be a contiguous, 16-byte aligned {tuple(shape)} {like.dtype} tensor on {like.device}")
+    return out
+
+
+def moe_gate_up(x: torch.Tensor, ids: torch.Tensor, gate, up, *, add_zero_bias: int = 0, out=None) -> torch.Tensor:
+    """h[t * top_k + j] = act_fn(x[t] . Wgate[e]) * (x[t] . Wup[e]) with e = ids[t, j], SiLU and the eager roundings, for every slot in ONE
+    launch (qllm_moe_gate_up, csrc/moe_decode.hip): [T * top_k, I].  The expert ids are read on the device; the row of a slot whose id is
+    outside [0, E) is left unwritten.  `moe_plan` says what is served; everything else raises QllmUnsupported before anything is launched."""
+    t, h = _moe_act("x", x, None, None)
+    top_k = _moe_routing(ids, None, t, x.dtype, x.device)
+    (e, kg, ng), (eu, ku, nu) = _moe_stack("gate", gate, x.device), _moe_stack("up", up, x.device)
+    if (eu, ku, nu) != (e, kg, ng) or kg != h or (gate[2] is None) != (up[2] is None):
+        raise _moe_no(f"gate and up must be [{h} -> I] stacks of one expert count and one kind of zero point")
+    _moe_sizes(t, h, ng)
+    if not x.is_cuda:
+        raise RuntimeError("moe_gate_up: x must be a HIP/CUDA tensor (qllm_amd has no CPU forward path)")
+    out = _moe_out("out", out, (t * top_k, ng), x)
+    with torch.cuda.device(x.device):
+        rc = _lib.load().qllm_moe_gate_up(x.data_ptr(), ids.data_ptr(), gate[0].data_ptr(), gate[1].data_ptr(), _ptr(gate[2]), up[0].data_ptr(),
+                                          up[1].data_ptr(), _ptr(up[2]), out.data_ptr(), t, top_k, e, h, ng, int(add_zero_bias), _act_dtype(x), _stream_ptr())
+    _lib.check(rc)
+    return out
+
+
+def moe_down(h: torch.Tensor, ids: torch.Tensor, weights: torch.Tensor, down, *, add_zero_bias: int = 0, out=None) -> torch.Tensor:
+    """y[t] = sum_j ((h[t * top_k + j] . Wdown[e]) * weights[t, j]) with e = ids[t, j]: the down projections of every slot and the routed
+    sum in ONE launch (qllm_moe_down, csrc/moe_decode.hip): [T, H].  Each projection is rounded to the activation type, its product with
+    the weight again, and the products are added in ascending expert id with one rounding per add -- transformers' index_add_ loop,
+    rounding for rounding; the same bits on every call.  Slots whose id is outside [0, E) add nothing.  `moe_plan` says what is served."""
+    e, i, hh = _moe_stack("down", down, h.device)
+    top_k = _moe_routing(ids, weights, ids.shape[0] if isinstance(ids, torch.Tensor) and ids.dim() == 2 else 0, h.dtype, h.device)
+    if weights is None:
+        raise _moe_no("weights must be given")
+    t = ids.shape[0]
+    _moe_act("h", h, t * top_k, i)
+    _moe_sizes(t, hh, i)
+    if not h.is_cuda:
+        raise RuntimeError("moe_down: h must be a HIP/CUDA tensor (qllm_amd has no CPU forward path)")
+    out = _moe_out("out", out, (t, hh), h)
+    wdt = _lib.DT_F32 if weights.dtype == torch.float32 else _act_dtype(h)
+    with torch.cuda.device(h.device):
+        rc = _lib.load().qllm_moe_down(h.data_ptr(), ids.data_ptr(), weights.data_ptr(), down[0].data_ptr(), down[1].data_ptr(), _ptr(down[2]),
+                                       out.data_ptr(), t, top_k, e, hh, i, int(add_zero_bias), wdt, _act_dtype(h), _stream_ptr())
+    _lib.check(rc)
+    return out
+
+
 ATTN_DECODE_HEAD_DIMS = (64, 128)   # what csrc/attn_decode.hip is built for
 ATTN_DECODE_MAX_GROUP = 8           # kAttnDecodeMaxGroup of csrc/kernels.hpp
 ATTN_DECODE_COUNTERS = 4096         # kCounterBytes / sizeof(int) of csrc/planner.hpp: attn_decode takes one arrival counter per (sequence, kv
@@ -1603,4 +1739,4 @@ def unpack_native(w: QllmWeight, keep, layout: str):
 __all__ = ["make_weight", "linear_forward", "linear_forward_grouped", "linear_forward_permuted", "linear_forward_bitpanel", "bitpanel_describe", "linear_forward_bitgemm", "bitgemm_describe", "bitgemm_min_m", "linear_forward_bitgroup", "bitgroup_describe", "linear_forward_swiglu", "swiglu_describe", "linear_forward_residual", "linear_forward_swiglu_residual", "residual_describe", "rmsnorm", "linear_forward_rmsnorm", "rmsnorm_describe", "linear_forward_shared", "dequant", "gather_columns", "gather_describe", "unpack_qweight", "pack_qweight",
            "workspace", "QllmUnsupported", "LAYOUTS", "plan_describe", "repack_native", "unpack_native", "hqq_quantize", "gptq_quantize",
            "gptq_quantize_static", "awq_quantize", "awq_clip_search", "attn_chunk_quant", "attn_chunk_quant_plan", "attn_chunk_quant_describe",
-           "attn_prefill_quant", "attn_prefill_quant_plan", "attn_prefill_quant_describe", "rope_qknorm", "rope_qknorm_plan"]
+           "attn_prefill_quant", "attn_prefill_quant_plan", "attn_prefill_quant_describe", "rope_qknorm", "rope_qknorm_plan", "moe_gate_up", "moe_down", "moe_plan", "moe_describe"]
