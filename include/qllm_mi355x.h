@@ -551,6 +551,38 @@ int qllm_moe_down(const void *h, const void *ids, const void *weights, const voi
                   void *stream);
 int qllm_moe_describe(int32_t T, int32_t top_k, int32_t E, int32_t H, int32_t I, char *buf, size_t buflen);
 
+/* ---- routed experts of a sparse mixture-of-experts block for prompts and batches (csrc/moe_prefill.hip) ----------------------------------- */
+/* The same block for any T >= 1 (meant for T > 4) with S = T * top_k <= 65536 slots and E <= 1024 experts as FOUR launches from three
+ * calls, whatever the routing, with no host synchronisation; same layers, stacks, ids, weights and tensors as the decode pair above.
+ *   qllm_moe_route:            reads ids on the device and writes the routing table at the head of `workspace`: per-expert counts, the
+ *                              slots sorted by expert (stable: equal experts in ascending slot), every expert's segment padded to whole
+ *                              row tiles of `tile_rows` rows (padding rows hold -1), per row tile its expert and first sorted row, the
+ *                              number of row tiles.  Slots whose id is outside [0, E) are dropped.  One block, a counting sort: the same
+ *                              table for the same ids on every call.
+ *   qllm_moe_prefill_gate_up:  h[slot] as qllm_moe_gate_up -- a grouped MFMA GEMM whose row tiles belong to different experts and whose
+ *                              rows x[slot / top_k] are gathered by the table; g and u never reach memory.  [T * top_k, I] in slot order.
+ *   qllm_moe_prefill_down:     round(round(h[slot] . Wdown[e]) * weights[slot]) per slot into the workspace (the same grouped GEMM), then
+ *                              y[t] = the sum of its slots' rows in ascending expert id (equal ids: ascending slot), one rounding per add
+ *                              from +0: qllm_moe_down's value.  No atomics on the outputs; the same bits on every call.
+ * tile_rows: 16 or 64 (the built heights), or 0: 64 where T * top_k / E >= 32, else 16; the three calls of one block take the same value.
+ * The grid of the two GEMMs is the host-known bound T * top_k / tile_rows + min(E, T * top_k) row tiles; blocks past the table's count leave.
+ * workspace: 256-byte aligned, qllm_moe_prefill_workspace_bytes(T, top_k, E, H, I) bytes (a pure function; 0 for sizes that are refused):
+ * the table and the [T * top_k, H] product rows.  qllm_moe_route needs only the table's share and accepts any size that covers it.
+ * QLLM_ERR_INVALID: a NULL pointer (qzeros excepted), unaligned pointers, T / top_k / E / H / I < 1, a tile_rows other than 0 / 16 / 64,
+ * add_zero_bias other than 0 / 1, a bad dtype code, a workspace that is too small.  QLLM_ERR_UNSUPPORTED: T * top_k > 65536, E > 1024,
+ * top_k > 8, H % 128 != 0, I % 128 != 0.  Every error is raised before any device work.  hipGraph-capturable.
+ * qllm_moe_prefill_describe: tile height, grids and LDS per kernel as text, or "refused: ..." (QLLM_OK) -- pure host code.
+ * ABI: the symbols are ADDITIVE within ABI 7 (QLLM_ABI_VERSION is unchanged): probe for them by symbol. */
+size_t qllm_moe_prefill_workspace_bytes(int32_t T, int32_t top_k, int32_t E, int32_t H, int32_t I);
+int qllm_moe_route(const void *ids, void *workspace, size_t workspace_bytes, int32_t T, int32_t top_k, int32_t E, int32_t tile_rows, void *stream);
+int qllm_moe_prefill_gate_up(const void *x, const void *workspace, size_t workspace_bytes, const void *gate_qweight, const void *gate_scales,
+                             const void *gate_qzeros, const void *up_qweight, const void *up_scales, const void *up_qzeros, void *h, int32_t T,
+                             int32_t top_k, int32_t E, int32_t H, int32_t I, int32_t tile_rows, int32_t add_zero_bias, int32_t act_dtype, void *stream);
+int qllm_moe_prefill_down(const void *h, const void *ids, const void *weights, void *workspace, size_t workspace_bytes, const void *down_qweight,
+                          const void *down_scales, const void *down_qzeros, void *y, int32_t T, int32_t top_k, int32_t E, int32_t H, int32_t I,
+                          int32_t tile_rows, int32_t add_zero_bias, int32_t weights_dtype, int32_t act_dtype, void *stream);
+int qllm_moe_prefill_describe(int32_t T, int32_t top_k, int32_t E, int32_t H, int32_t I, int32_t tile_rows, char *buf, size_t buflen);
+
 /* ---- single-token attention over the KV cache -------------------------------------------------------------------------------------------- */
 /* out = softmax(scaling * q K^T + mask) V for ONE query token per sequence against caches [batch, kv_heads, max_len, head_dim] of which
  * the first kv_len positions count, in ONE launch (csrc/attn_decode.hip, flash-decoding): a block owns one (batch entry, kv head, split of

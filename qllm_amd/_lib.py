@@ -112,6 +112,11 @@ SIGNATURES = {
     "qllm_moe_gate_up": (C.c_int, [vp] * 9 + [i32] * 7 + [vp]),
     "qllm_moe_down": (C.c_int, [vp] * 7 + [i32] * 8 + [vp]),
     "qllm_moe_describe": (C.c_int, [i32, i32, i32, i32, i32, C.c_char_p, sz]),
+    "qllm_moe_prefill_workspace_bytes": (sz, [i32] * 5),
+    "qllm_moe_route": (C.c_int, [vp, vp, sz] + [i32] * 4 + [vp]),
+    "qllm_moe_prefill_gate_up": (C.c_int, [vp, vp, sz] + [vp] * 7 + [i32] * 8 + [vp]),
+    "qllm_moe_prefill_down": (C.c_int, [vp] * 4 + [sz] + [vp] * 4 + [i32] * 9 + [vp]),
+    "qllm_moe_prefill_describe": (C.c_int, [i32] * 6 + [C.c_char_p, sz]),
     "qllm_attn_decode": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i64, vp, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, i32, i64, i64,
                                    C.c_float, i32, vp, sz, vp]),
     "qllm_attn_decode_workspace_bytes": (sz, [i32, i32, i32, i32, i64]),

@@ -1142,6 +1142,96 @@ int qllm_moe_describe(int32_t T, int32_t top_k, int32_t E, int32_t H, int32_t I,
   return QLLM_OK;
 }
 
+// ---- the routed experts above four tokens (moe_prefill.hip): route, grouped gate/up, grouped down + combine ------------------------------------
+static int check_moe_prefill_shape(int32_t T, int32_t top_k, int32_t E, int32_t H, int32_t I, int32_t tile_rows) {
+  if (T <= 0 || top_k <= 0 || E <= 0 || H <= 0 || I <= 0)
+    return set_error(QLLM_ERR_INVALID, "T, top_k, E, H and I must be >= 1 (got T=%d top_k=%d E=%d H=%d I=%d)", T, top_k, E, H, I);
+  if (tile_rows != 0 && tile_rows != kMoePrefillTileLo && tile_rows != kMoePrefillTileHi)
+    return set_error(QLLM_ERR_INVALID, "tile_rows must be 0, %d or %d (got %d)", kMoePrefillTileLo, kMoePrefillTileHi, tile_rows);
+  if (top_k > kMoeMaxTopK) return set_error(QLLM_ERR_UNSUPPORTED, "moe_prefill serves top_k 1..%d (got %d)", kMoeMaxTopK, top_k);
+  if ((int64_t)T * top_k > kMoePrefillMaxSlots)
+    return set_error(QLLM_ERR_UNSUPPORTED, "moe_prefill serves T * top_k <= %d slots per call (got %lld)", kMoePrefillMaxSlots, (long long)T * top_k);
+  if (E > kMoePrefillMaxExperts) return set_error(QLLM_ERR_UNSUPPORTED, "moe_prefill serves up to %d experts (got %d)", kMoePrefillMaxExperts, E);
+  if (H % 128 != 0 || I % 128 != 0)
+    return set_error(QLLM_ERR_UNSUPPORTED, "moe_prefill serves 128-wide groups: H %% 128 == 0 and I %% 128 == 0 (got H=%d I=%d)", H, I);
+  return QLLM_OK;
+}
+static int check_moe_workspace(const void *workspace, size_t have, size_t need) {
+  if (!workspace) return set_error(QLLM_ERR_INVALID, "workspace must not be NULL");
+  if ((uintptr_t)workspace % 256) return set_error(QLLM_ERR_INVALID, "workspace must be 256-byte aligned");
+  if (have < need) return set_error(QLLM_ERR_INVALID, "workspace too small: %zu bytes, need %zu", have, need);
+  return QLLM_OK;
+}
+static size_t moe_prefill_bytes(int32_t T, int32_t top_k, int32_t E, int32_t H) {
+  return moe_route_table(T * top_k, E).bytes + ((size_t)T * top_k * H * 2 + 255) / 256 * 256;
+}
+static int moe_tile(int32_t T, int32_t top_k, int32_t E, int32_t tile_rows) { return tile_rows ? tile_rows : moe_prefill_tile_rows(T * top_k, E); }
+
+size_t qllm_moe_prefill_workspace_bytes(int32_t T, int32_t top_k, int32_t E, int32_t H, int32_t I) {
+  clear_error();
+  if (check_moe_prefill_shape(T, top_k, E, H, I, 0)) return 0;
+  return moe_prefill_bytes(T, top_k, E, H);
+}
+
+int qllm_moe_route(const void *ids, void *workspace, size_t workspace_bytes, int32_t T, int32_t top_k, int32_t E, int32_t tile_rows, void *stream) {
+  clear_error();
+  if (!ids) return set_error(QLLM_ERR_INVALID, "ids must not be NULL");
+  if ((uintptr_t)ids % 8) return set_error(QLLM_ERR_INVALID, "ids must be 8-byte aligned");
+  if (int rc = check_moe_prefill_shape(T, top_k, E, 128, 128, tile_rows)) return rc;
+  if (int rc = check_moe_workspace(workspace, workspace_bytes, moe_route_table(T * top_k, E).bytes)) return rc;
+  return launch_moe_route((const int64_t *)ids, (int *)workspace, T * top_k, E, moe_tile(T, top_k, E, tile_rows), (hipStream_t)stream);
+}
+
+int qllm_moe_prefill_gate_up(const void *x, const void *workspace, size_t workspace_bytes, const void *gate_qweight, const void *gate_scales,
+                             const void *gate_qzeros, const void *up_qweight, const void *up_scales, const void *up_qzeros, void *h, int32_t T,
+                             int32_t top_k, int32_t E, int32_t H, int32_t I, int32_t tile_rows, int32_t add_zero_bias, int32_t act_dtype, void *stream) {
+  clear_error();
+  if (!x || !h) return set_error(QLLM_ERR_INVALID, "x / h must not be NULL");
+  if (int rc = check_moe_stack("gate", gate_qweight, gate_scales, gate_qzeros)) return rc;
+  if (int rc = check_moe_stack("up", up_qweight, up_scales, up_qzeros)) return rc;
+  if ((gate_qzeros == nullptr) != (up_qzeros == nullptr)) return set_error(QLLM_ERR_INVALID, "gate_qzeros and up_qzeros must both be given or both be NULL");
+  if ((uintptr_t)x % 16 || (uintptr_t)h % 16) return set_error(QLLM_ERR_INVALID, "x / h must be 16-byte aligned");
+  if (int rc = check_moe_call(add_zero_bias, act_dtype)) return rc;
+  if (int rc = check_moe_prefill_shape(T, top_k, E, H, I, tile_rows)) return rc;
+  const MoeRouteTable tb = moe_route_table(T * top_k, E);
+  if (int rc = check_moe_workspace(workspace, workspace_bytes, tb.bytes)) return rc;
+  const MoePrefillParams p{x, (const int *)workspace, (const uint32_t *)gate_qweight, (const uint32_t *)up_qweight, (const half_t *)gate_scales,
+                           (const half_t *)up_scales, (const uint32_t *)gate_qzeros, (const uint32_t *)up_qzeros, nullptr, h, tb, top_k, H, I, add_zero_bias, 0};
+  return launch_moe_prefill_gemm(p, 0, T * top_k, E, moe_tile(T, top_k, E, tile_rows), act_dtype == QLLM_BF16, (hipStream_t)stream);
+}
+
+int qllm_moe_prefill_down(const void *h, const void *ids, const void *weights, void *workspace, size_t workspace_bytes, const void *down_qweight,
+                          const void *down_scales, const void *down_qzeros, void *y, int32_t T, int32_t top_k, int32_t E, int32_t H, int32_t I,
+                          int32_t tile_rows, int32_t add_zero_bias, int32_t weights_dtype, int32_t act_dtype, void *stream) {
+  clear_error();
+  if (!h || !ids || !weights || !y) return set_error(QLLM_ERR_INVALID, "h / ids / weights / y must not be NULL");
+  if (int rc = check_moe_stack("down", down_qweight, down_scales, down_qzeros)) return rc;
+  if (int rc = check_moe_call(add_zero_bias, act_dtype)) return rc;
+  if (weights_dtype != QLLM_F32 && weights_dtype != act_dtype) return set_error(QLLM_ERR_INVALID, "weights_dtype must be QLLM_F32 or act_dtype");
+  if ((uintptr_t)h % 16 || (uintptr_t)ids % 8 || (uintptr_t)y % 16 || (uintptr_t)weights % (weights_dtype == QLLM_F32 ? 4 : 2))
+    return set_error(QLLM_ERR_INVALID, "h / y must be 16-byte aligned, ids 8-byte, weights to their element");
+  if (int rc = check_moe_prefill_shape(T, top_k, E, H, I, tile_rows)) return rc;
+  const MoeRouteTable tb = moe_route_table(T * top_k, E);
+  if (int rc = check_moe_workspace(workspace, workspace_bytes, moe_prefill_bytes(T, top_k, E, H))) return rc;
+  void *prod = (char *)workspace + tb.bytes;
+  const MoePrefillParams p{h, (const int *)workspace, (const uint32_t *)down_qweight, nullptr, (const half_t *)down_scales, nullptr,
+                           (const uint32_t *)down_qzeros, nullptr, weights, prod, tb, top_k, I, H, add_zero_bias, weights_dtype == QLLM_F32};
+  if (int rc = launch_moe_prefill_gemm(p, 1, T * top_k, E, moe_tile(T, top_k, E, tile_rows), act_dtype == QLLM_BF16, (hipStream_t)stream)) return rc;
+  const MoeCombineParams c{prod, (const int64_t *)ids, y, top_k, E, H};
+  return launch_moe_combine(c, T, act_dtype == QLLM_BF16, (hipStream_t)stream);
+}
+
+int qllm_moe_prefill_describe(int32_t T, int32_t top_k, int32_t E, int32_t H, int32_t I, int32_t tile_rows, char *buf, size_t buflen) {
+  clear_error();
+  if (!buf || buflen == 0) return set_error(QLLM_ERR_INVALID, "buf must not be NULL");
+  if (int rc = check_moe_prefill_shape(T, top_k, E, H, I, tile_rows)) return describe_refusal(rc, kRefused, buf, buflen);
+  const int bm = moe_tile(T, top_k, E, tile_rows), tiles = moe_prefill_max_tiles(T * top_k, E, bm);
+  snprintf(buf, buflen, "moe_prefill tile_rows=%d route grid=1 waves=%d lds=%zu | gate_up grid=%dx%d waves=%d lds=%zu | down grid=%dx%d waves=%d lds=%zu | combine grid=%dx%d",
+           bm, kMoeRouteWaves, moe_route_lds_bytes(E), tiles, I / 64, kMoePrefillWaves, moe_prefill_lds_bytes(bm), tiles, H / 128, kMoePrefillWaves,
+           moe_prefill_lds_bytes(bm), (H / 8 + 255) / 256, T);
+  return QLLM_OK;
+}
+
 // ---- attention over the KV cache: the host rules of the decode and the prefill entries, each written once -----------------------------------
 // What differs between the two kernels is an argument: the name in the "%s serves ..." texts, the pointers and strides an entry has and
 // the words its texts call them by.  The entries call these in one order -- the call,

@@ -327,6 +327,58 @@ struct MoeDownParams {
 int launch_moe_gate_up(const MoeGateUpParams &p, int T, int act_bf16, hipStream_t stream);
 int launch_moe_down(const MoeDownParams &p, int T, int act_bf16, hipStream_t stream);
 
+// ---- moe_prefill.hip: the routed experts above kMoeMaxTokens tokens -- route, grouped gate/up + SwiGLU, grouped down, combine (MFMA) ----------
+constexpr int kMoePrefillMaxSlots = 65536;    // S = T * top_k per call
+constexpr int kMoePrefillMaxExperts = 1024;
+constexpr int kMoePrefillTileLo = 16, kMoePrefillTileHi = 64;   // the two built row-tile heights
+constexpr int kMoePrefillWaves = 4, kMoePrefillThreads = kMoePrefillWaves * 64;
+constexpr int kMoePrefillKT = 256;            // k per A tile in LDS (two groups)
+constexpr int kMoeRouteWaves = 16, kMoeRouteThreads = kMoeRouteWaves * 64;
+
+// The routing table at the head of the workspace, in ints; a pure function of (S, E), the same for both tile heights:
+//   [0] row tiles  [1] tile height  (16 ints) | counts[E] | tile_expert[max_tiles] | tile_row0[max_tiles] | sorted[cap_rows]
+// followed, 256-byte aligned, by the per-slot product rows [S, H] of the activation type.
+struct MoeRouteTable {
+  int counts, tile_expert, tile_row0, sorted, max_tiles, cap_rows;
+  size_t bytes;                               // of the table, rounded up to 256
+};
+inline int moe_prefill_max_tiles(int S, int E, int BM) { return S / BM + (E < S ? E : S); }
+inline MoeRouteTable moe_route_table(int S, int E) {
+  MoeRouteTable t;
+  t.max_tiles = moe_prefill_max_tiles(S, E, kMoePrefillTileLo);                        // (the low tile has the most tiles,
+  t.cap_rows = moe_prefill_max_tiles(S, E, kMoePrefillTileHi) * kMoePrefillTileHi;     //  the high tile the most padded rows)
+  t.counts = 16;
+  t.tile_expert = t.counts + E;
+  t.tile_row0 = t.tile_expert + t.max_tiles;
+  t.sorted = t.tile_row0 + t.max_tiles;
+  t.bytes = ((size_t)(t.sorted + t.cap_rows) * 4 + 255) / 256 * 256;
+  return t;
+}
+inline int moe_prefill_tile_rows(int S, int E) { return S / E >= 32 ? kMoePrefillTileHi : kMoePrefillTileLo; }   // from T * top_k / E only
+
+struct MoePrefillParams {
+  const void *a;                      // gate/up: x [T, H]; down: h [S, I]
+  const int *table;                   // the routing table
+  const uint32_t *q0, *q1;            // gate, up stacks; down: q0 only
+  const half_t *s0, *s1;
+  const uint32_t *z0, *z1;            // NULL: symmetric
+  const void *weights;                // down: [S] float32 or the activation type
+  void *out;                          // gate/up: h [S, I]; down: the product rows [S, H]
+  MoeRouteTable tb;
+  int top_k, K, N, add_zero_bias, weights_f32;
+};
+struct MoeCombineParams {
+  const void *prod;                   // [S, H]
+  const int64_t *ids;
+  void *y;                            // [T, H]
+  int top_k, E, H;
+};
+int launch_moe_route(const int64_t *ids, int *table, int S, int E, int tile_rows, hipStream_t stream);
+int launch_moe_prefill_gemm(const MoePrefillParams &p, int down, int S, int E, int tile_rows, int act_bf16, hipStream_t stream);
+int launch_moe_combine(const MoeCombineParams &p, int T, int act_bf16, hipStream_t stream);
+size_t moe_prefill_lds_bytes(int tile_rows);
+size_t moe_route_lds_bytes(int E);
+
 // ---- attn_decode.hip: one query token per sequence against the first kv_len positions of a KV cache (flash-decoding) ---------------------
 constexpr int kAttnDecodeMaxGroup = 8;    // query heads per kv head
 constexpr int kAttnDecodeMaxSplits = 32;  // blocks per (batch entry, kv head)

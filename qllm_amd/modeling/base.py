@@ -142,7 +142,8 @@ def release_reference_layouts(model: torch.nn.Module, on: bool = True) -> int:
 
 def load_quantized(model_dir: str, device: Optional[str] = "cuda", torch_dtype: Optional[torch.dtype] = None,
                    release_reference: bool = True, fuse_mlp: bool = False, fuse_norm: bool = False, fuse_residual: bool = False,
-                   fuse_rope: bool = False, fuse_attention: bool = False, fuse_attention_prefill: bool = False):
+                   fuse_rope: bool = False, fuse_attention: bool = False, fuse_attention_prefill: bool = False,
+                   fuse_moe_prefill: bool = False):
     """Local equivalent of AutoQuantizedModelForCausalLM.from_quantized (base.py:226-322).  `release_reference`: see
     release_reference_layouts (QLLM_RELEASE_REFERENCE=0 in the environment keeps both copies).  `fuse_mlp` (opt-in): fold
     act_fn(gate) * up of the SwiGLU MLPs into the down_proj launch (q_layers/fused_mlp.py); model.fused_mlps counts the modules.
@@ -162,7 +163,9 @@ def load_quantized(model_dir: str, device: Optional[str] = "cuda", torch_dtype: 
     (ops.attn_prefill_quant).
     Always: a sparse MoE block (Mixtral, Qwen3-MoE) whose checkpoint holds per-expert `.qweight` tensors gets a `QuantExperts`
     (q_layers/quant_experts.py) for its experts; model.quant_experts counts the blocks, and load_report["quantized_layers"] includes
-    their layers."""
+    their layers.  `fuse_moe_prefill` (opt-in): those blocks also run calls of more than four tokens -- prompts, chunks, batched decode
+    -- as the routed launches of ops.moe_route / moe_prefill_gate_up / moe_prefill_down instead of the loop over the hit experts
+    (QLLM_FUSE_MOE_PREFILL=0 or QLLM_FUSE_MOE=0 force the loop)."""
     import transformers
 
     hf_cfg = transformers.AutoConfig.from_pretrained(model_dir)
@@ -203,7 +206,7 @@ def load_quantized(model_dir: str, device: Optional[str] = "cuda", torch_dtype: 
         info = cfg.by_layer.get(name, {"wbits": cfg.bits, "groupsize": cfg.group_size})
         expert_layers.append(name)
         return target(info["wbits"], info["groupsize"], k, n, name + ".bias" in keys, dtype=dtype)
-    model.quant_experts = install_quant_experts(model, keys, expert_layer)
+    model.quant_experts = install_quant_experts(model, keys, expert_layer, fuse_moe_prefill=fuse_moe_prefill)
     model.tie_weights()
     missing, unexpected = [], []
     for sd in shards:

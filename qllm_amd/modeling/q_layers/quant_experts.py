@@ -6,12 +6,13 @@ nowhere to go.  `QuantExperts` holds one q_layer per expert and projection under
 `experts.<e>.w1 / w3 / w2` (gate, up, down), Qwen3-MoE `experts.<e>.gate_proj / up_proj / down_proj` -- so load_state_dict fills them
 and state_dict writes them back (a Mixtral under transformers' `mlp`, not the checkpoint's `block_sparse_moe`).
 
-Two routes.  Where `ops.moe_plan` serves the call -- 1..4 tokens, 4-bit layers with 128-wide groups, packed or symmetric zero points,
+Three routes.  Where `ops.moe_plan` serves the call -- 1..4 tokens, 4-bit layers with 128-wide groups, packed or symmetric zero points,
 native copies -- the block is TWO launches (ops.moe_gate_up, ops.moe_down; csrc/moe_decode.hip) that read the expert ids on the device:
 nothing goes back to the host, so a decode step captures into a graph.  For that the native copies of each projection are stacked per
 expert in one allocation, made once; every layer's native buffers become views of its slice (`_hip_forward.py`'s native-copy policy: the
 layer regenerates its reference buffers from them, and `release_reference` keeps working), so nothing is stored twice.  Everything else
--- prefill, other bit widths or group sizes, HQQ's fp16 zero points, act-order layers, a CPU device, grad mode, QLLM_FUSE_MOE=0 -- is
+-- more tokens (unless `fuse_moe_prefill` is on: then ops.moe_route / moe_prefill_gate_up / moe_prefill_down, csrc/moe_prefill.hip, serve
+the same layers for any number of tokens as four launches, equally captured), other bit widths or group sizes, HQQ's fp16 zero points, act-order layers, a CPU device, grad mode, QLLM_FUSE_MOE=0 -- is
 the family's own loop restated over the per-expert q_layers (one_hot, nonzero, per hit expert three layer calls, index_add_)."""
 from __future__ import annotations
 
@@ -44,6 +45,7 @@ class QuantExperts(nn.ModuleList):
         self.__dict__["act_fn"] = act_fn   # (not a child: the list's children are the experts, and the state dict holds only their buffers)
         self._stacks = None   # ((qweight, scales, qzeros) x gate, up, down, add_zero_bias), False (not stackable) or None (not built)
         self._installed, self._refused, self._revalidate = None, set(), False   # the slices given to the layers; refused forms
+        self.fuse_moe_prefill = False   # opt-in (install_quant_experts): more than ops.MOE_MAX_TOKENS tokens as the routed launches
 
     @classmethod
     def from_experts(cls, experts, names, make_layer):
@@ -121,8 +123,11 @@ class QuantExperts(nn.ModuleList):
         return tuple(stacks) + (azb,)
 
     def _fused_plan(self, hidden_states, top_k_index, top_k_weights):
-        """(plan, stacks) where the two launches serve this call, else None."""
-        if (os.environ.get("QLLM_FUSE_MOE", "1") == "0" or hidden_states.dim() != 2 or not 1 <= hidden_states.shape[0] <= ops.MOE_MAX_TOKENS
+        """(plan, stacks) where fused launches serve this call -- 1..4 tokens: the decode pair (`ops.moe_plan`, 5 sizes); more, with
+        `fuse_moe_prefill` on: the routed launches (`ops.moe_prefill_plan`, 6 sizes, for the first chunk of rows) -- else None."""
+        many = hidden_states.dim() == 2 and hidden_states.shape[0] > ops.MOE_MAX_TOKENS
+        if (os.environ.get("QLLM_FUSE_MOE", "1") == "0" or hidden_states.dim() != 2 or hidden_states.shape[0] < 1
+                or (many and (not self.fuse_moe_prefill or os.environ.get("QLLM_FUSE_MOE_PREFILL", "1") == "0"))
                 or not _act_tensors_ok(hidden_states) or not top_k_index.is_cuda or not top_k_weights.is_cuda
                 or (torch.is_grad_enabled() and top_k_weights.requires_grad)):
             return None
@@ -136,10 +141,17 @@ class QuantExperts(nn.ModuleList):
         if not self._stacks or key in self._refused:
             return None
         try:
+            if many:
+                rows = self._chunk_rows(top_k_index)
+                return ops.moe_prefill_plan(hidden_states[:rows], top_k_index[:rows], top_k_weights[:rows], *self._stacks[:3]), self._stacks
             return ops.moe_plan(hidden_states, top_k_index, top_k_weights, *self._stacks[:3]), self._stacks
         except ops.QllmUnsupported:
             self._refused.add(key)   # (a form is refused for its sizes and types: not asked again, the loop runs on every step of it)
             return None
+
+    @staticmethod
+    def _chunk_rows(top_k_index):
+        return max(1, ops.MOE_PREFILL_MAX_SLOTS // max(1, top_k_index.shape[-1]))   # rows of one routed call
 
     def _check_stacks(self):
         """After a state_dict() (the layers materialised their reference buffers) and whenever the first layer's native copy is no longer
@@ -159,7 +171,16 @@ class QuantExperts(nn.ModuleList):
         served = self._fused_plan(x, ids, wts)
         if served is None:
             return self.forward_loop(hidden_states, top_k_index, top_k_weights)
-        _, (gate, up, down, azb) = served
+        plan, (gate, up, down, azb) = served
+        if len(plan) == 6:      # the routed launches; rows are independent, so calls of more slots than one call serves go in row chunks
+            out, rows = torch.empty_like(x), self._chunk_rows(ids)
+            for r in range(0, x.shape[0], rows):
+                xs, ic, wc = x[r:r + rows], ids[r:r + rows], wts[r:r + rows]
+                nbytes = ops.moe_prefill_workspace_bytes(xs.shape[0], ic.shape[1], self.num_experts, xs.shape[1], gate[0].shape[1] * 16)
+                route = ops.moe_route(ic, self.num_experts, workspace=torch.empty(nbytes, dtype=torch.uint8, device=x.device))
+                h = ops.moe_prefill_gate_up(xs, ic, route, gate, up, add_zero_bias=azb)
+                ops.moe_prefill_down(h, ic, wc, route, down, add_zero_bias=azb, out=out[r:r + rows])
+            return out
         h = ops.moe_gate_up(x, ids, gate, up, add_zero_bias=azb)
         return ops.moe_down(h, ids, wts, down, add_zero_bias=azb)
 
@@ -182,10 +203,10 @@ class QuantExperts(nn.ModuleList):
         return final
 
 
-def install_quant_experts(model: nn.Module, keys, make_layer) -> int:
+def install_quant_experts(model: nn.Module, keys, make_layer, fuse_moe_prefill: bool = False) -> int:
     """Put a `QuantExperts` in the place of the experts of every sparse block of `model` (`SPARSE_BLOCKS`) whose per-expert `.qweight`
     tensors `keys` names; the router (`gate`) stays the family's.  `make_layer(in_features, out_features, name)` builds the q_layer of
-    the module called `name`.  Returns how many blocks were given one."""
+    the module called `name`.  `fuse_moe_prefill`: the modules' opt-in of the same name.  Returns how many blocks were given one."""
     n = 0
     for name, block in list(model.named_modules()):
         names = SPARSE_BLOCKS.get(type(block).__name__)
@@ -194,5 +215,6 @@ def install_quant_experts(model: nn.Module, keys, make_layer) -> int:
             continue
         prefix = f"{name}.experts"
         block.experts = QuantExperts.from_experts(experts, names, lambda k, o, e, proj: make_layer(k, o, f"{prefix}.{e}.{proj}"))
+        block.experts.fuse_moe_prefill = bool(fuse_moe_prefill)
         n += 1
     return n

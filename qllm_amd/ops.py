@@ -774,6 +774,171 @@ def moe_down(h: torch.Tensor, ids: torch.Tensor, weights: torch.Tensor, down, *,
     return out
 
 
+MOE_PREFILL_MAX_SLOTS, MOE_PREFILL_MAX_EXPERTS, MOE_PREFILL_TILES = 65536, 1024, (16, 64)   # kMoePrefill* of csrc/kernels.hpp
+
+
+def _moe_pre_no(why):
+    return QllmUnsupported(_lib.QLLM_ERR_UNSUPPORTED, "moe_prefill: " + why)
+
+
+class MoeRoute:
+    """What `moe_route` made: the workspace whose head holds the routing table on the device, and the sizes it was made for."""
+    __slots__ = ("workspace", "tokens", "top_k", "num_experts", "tile_rows")
+
+    def __init__(self, workspace, tokens, top_k, num_experts, tile_rows):
+        self.workspace, self.tokens, self.top_k, self.num_experts, self.tile_rows = workspace, tokens, top_k, num_experts, tile_rows
+
+    def table(self):
+        """(tiles, counts [E], sorted slots of the tiles' rows [tiles * tile_rows] with -1 in padding rows, tile_expert [tiles], tile_row0
+        [tiles]) read back from the device -- for tests and tools; nothing on the forward path calls it."""
+        s, e = self.tokens * self.top_k, self.num_experts
+        lo, hi = MOE_PREFILL_TILES
+        max_tiles = s // lo + min(e, s)
+        ints = self.workspace.view(torch.int32)
+        tiles = int(ints[0])
+        c0, te, t0 = 16, 16 + e, 16 + e + max_tiles
+        srt = t0 + max_tiles
+        return (tiles, ints[c0:c0 + e].cpu(), ints[srt:srt + tiles * self.tile_rows].cpu(), ints[te:te + tiles].cpu(), ints[t0:t0 + tiles].cpu())
+
+
+def _moe_prefill_sizes(t: int, top_k: int, e: int, h: int, i: int, tile_rows):
+    if not 1 <= top_k <= MOE_MAX_TOP_K:
+        raise _moe_pre_no(f"top_k 1..{MOE_MAX_TOP_K} (got {top_k})")
+    if t < 1 or t * top_k > MOE_PREFILL_MAX_SLOTS:
+        raise _moe_pre_no(f"1..{MOE_PREFILL_MAX_SLOTS} slots T * top_k per call (got {t} x {top_k}): cut the rows into chunks")
+    if not 1 <= e <= MOE_PREFILL_MAX_EXPERTS:
+        raise _moe_pre_no(f"1..{MOE_PREFILL_MAX_EXPERTS} experts (got {e})")
+    if h % 128 or i % 128 or h < 128 or i < 128:
+        raise _moe_pre_no(f"H % 128 == 0 and I % 128 == 0 (got H={h} I={i})")
+    if tile_rows is not None and tile_rows not in MOE_PREFILL_TILES:
+        raise _moe_pre_no(f"tile_rows must be None or one of the built heights {MOE_PREFILL_TILES} (got {tile_rows})")
+    return tile_rows if tile_rows is not None else (MOE_PREFILL_TILES[1] if t * top_k // e >= 32 else MOE_PREFILL_TILES[0])
+
+
+def _moe_ids(ids, device=None):
+    if (not isinstance(ids, torch.Tensor) or ids.dim() != 2 or ids.dtype != torch.int64 or not ids.is_contiguous()
+            or (device is not None and ids.device != device)):
+        raise _moe_pre_no(f"ids must be a contiguous int64 [T, top_k] tensor{'' if device is None else f' on {device}'}")
+    return ids.shape
+
+
+def moe_prefill_workspace_bytes(t: int, top_k: int, e: int, h: int, i: int) -> int:
+    """Bytes of the workspace of one routed-experts call: the routing table and the [T * top_k, H] product rows (0: refused sizes)."""
+    return int(_lib.load().qllm_moe_prefill_workspace_bytes(int(t), int(top_k), int(e), int(h), int(i)))
+
+
+def moe_prefill_plan(x: torch.Tensor, ids: torch.Tensor, weights: torch.Tensor, gate, up, down, *, tile_rows=None):
+    """What `moe_route`, `moe_prefill_gate_up` and `moe_prefill_down` are launched with for these tensors -- (T, top_k, E, H, I, tile_rows)
+    -- or QllmUnsupported with the reason.  As `moe_plan`, but any T with T * top_k <= 65536, E <= 1024 and no bound on H; tile_rows None:
+    64 where T * top_k / E >= 32, else 16; and, measured, T <= 512 or T * top_k <= 128 * E (beyond, the loop's GEMMs can win).  The three
+    launchers themselves take every size up to their limits.  Pure host code, any device."""
+    t, h = _moe_act("x", x, None, None)
+    try:
+        top_k = _moe_routing(ids, weights, t, x.dtype, x.device)
+        if weights is None:
+            raise _moe_no("weights must be given")
+        (e, kg, ng), (eu, ku, nu), (ed, kd, nd) = (_moe_stack(n, s, x.device) for n, s in (("gate", gate), ("up", up), ("down", down)))
+    except QllmUnsupported as err:
+        raise _moe_pre_no(str(err).split("moe_decode: ", 1)[-1]) from None
+    if (eu, ku, nu) != (e, kg, ng) or (ed, kd, nd) != (e, ng, kg) or kg != h:
+        raise _moe_pre_no(f"gate and up must be [{h} -> I] and down [I -> {h}] stacks of one expert count (got {(e, kg, ng)}, {(eu, ku, nu)}, {(ed, kd, nd)})")
+    if len({s[2] is None for s in (gate, up, down)}) != 1:
+        raise _moe_pre_no("the three stacks must all have packed zero points or all be symmetric")
+    bm = _moe_prefill_sizes(t, top_k, e, h, ng, tile_rows)
+    if t > 512 and t * top_k > 128 * e:
+        # measured (profiles/moe_prefill.md): at Mixtral's sizes and 2048 tokens the launches win x1.30 under uniform routing and LOSE x0.89
+        # with every token on two experts -- the loop's GEMMs read an expert once for thousands of rows, a 64-row tile re-reads its panel;
+        # 512 tokens win under both routings.  The routing is not known on the host, so the whole region is the loop's.
+        raise _moe_pre_no(f"with {t} tokens and {t * top_k // e} rows per expert on average the loop's GEMMs can be faster (served: T <= 512 or T * top_k <= 128 * E)")
+    return t, top_k, e, h, ng, bm
+
+
+def moe_prefill_describe(t: int, top_k: int, e: int, h: int, i: int, tile_rows=None) -> str:
+    """Tile height, grids and LDS of the four launches ("moe_prefill tile_rows=16 route grid=1 ... | combine grid=1x16"), or "refused: ...".
+    Pure host code."""
+    return _describe("qllm_moe_prefill_describe", 384, int(t), int(top_k), int(e), int(h), int(i), int(tile_rows or 0))
+
+
+def moe_route(ids: torch.Tensor, num_experts: int, *, tile_rows=None, workspace=None) -> MoeRoute:
+    """The routing table of ids [T, top_k] (int64, on the device) in ONE launch (qllm_moe_route, csrc/moe_prefill.hip): per-expert counts,
+    the slots sorted by expert (stable), every expert's segment padded to row tiles of `tile_rows` rows, per tile its expert and first row.
+    Ids outside [0, num_experts) are dropped.  `workspace`: a uint8 tensor of at least `moe_prefill_workspace_bytes` bytes (the down
+    projection keeps its per-slot rows there); None: the table alone is allocated, enough for `moe_prefill_gate_up`."""
+    t, top_k = _moe_ids(ids)
+    e = int(num_experts)
+    bm = _moe_prefill_sizes(t, top_k, e, 128, 128, tile_rows)
+    if not ids.is_cuda:
+        raise RuntimeError("moe_route: ids must be a HIP/CUDA tensor (qllm_amd has no CPU forward path)")
+    if workspace is None:
+        workspace = torch.empty(moe_prefill_workspace_bytes(t, top_k, e, 128, 128), dtype=torch.uint8, device=ids.device)
+    elif workspace.dtype != torch.uint8 or workspace.device != ids.device or not workspace.is_contiguous() or workspace.data_ptr() % 256:
+        raise RuntimeError(f"workspace must be a contiguous, 256-byte aligned uint8 tensor on {ids.device}")
+    with torch.cuda.device(ids.device):
+        rc = _lib.load().qllm_moe_route(ids.data_ptr(), workspace.data_ptr(), workspace.numel(), t, top_k, e, bm, _stream_ptr())
+    _lib.check(rc)
+    return MoeRoute(workspace, t, top_k, e, bm)
+
+
+def _moe_route_for(route, ids, e):
+    if not isinstance(route, MoeRoute) or (route.tokens, route.top_k) != tuple(ids.shape) or route.num_experts != e or route.workspace.device != ids.device:
+        raise _moe_pre_no(f"route must be moe_route's result for ids {tuple(ids.shape)} over {e} experts on {ids.device}")
+
+
+def moe_prefill_gate_up(x: torch.Tensor, ids: torch.Tensor, route: MoeRoute, gate, up, *, add_zero_bias: int = 0, out=None) -> torch.Tensor:
+    """`moe_gate_up`'s h [T * top_k, I] for any number of tokens: a grouped MFMA GEMM over the row tiles of `route`
+    (qllm_moe_prefill_gate_up, csrc/moe_prefill.hip), the eager roundings, rows of dropped slots left unwritten."""
+    t, h = _moe_act("x", x, None, None)
+    _moe_ids(ids, x.device)
+    try:
+        (e, kg, ng), (eu, ku, nu) = _moe_stack("gate", gate, x.device), _moe_stack("up", up, x.device)
+    except QllmUnsupported as err:
+        raise _moe_pre_no(str(err).split("moe_decode: ", 1)[-1]) from None
+    if (eu, ku, nu) != (e, kg, ng) or kg != h or (gate[2] is None) != (up[2] is None) or ids.shape[0] != t:
+        raise _moe_pre_no(f"gate and up must be [{h} -> I] stacks of one expert count and one kind of zero point, ids [{t}, top_k]")
+    _moe_route_for(route, ids, e)
+    top_k = ids.shape[1]
+    _moe_prefill_sizes(t, top_k, e, h, ng, route.tile_rows)
+    if not x.is_cuda:
+        raise RuntimeError("moe_prefill_gate_up: x must be a HIP/CUDA tensor (qllm_amd has no CPU forward path)")
+    out = _moe_out("out", out, (t * top_k, ng), x)
+    ws = route.workspace
+    with torch.cuda.device(x.device):
+        rc = _lib.load().qllm_moe_prefill_gate_up(x.data_ptr(), ws.data_ptr(), ws.numel(), gate[0].data_ptr(), gate[1].data_ptr(), _ptr(gate[2]),
+                                                  up[0].data_ptr(), up[1].data_ptr(), _ptr(up[2]), out.data_ptr(), t, top_k, e, h, ng, route.tile_rows,
+                                                  int(add_zero_bias), _act_dtype(x), _stream_ptr())
+    _lib.check(rc)
+    return out
+
+
+def moe_prefill_down(h: torch.Tensor, ids: torch.Tensor, weights: torch.Tensor, route: MoeRoute, down, *, add_zero_bias: int = 0, out=None) -> torch.Tensor:
+    """`moe_down`'s y [T, H] for any number of tokens, in two launches of one call (qllm_moe_prefill_down): the grouped down projection
+    writes round(round(d) * w) per slot into the route's workspace, the combine adds a token's rows in ascending expert id with one
+    rounding per add.  The route's workspace must have `moe_prefill_workspace_bytes` bytes."""
+    _moe_ids(ids, h.device if isinstance(h, torch.Tensor) else None)
+    t, top_k = ids.shape
+    try:
+        e, i, hh = _moe_stack("down", down, h.device)
+        _moe_routing(ids, weights, t, h.dtype, h.device)
+        if weights is None:
+            raise _moe_no("weights must be given")
+        _moe_act("h", h, t * top_k, i)
+    except QllmUnsupported as err:
+        raise _moe_pre_no(str(err).split("moe_decode: ", 1)[-1]) from None
+    _moe_route_for(route, ids, e)
+    _moe_prefill_sizes(t, top_k, e, hh, i, route.tile_rows)
+    if not h.is_cuda:
+        raise RuntimeError("moe_prefill_down: h must be a HIP/CUDA tensor (qllm_amd has no CPU forward path)")
+    out = _moe_out("out", out, (t, hh), h)
+    ws = route.workspace
+    wdt = _lib.DT_F32 if weights.dtype == torch.float32 else _act_dtype(h)
+    with torch.cuda.device(h.device):
+        rc = _lib.load().qllm_moe_prefill_down(h.data_ptr(), ids.data_ptr(), weights.data_ptr(), ws.data_ptr(), ws.numel(), down[0].data_ptr(),
+                                               down[1].data_ptr(), _ptr(down[2]), out.data_ptr(), t, top_k, e, hh, i, route.tile_rows, int(add_zero_bias),
+                                               wdt, _act_dtype(h), _stream_ptr())
+    _lib.check(rc)
+    return out
+
+
 ATTN_DECODE_HEAD_DIMS = (64, 128)   # what csrc/attn_decode.hip is built for
 ATTN_DECODE_MAX_GROUP = 8           # kAttnDecodeMaxGroup of csrc/kernels.hpp
 ATTN_DECODE_COUNTERS = 4096         # kCounterBytes / sizeof(int) of csrc/planner.hpp: attn_decode takes one arrival counter per (sequence, kv
@@ -1739,4 +1904,5 @@ def unpack_native(w: QllmWeight, keep, layout: str):
 __all__ = ["make_weight", "linear_forward", "linear_forward_grouped", "linear_forward_permuted", "linear_forward_bitpanel", "bitpanel_describe", "linear_forward_bitgemm", "bitgemm_describe", "bitgemm_min_m", "linear_forward_bitgroup", "bitgroup_describe", "linear_forward_swiglu", "swiglu_describe", "linear_forward_residual", "linear_forward_swiglu_residual", "residual_describe", "rmsnorm", "linear_forward_rmsnorm", "rmsnorm_describe", "linear_forward_shared", "dequant", "gather_columns", "gather_describe", "unpack_qweight", "pack_qweight",
            "workspace", "QllmUnsupported", "LAYOUTS", "plan_describe", "repack_native", "unpack_native", "hqq_quantize", "gptq_quantize",
            "gptq_quantize_static", "awq_quantize", "awq_clip_search", "attn_chunk_quant", "attn_chunk_quant_plan", "attn_chunk_quant_describe",
-           "attn_prefill_quant", "attn_prefill_quant_plan", "attn_prefill_quant_describe", "rope_qknorm", "rope_qknorm_plan", "moe_gate_up", "moe_down", "moe_plan", "moe_describe"]
+           "attn_prefill_quant", "attn_prefill_quant_plan", "attn_prefill_quant_describe", "rope_qknorm", "rope_qknorm_plan", "moe_gate_up", "moe_down", "moe_plan", "moe_describe",
+           "moe_route", "moe_prefill_gate_up", "moe_prefill_down", "moe_prefill_plan", "moe_prefill_describe", "moe_prefill_workspace_bytes", "MoeRoute"]
